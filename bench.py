@@ -44,13 +44,9 @@ import os
 import sys
 import time
 
-# read when libamdhip64 is loaded, i.e. by `import torch`: the update runs on up to six streams, and with the runtime's default
-# of 4 hardware queues the ingest copy shares one with a compute pipeline (srl_amd/hip.py; INTEGRATION.md switches)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.distributed as dist  # noqa: E402
+import numpy as np
+import torch
+import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -505,6 +501,35 @@ def recorded_counters(envs, T, chunk_rows):
     return dict(mfma_busy=None, counters_note="no SQ counter recording under profiles/ at this configuration")
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def step_outputs(res, batch, trainer):
+    """What a caller of ``trainer.step`` receives from one step, as host arrays: the step's statistics, the advantages and
+    returns the step wrote back into the sample, and the updated parameters (checkpoint names and layout)."""
+    out = {f"stats.{k}": np.asarray(v, np.float64) for k, v in sorted(res.stats.items())}
+    for k in ("adv", "ret"):
+        v = getattr(batch.analyzed_result, k)
+        out[k] = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32)
+    for k, v in trainer.policy.get_checkpoint()["state_dict"].items():
+        v = v.detach().cpu().numpy()
+        out[f"param.{k}"] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    return out
+
+
+def dump_outputs(outputs, out_dir):
+    """``DIR/<name>.npy`` per array.  Over DUMP_LIMIT_BYTES in all, every array above its even share of the limit is replaced
+    by a fixed, seeded sample of its elements (flattened, indices in ascending order), so that two builds stay comparable."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(v.nbytes for v in outputs.values())
+    share = DUMP_LIMIT_BYTES // len(outputs)
+    for name, v in outputs.items():
+        if total > DUMP_LIMIT_BYTES and v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -527,6 +552,8 @@ def main():
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` / `scaling_model` objects (the other BASELINE configurations and the per-rank shard)")
     ap.add_argument("--no-mlp", action="store_true", help="skip `roofline_mlp`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step returned as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -578,6 +605,20 @@ def main():
 
     T, B = args.rollout_len, args.global_envs // world
 
+    # The headline's LAST timed update starts from the trainer's initial parameters and optimiser state (--dump-outputs writes
+    # what it computes): its inputs are then the same in every run, and its results repeat up to the rounding of one update
+    # (atomics, stream order).  The updates before it run chained, as a trainer runs them; the ~100 chained updates on one
+    # sample would amplify that rounding into different weights.  The restore is three device copies of the flat buffer.
+    net = trainer.policy.net
+    init_state = (net.flat.clone(), trainer._m.clone(), trainer._v.clone())
+
+    def restore_init():
+        net.flat.copy_(init_state[0])
+        trainer._m.copy_(init_state[1])
+        trainer._v.copy_(init_state[2])
+        trainer._opt_steps = 0
+        net.params_changed()
+
     def sync():
         if use_dist:
             dist.barrier()
@@ -585,7 +626,7 @@ def main():
 
     step_marks = []  # HIP events between the timed steps of the last `timed` call (no synchronisation inside the region)
 
-    def timed(fn, warmup, steps):
+    def timed(fn, warmup, steps, from_init=False):
         for _ in range(warmup):
             fn()
         sync()
@@ -593,6 +634,8 @@ def main():
         t0 = time.perf_counter()
         for i in range(steps):
             marks[i].record()
+            if from_init and i == steps - 1:
+                restore_init()
             r = fn()
         marks[steps].record()
         sync()
@@ -607,6 +650,10 @@ def main():
     def rate(el, steps):
         return T * B * world * steps / el
 
+    def dump_headline(res, batch):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(step_outputs(res, batch, trainer), args.dump_outputs)
+
     # ---- (1) the update with the whole sample resident in HBM, data seeds 0, 1, 2 ---------------------------------
     # one sample at a time (14.9 GB of frames each); the last one (seed 0 + rank offset) stays for the legs below
     seeds = [int(s) for s in args.seeds.split(",")] if args.seeds else [0]
@@ -616,11 +663,14 @@ def main():
         sample = None
         torch.cuda.empty_cache()
         sample = device_sample(1000 * sd + rank, T, B, device)
-        el, res = timed(lambda: trainer.step(sample), args.warmup if i == 0 else 2, args.steps)
+        el, res = timed(lambda: trainer.step(sample), args.warmup if i == 0 else 2, args.steps,
+                        from_init=args.no_from_host and i == len(seeds) - 1)
         ms = sorted(step_marks)
         per_seed[str(sd)] = dict(ms_per_step=1e3 * el / args.steps, ms_per_step_median=ms[len(ms) // 2], ms_per_step_min=ms[0])
         all_marks += ms
         el_res += el
+    if args.no_from_host:  # the resident update is the headline
+        dump_headline(res, sample)
     marks_res = sorted(all_marks)
     n_res = args.steps * len(seeds)
     resident = dict(value=rate(el_res, n_res), unit="env-steps/s", ms_per_step=1e3 * el_res / n_res, steps=n_res,
@@ -730,7 +780,7 @@ def main():
             slot = b.metadata["ring_slot"]
             ring.release(slot)
             ring.recycle(slot)
-            return r
+            return r, b
 
         # ---- (2a) no observation ring: every leaf, frames included, crosses the link inside the timed region ---------------
         if not args.no_plain_copy:
@@ -831,7 +881,9 @@ def main():
         ring.attach_obs_ring(obs_ring)
 
         # ---- (2c) SURVEY 8d's t_update with the ring: the headline ---------------------------------------------------------
-        el_fed, res = timed(fed_step, args.warmup, args.steps)
+        el_fed, (res, last_batch) = timed(fed_step, args.warmup, args.steps, from_init=True)
+        dump_headline(res, last_batch)
+        del last_batch
         marks_fed = sorted(step_marks)
         ms_step = 1e3 * el_fed / args.steps
         scalar_bytes = sum(v.nbytes for k, v in ring.host_blocks(0).items() if k != "obs.obs")

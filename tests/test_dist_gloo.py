@@ -41,6 +41,7 @@ def _worker(rank, world, port, adv, mask, expected, ckpt_flat):
         # parameter broadcast through the policy's own method on a CPU shell
         import srl_amd
         from srl_amd.api import config, policy as policy_api
+        policy_api.resolve_device = lambda: "cpu"  # a CPU shell on a machine with a GPU too (gloo, CPU tensors)
         srl_amd.register_all()
         pol = policy_api.make(config.Policy("actor-critic", args=dict(obs_dim=4, action_dim=2, hidden_dim=8,
                                                                          num_dense_layers=1, num_rnn_layers=0,
