@@ -1,7 +1,7 @@
 #!/bin/bash
-# Build libsrlhip_<tag>.so next to the product library with extra compiler flags on the GEMM / convolution sources
-# (timing experiments: leave-out switches such as -DSRL_GEMM3_DBG=...), reusing every other object of the normal build.
-#   scripts/build_variant.sh noload -DSRL_GEMM3_DBG=1 ;  SRL_HIP_LIB=$PWD/srl_amd/csrc/libsrlhip_noload.so python3 scripts/gemm_bench.py conv
+# Build libsrlhip_<tag>.so of the current tree next to the product library with extra compiler flags on the GEMM / convolution
+# sources (compile-time variants such as -DSRL_OBS_LINE_STORES=0), reusing every other object of the normal build.
+#   scripts/build_variant.sh nolines -DSRL_OBS_LINE_STORES=0 ;  SRL_HIP_LIB=$PWD/srl_amd/csrc/libsrlhip_nolines.so python3 scripts/obs_fwd_bench.py
 set -e
 tag=$1; shift
 cd "$(dirname "$0")/.."

@@ -1,6 +1,5 @@
 """Per-kernel times of the convolution / FC launches of one 16384-row chunk of the benchmark's network, with operand ranges
-(the two-piece f16 kernels) and sign masks as the trainer passes them.  Used with leave-out builds
-(scripts/build_variant.sh <tag> -DSRL_GEMM3_DBG=<bits>; SRL_HIP_LIB=...).  usage: python3 scripts/conv_probe.py [rows]"""
+(the two-piece f16 kernels) and sign masks as the trainer passes them.  usage: python3 scripts/conv_probe.py [rows]"""
 import os
 import sys
 

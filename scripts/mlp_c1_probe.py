@@ -43,4 +43,4 @@ for t in keep[2::4] + keep[3::4]:
 bw()
 torch.cuda.synchronize()
 print(f"rows {rows} tape floats {tld}: y sum {float(y.double().sum()):.6f}  grads " + " ".join(f"{float(t.double().sum()):.5f}" for t in keep[2::4]))
-print(f"fwd {timeit(fw):8.1f} us   bwd {timeit(bw):8.1f} us   SRL_MLP_DBG={os.environ.get('SRL_MLP_DBG', '0')}", flush=True)
+print(f"fwd {timeit(fw):8.1f} us   bwd {timeit(bw):8.1f} us", flush=True)

@@ -1,4 +1,4 @@
-"""Timing only of the first layer's block weight gradient (obs_h2.h), phase 1 (position sums): for the SRL_OBSB_DBG leave-outs."""
+"""Timing only of the first layer's weight gradient, phase 1 (position sums): the block kernel (obs_h2.h) and the bf16 one."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,7 +20,7 @@ dz = (1e-3 * f(n, 400, 32) * (f(n, 400, 32) > 0)).contiguous()
 amax = dz.abs().max().reshape(1).clone()
 wsb = torch.empty(hip.conv2d_obs_bwd_workspace(desc), device=DEV)
 outs = [torch.zeros(32 * 256, device=DEV), torch.zeros(32, device=DEV), torch.zeros(21 * 21 * 64, device=DEV), torch.zeros(21 * 21 * 64, device=DEV)]
-for bound in ([True, False] if os.environ.get("SRL_OBSB_DBG", "0") == "0" else [True]):
+for bound in (True, False):
     run = lambda: hip.conv2d_obs_bwd(desc, s2d.data_ptr(), True, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w.data_ptr(),
                                      dz.data_ptr(), *[o.data_ptr() for o in outs], wsb.data_ptr(), channels_last=True, row_index=rows, phase=1,
                                      dz_absmax_ptr=amax.data_ptr() if bound else None)
@@ -33,4 +33,4 @@ for bound in ([True, False] if os.environ.get("SRL_OBSB_DBG", "0") == "0" else [
         run()
     e.record()
     torch.cuda.synchronize()
-    print(f"obs bwd {'block' if bound else 'bf16 '} DBG={os.environ.get('SRL_OBSB_DBG', '0'):>2s}: {a.elapsed_time(e) / 20 * 1e3:8.1f} us per call", flush=True)
+    print(f"obs bwd {'block' if bound else 'bf16 '}: {a.elapsed_time(e) / 20 * 1e3:8.1f} us per call", flush=True)

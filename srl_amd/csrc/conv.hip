@@ -12,16 +12,6 @@
 
 using namespace srlgemm;
 
-// First-layer block kernels (obs_h2.h): XCD-contiguous numbering of the (position block, sample range) workgroups, so that the
-// blocks an XCD works on are neighbours in the frame and share window rows / columns in ITS L2.  Measured (scripts/obs_xcd_traffic.sh,
-// scripts/ab_bench.sh): the forward's fetched bytes per launch fall by a third (494 -> 326 counter MB), the weight gradient's by a
-// sixth (872 -> 729) -- and the update gets 0.4 ms SLOWER (87.9 / 88.6 -> 88.3 / 89.0 ms, alternating runs on one box): these
-// kernels are bound by their vector work, not by the frames' bytes.  Opt-in (SRL_OBS_XCD=1).
-static int obs_xcd_order() {
-  static const int v = [] { const char* e = getenv("SRL_OBS_XCD"); return (e && e[0] == '1') ? 1 : 0; }();
-  return v;
-}
-
 namespace {
 
 constexpr int K3 = 16;  // k-step depth of the bf16x3 kernels (48 KB of LDS per 128x128 workgroup: three per CU)
@@ -696,7 +686,6 @@ static int conv2d_obs_fwd_run(void* stream, const srl_conv_desc* d, const void* 
       long nsplit = nblk < 256 ? 256 / nblk : 1;
       if (nsplit > ntiles) nsplit = ntiles;
       h.nsplit = (int)nsplit;
-      h.xcd = obs_xcd_order();
       const unsigned grid = (unsigned)(nblk * nsplit);
       constexpr int lds = srlobs::kStages * srlobs::kStageBytes + srlobs::kMeta * srlobs::kTile * 16 + srlobs::kWaves * 96 * 4 +
                           (SRL_OBS_LINE_STORES ? srlobs::kWaves * srlobs::kTile * 144 : 0);  // stages, records, tables, store rows
@@ -705,17 +694,9 @@ static int conv2d_obs_fwd_run(void* stream, const srl_conv_desc* d, const void* 
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * srlobs::kWaves), lds, st, h);
       };
       srl_count_dispatch(SRL_DISP_OBS_FWD_BF16, 256, 2, (int)grid);
-      const char* dbg = getenv("SRL_OBS_DBG");  // timing experiments (wrong results): see obs_h2.h
-      switch (dbg ? atoi(dbg) : 0) {
-        case 1: go(srlobs::obs_fwd_h2_kernel<1, 1>); break;
-        case 2: go(srlobs::obs_fwd_h2_kernel<1, 2>); break;
-        case 4: go(srlobs::obs_fwd_h2_kernel<1, 4>); break;
-        case 7: go(srlobs::obs_fwd_h2_kernel<1, 7>); break;
-        default:
-          if (d->act == 1) go(srlobs::obs_fwd_h2_kernel<1>);
-          else if (d->act == 2) go(srlobs::obs_fwd_h2_kernel<2>);
-          else go(srlobs::obs_fwd_h2_kernel<0>);
-      }
+      if (d->act == 1) go(srlobs::obs_fwd_h2_kernel<1>);
+      else if (d->act == 2) go(srlobs::obs_fwd_h2_kernel<2>);
+      else go(srlobs::obs_fwd_h2_kernel<0>);
       SRL_LAUNCH_CHECK();
       return 0;
     }
@@ -732,19 +713,11 @@ static int conv2d_obs_fwd_run(void* stream, const srl_conv_desc* d, const void* 
     a.y_absmax = y_absmax;
     a.y_mask = y_mask;
     a.nsplit = obs_bf16_split(d->n, P, 3);
-    const char* dbg = getenv("SRL_OBS_DBG");  // timing experiments (wrong results): see obs_bf16.h
     const dim3 grid(srlobs::xcd_position_grid(P, a.nsplit));
     srl_count_dispatch(SRL_DISP_OBS_FWD_BF16, 256, y_h2 ? 1 : 0, a.nsplit);
-    switch (dbg ? atoi(dbg) : 0) {
-      case 3: hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 3>), grid, dim3(256), 0, st, a); break;
-      case 4: hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 4>), grid, dim3(256), 0, st, a); break;
-      case 8: hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 8>), grid, dim3(256), 0, st, a); break;
-      case 12: hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 12>), grid, dim3(256), 0, st, a); break;
-      default:
-        if (y_h2) hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 0, true, true>), grid, dim3(256), 0, st, a);
-        else if (y_mask) hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 0, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, 0>), grid, dim3(256), 0, st, a);
-    }
+    if (y_h2) hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, true, true>), grid, dim3(256), 0, st, a);
+    else if (y_mask) hipLaunchKernelGGL((srlobs::obs_fwd_bf16_kernel<256, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(srlobs::obs_fwd_bf16_kernel<256>, grid, dim3(256), 0, st, a);
     SRL_LAUNCH_CHECK();
     return 0;
   }
@@ -910,28 +883,12 @@ static int conv2d_obs_bwd_run(void* stream, const srl_conv_desc* d, const void* 
     a.frames = static_cast<const uint8_t*>(obs); a.img_stride = (long)d->H * d->W * d->Cin; a.meta = meta; a.n = d->n;
     a.dz = dz; a.dz_bound = dz_absmax; a.rstd_bound = rstd_max; a.Q = slabs_h2; a.slab = (long)P * d->Cout * Kp; a.R = R; a.C = C;
     a.GW = d->W; a.OW = OW; a.OH = OH; a.P = P; a.nsplit = obs_bwd_h2_split(P);
-    a.xcd = obs_xcd_order();
     if (a.nsplit > srl_ceil_div(d->n, (long)srlobs::kTileB)) a.nsplit = (int)srl_ceil_div(d->n, (long)srlobs::kTileB);  // (a range of tiles each)
     const unsigned grid = (unsigned)((P / (srlobs::kBlkH * srlobs::kBlkW)) * a.nsplit);
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, srlobs::kLdsB);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * srlobs::kWaves), srlobs::kLdsB, st, a);
-    };
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(srlobs::obs_bwd_h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              srlobs::kLdsB);
     srl_count_dispatch(SRL_DISP_OBS_BWD_BF16, 256, 2, a.nsplit);
-    const char* dbg = getenv("SRL_OBSB_DBG");  // timing experiments (wrong results): see obs_h2.h
-    switch (dbg ? atoi(dbg) : 0) {
-      case 1: go(srlobs::obs_bwd_h2_kernel<1>); break;
-      case 2: go(srlobs::obs_bwd_h2_kernel<2>); break;
-      case 3: go(srlobs::obs_bwd_h2_kernel<3>); break;
-      case 4: go(srlobs::obs_bwd_h2_kernel<4>); break;
-      case 7: go(srlobs::obs_bwd_h2_kernel<7>); break;
-      case 8: go(srlobs::obs_bwd_h2_kernel<8>); break;
-      case 19: go(srlobs::obs_bwd_h2_kernel<19>); break;
-      case 23: go(srlobs::obs_bwd_h2_kernel<23>); break;
-      case 12: go(srlobs::obs_bwd_h2_kernel<12>); break;
-      case 15: go(srlobs::obs_bwd_h2_kernel<15>); break;
-      default: go(srlobs::obs_bwd_h2_kernel<0>);
-    }
+    hipLaunchKernelGGL(srlobs::obs_bwd_h2_kernel, dim3(grid), dim3(64 * srlobs::kWaves), srlobs::kLdsB, st, a);
     SRL_LAUNCH_CHECK();
     reduce_slabs(st, slabs_h2, a.nsplit, (long)P, (long)d->Cout, Kp, Q, Kp, (long)d->Cout * Kp, first ? 0 : 1);
     SRL_LAUNCH_CHECK();

@@ -31,12 +31,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-// timing experiments only (scripts/build_variant.sh -DSRL_GEMM3_DBG=<bits>; results are wrong): 1 no in-loop global loads,
-// 2 no in-loop LDS writes, 4 no split arithmetic, 8 no barrier, 16 no epilogue, 128 one k-step only, 32 / 64 every gather
-// redirected into a 16 KB / 1 MB window (gemm_core.h bload4).  DESIGN.md section 4 records what they showed.
-#ifndef SRL_GEMM3_DBG
-#define SRL_GEMM3_DBG 0
-#endif
 // 1: the global loads of two consecutive k-steps are issued together (see gemm3_kernel); 0: one tile per step
 #ifndef SRL_GEMM3_PAIR
 #define SRL_GEMM3_PAIR 1
@@ -71,7 +65,6 @@ __device__ __forceinline__ void split3_quad(const float* v, uint2 (&pl)[3]) {
   uint32_t b[3][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if (SRL_GEMM3_DBG & 4) { b[0][i] = b[1][i] = b[2][i] = __float_as_uint(v[i]); continue; }
     b[0][i] = __float_as_uint(v[i]) & 0xffff0000u;
     const float r1 = v[i] - __uint_as_float(b[0][i]);
     b[1][i] = __float_as_uint(r1) & 0xffff0000u;
@@ -122,7 +115,7 @@ __device__ __forceinline__ void store3(const float* regs, uint8_t* lds, float sc
       continue;
     }
     uint2 pl[3];
-    if (RAW == 1) {  // the operand arrives already split (BPRE; SRL_GEMM3_DBG & 256 as a timing experiment): two pieces per 16 bytes
+    if (RAW == 1) {  // the operand arrives already split (BPRE): two pieces per 16 bytes
       pl[0] = make_uint2(__float_as_uint(regs[4 * q]), __float_as_uint(regs[4 * q + 1]));
       pl[1] = make_uint2(__float_as_uint(regs[4 * q + 2]), __float_as_uint(regs[4 * q + 3]));
       pl[2] = pl[0];
@@ -280,7 +273,6 @@ __global__ __launch_bounds__(WM * WN * 64, min_waves3(BM, BN, KB, NP)) void gemm
   long kend_l = kend;
   if (kcur < 0) { kcur = kbeg; kend_l = kbeg; }  // no tap reaches this pixel: one step on an all-zero tile
   long knext = nextk(kcur);
-  if (SRL_GEMM3_DBG & 128) knext = -1;
 
   // prologue: the first tile into LDS buffer 0, the second into registers (PAIR: both loaded together, set 0 and set 1)
   sa.load(g.a, m0, g.M, kcur, kend_l, true);
@@ -291,7 +283,7 @@ __global__ __launch_bounds__(WM * WN * 64, min_waves3(BM, BN, KB, NP)) void gemm
   }
   cs_acc(sa.r);
   store3<SA, BM, AKM, KB, NT, NP>(sa.r, lds, sc_a);
-  store3<SB, BN, BKM, KB, NT, NP, BPRE ? BPRE : ((SRL_GEMM3_DBG & 256) != 0 ? 1 : 0)>(sb.r, lds + TA::BYTES, sc_b);
+  store3<SB, BN, BKM, KB, NT, NP, BPRE>(sb.r, lds + TA::BYTES, sc_b);
   __syncthreads();
   if (!PAIR) {  // the second tile -- or, for a product of a single k-step, an out-of-range tile: zeros (the step's staging is
     // unconditional, and the fused column sums would count the first tile twice if it were still in the registers)
@@ -351,11 +343,9 @@ __global__ __launch_bounds__(WM * WN * 64, min_waves3(BM, BN, KB, NP)) void gemm
       if (kb == 0) {
         (void)k1;
         cs_acc(ra);
-        if (!(SRL_GEMM3_DBG & 2)) {
-          store3<SA, BM, AKM, KB, NT, NP>(ra, nxt, sc_a);           // tile t+1 (or zeros): registers -> the other LDS buffer
-          store3<SB, BN, BKM, KB, NT, NP, BPRE ? BPRE : ((SRL_GEMM3_DBG & 256) != 0 ? 1 : 0)>(rb, nxt + TA::BYTES, sc_b);
-        }
-        if (!(SRL_GEMM3_DBG & 1) && (!PAIR || cur == 0)) {
+        store3<SA, BM, AKM, KB, NT, NP>(ra, nxt, sc_a);           // tile t+1 (or zeros): registers -> the other LDS buffer
+        store3<SB, BN, BKM, KB, NT, NP, BPRE>(rb, nxt + TA::BYTES, sc_b);
+        if (!PAIR || cur == 0) {
           sa.load(g.a, m0, g.M, k2x, kend, true);         // tile t+2 (or nothing): global -> registers
           sb.load(g.b, n0, g.N, k2x, kend, true);
           if (PAIR) {
@@ -375,7 +365,7 @@ __global__ __launch_bounds__(WM * WN * 64, min_waves3(BM, BN, KB, NP)) void gemm
         }
       }
     }
-    if (!(SRL_GEMM3_DBG & 8)) __syncthreads();
+    __syncthreads();
   };
   if (!PAIR) {
     for (;;) {
@@ -424,7 +414,6 @@ __global__ __launch_bounds__(WM * WN * 64, min_waves3(BM, BN, KB, NP)) void gemm
         for (int r = 0; r < 16; ++r) acc[i][j][r] *= inv;
   }
   constexpr int EPI = AMODE == SRC_DGRAD ? 1 : 0;
-  if ((SRL_GEMM3_DBG & 16) && acc[0][0][0] != 12345.f) return;
   bool interior = m0 + BM <= g.M && n0 + BN <= g.N;
   if (g.o.rowmap && g.o.grp_shift)  // position-grouped rows: the tile's BM images must exist as well
     interior = interior && (((fdiv((uint32_t)(m0 >> g.o.grp_shift), g.o.f_img) + 1u) << g.o.grp_shift) <= (uint32_t)g.o.n_img);

@@ -327,12 +327,7 @@ constexpr uint32_t kInvalidOff = 0xFFFFFF00u;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)kNumRecords, 0x00020000);
 }
-#ifndef SRL_GEMM3_DBG
-#define SRL_GEMM3_DBG 0  // timing experiments only, see gemm_bf16x3.h
-#endif
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t rs, uint32_t voff) {
-  if ((SRL_GEMM3_DBG & 32) && voff != kInvalidOff) voff &= 0x3ff0u;    // every gather lands in one 16 KB window (L1 hits)
-  if ((SRL_GEMM3_DBG & 64) && voff != kInvalidOff) voff &= 0xffff0u;   // ... in one 1 MB window (L2 hits)
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }

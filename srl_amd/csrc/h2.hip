@@ -238,18 +238,6 @@ extern "C" int srl_h2_gemm(void* stream, const srl_h2_gemm_desc* d) {
   // k-halves in every wavefront -- a third less staged per multiply-add, on a two-stage ring (240 -> 220 us per 16 384 rows)
   static const bool wide_on = [] { const char* e = getenv("SRL_H2GEMM_WIDE"); return !(e && e[0] == '0'); }();
   const bool wide = wide_on && d->NC >= 1024 && d->K <= 1024;
-  static const bool half_cnt = [] { const char* e = getenv("SRL_H2GEMM_HALF"); return e && e[0] == '1'; }();
-  static const int dbg = [] { const char* e = getenv("SRL_H2G_DBG"); return e ? atoi(e) : 0; }();
-  a.dbg = dbg;
-  int rc;
-  const auto count_old = [&] { srl_count_dispatch(SRL_DISP_H2, 3, wide ? 8 : (d->NC >= 128 ? 4 : 2), wide && !half_cnt ? 2 : 3); };
-  // (two 4-wavefront workgroups of 128 x 256 per CU on half k-steps instead of one 8-wavefront workgroup of 256 x 256: h2gemm.h HALF)
-  // Alone 209.5 -> 192.3 us per 16 384 rows of the Linear's data gradient (same box; its leave-outs then overlap: no DMA 138, no
-  // MFMAs 149, no stores 143) -- but inside the update, beside the three other row-chunk pipelines, the update gets SLOWER (91.1 /
-  // 91.6 ms with the 8-wavefront kernel, 92.4 / 92.4 with this one, alternating runs on one box): the smaller tile stages 1.5 x the
-  // bytes per multiply-add (613 against 452 MB of counted traffic per launch) and that is what the neighbours compete for.  Opt-in
-  // (SRL_H2GEMM_HALF=1) for the record.
-  static const bool half_on = [] { const char* e = getenv("SRL_H2GEMM_HALF"); return e && e[0] == '1'; }();
   // round 6: the wide product as a PERSISTENT kernel (h2gemmp.h: one workgroup per CU walks its tiles, the ring never drains, a
   // tile's stores are not waited for) -- same operands, same piece products in the same order: bit-identical output.  207 -> 191 us
   // per 16 384 rows of the Linear's data gradient on one box, launched alone.
@@ -261,20 +249,20 @@ extern "C" int srl_h2_gemm(void* stream, const srl_h2_gemm_desc* d) {
   static const int pers_mode = [] { const char* e = getenv("SRL_H2GEMM_P"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : 2; }();
   // ... and every product large enough that a 256 x 256 tile still fills the chip several times over (the football tower's layers:
   // 51 200 rows x 704 ... 22 528 channels): a third fewer operand bytes staged per multiply-add than the 256 x 128 tiles, 4-13 %
-  // faster at those shapes (scripts/h2r6_probe.hip)
+  // faster at those shapes
   // (chosen from the layer's widths and a row floor only: the pieces an encoder's rows are cut into must not change kernels --
   // `test_config4_football_per_gpu_size` holds an update to its own result under another cut)
   const bool big = d->M >= 4096 && d->NC >= 2048 && d->K >= 1024;
-  if (((wide && pers_mode == 1) || (big && pers_mode >= 1)) && !half_on && !dbg) {
+  int rc;
+  if ((wide && pers_mode == 1) || (big && pers_mode >= 1)) {
     srl_count_dispatch(SRL_DISP_H2, 5, 8, H2P_NSLOT);
-    rc = h2gemmp_launch<0>((hipStream_t)stream, a);
+    rc = h2gemmp_launch((hipStream_t)stream, a);
     SRL_CHECK_ARG(rc == 0, "grid too large / rows of 8 MiB and more");
     SRL_LAUNCH_CHECK();
     return 0;
   }
-  count_old();
-  if (wide && half_on) rc = h2gemm_launch<8, H2X_DENSE, 3, false, true>((hipStream_t)stream, a);
-  else if (wide) rc = h2gemm_launch<8, H2X_DENSE, 2, false>((hipStream_t)stream, a);
+  srl_count_dispatch(SRL_DISP_H2, 3, wide ? 8 : (d->NC >= 128 ? 4 : 2), wide ? 2 : 3);
+  if (wide) rc = h2gemm_launch<8, H2X_DENSE, 2, false>((hipStream_t)stream, a);
   else if (d->NC >= 128) rc = h2gemm_launch<4, H2X_DENSE, 3>((hipStream_t)stream, a);
   else rc = h2gemm_launch<2, H2X_DENSE, 3>((hipStream_t)stream, a);
   SRL_CHECK_ARG(rc == 0, "grid too large");
@@ -304,7 +292,7 @@ extern "C" int srl_h2_wgrad_dense(void* stream, const void* a, const void* b, co
   h2tn_plan(M, ((NA + 255) / 256) * ((NB + 255) / 256), &g.splits, &g.rows_per_split);
   g.slabs = g.splits == 1 && !accumulate ? gw : workspace;   // (one range, nothing to add to: the slab IS the result)
   srl_count_dispatch(SRL_DISP_H2, 4, 8, H2TN_NSLOT);
-  SRL_CHECK_ARG(h2tn_launch<0>(st, g) == 0, "grid too large");
+  SRL_CHECK_ARG(h2tn_launch(st, g) == 0, "grid too large");
   if (g.slabs != gw) srlgemm::reduce_slabs(st, workspace, g.splits, 1L, (long)NA, (long)NB, gw, (long)NB, 0L, accumulate ? 1 : 0);
   SRL_LAUNCH_CHECK();
   return 0;

@@ -134,10 +134,6 @@ __device__ __forceinline__ uint32_t h2_xor32(uint32_t x, bool upper) {
 #ifndef SRL_H2C_SCHED
 #define SRL_H2C_SCHED 1
 #endif
-// timing experiments (wrong results): 1 no DMA after the first batches, 2 no MFMA chain, 4 no stores
-#ifndef SRL_H2C_DBG
-#define SRL_H2C_DBG 0
-#endif
 
 // k-blocks (tap, channel block) of a block's MFMA chain whose tap row is in the row mask RM (bit r = taps r * TPR .. + TPR - 1)
 template <int NKB> struct H2ActiveKb { int n; int kb[NKB]; };
@@ -352,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
     constexpr bool CLAMP = ID == H2C_F2 || ID == H2C_F3;   // data gradients take no activation (srl_h2_conv checks)
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = CLAMP ? fmaxf(acc[r] * inv + bqc[r], lo) : acc[r] * inv + bqc[r];
-    const bool ok = m.ok && !(SRL_H2C_DBG & 4);
+    const bool ok = m.ok;
     const uint32_t img32 = (uint32_t)m.img;
     if (MASK_IN) {   // bit r -> all ones / zero (v_bfe_i32), and: two vector instructions per value
 #pragma unroll
@@ -502,11 +498,10 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
           else nm.bits[c] = *reinterpret_cast<const uint32_t*>(mreg + il * MIMGB + (po + mi_pix[c]) * 4) >> mi_shift[c];
         }
       }
-      if (SRL_H2C_DBG & 2) { epilogue(pacc, pm); pm = nm; continue; }
       // (dense enumeration: output (oy, ox) sits at grid entry oy * GW + ox = e + oy * (GW - OW))
       const uint8_t* xb_ = slot + (il * GE::NPIX_L + bi * 16) * (GE::SRC == H2S_ROWSWZ ? 128 : 16) +
                            (GE::DENSE ? oy * ((GE::GW - GE::OW) * 16) : 0);
-      if (ID == H2C_D3 && !(SRL_H2C_DBG & 8)) {
+      if (ID == H2C_D3) {
         // output rows of block bi: outputs 16 bi .. + 15 of the 9-wide image; tap row ky reads dz row y - ky, which exists for
         // 0 <= y - ky <= 6: block 0 (y = 0, 1) never through ky = 2, block 4 (y = 7, 8) never through ky = 0, block 5 (y = 8) only
         // through ky = 2
@@ -516,7 +511,7 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
         else if (bi == 4) block(std::integral_constant<int, 0b110>{}, xb_, pacc, pm, nm);
         else if (bi == 5) block(std::integral_constant<int, 0b100>{}, xb_, pacc, pm, nm);
         else block(std::integral_constant<int, 0b111>{}, xb_, pacc, pm, nm);
-      } else if (ID == H2C_D2 && !(SRL_H2C_DBG & 8)) {
+      } else if (ID == H2C_D2) {
         // class-grid rows of block bi: outputs 16 bi .. + 15 of the 10-wide class image; tap row dy reads dz row a - dy, which
         // exists for 0 <= a - dy <= 8: block 6 (a = 9 alone) only through dy = 1
         static_assert(ID != H2C_D2 || (NB_IMG == 7 && GE::GW == 11 && GE::OW == 10 && GE::NTAP == 4), "row mask below is conv2's");
@@ -540,7 +535,7 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const long bn = b + (long)(NSLOT - 1) * gridDim.x;
-    if (bn < nbatch && !(SRL_H2C_DBG & 1)) issue(bn, s_nxt);
+    if (bn < nbatch) issue(bn, s_nxt);
     if (ph == 0) compute(std::integral_constant<int, 0>{}, b, s_cur);
     else compute(std::integral_constant<int, NPH - 1>{}, b, s_cur);
     s_cur = s_cur + 1 == NSLOT ? 0 : s_cur + 1;

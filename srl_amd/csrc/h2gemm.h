@@ -86,7 +86,6 @@ struct H2Args {
   uint32_t* mask_out;       // relu sign bits of out, natural element order, or null
   const uint32_t* mask_in;  // out *= bit of this mask at the output element (relu derivative), or null
   int32_t mask_in_h2;       // mask_in's bits are in h2 order (bit 8 g + j of a 32-block's word: what h2conv.h's forward kernels write)
-  int32_t dbg;              // timing experiments (wrong results; SRL_H2G_DBG): 1 no DMA, 2 no fragment reads / MFMAs, 4 no epilogue stores
   // DENSE only: the reduction split over `ksplits` workgroups per tile, split s writing its raw partial sums (no bias, activation or
   // mask: the consumer adds the slabs) to out + s * slab_bytes.  A few hundred rows times a long reduction (the Linear forward of
   // an inference batch: 2048 x 512 over K = 3136 is 32 tiles on 256 CUs, each filling 4.8 MB at a CU's ~33 GB/s: 104 us).
@@ -261,19 +260,14 @@ static __global__ void h2_unpack_kernel(const uint8_t* __restrict__ src, int64_t
 // KSPLIT (the default geometry): wavefront w = (position block w & 3, k-half w >> 2), every wavefront all NCB channel blocks.
 // !KSPLIT (NCB = 8, the data gradient of a wide Linear: 256 channels per workgroup, a third less staged per flop): wavefront
 // w = (position block w & 3, channel half w >> 2), both k-halves of every step; no exchange at the end.
-// HALF (round 5; NCB = 8, dense, unsplit): 128 positions x 256 channels per workgroup of FOUR wavefronts, k-steps of 16 k-values
-// (64-byte rows: one k-half of the h2p block), S stages of 24 KB -- so that TWO workgroups share a CU.  With one 8-wavefront
-// workgroup per CU a tile's ring fill, k-loop and 256 KB of stores run one after the other (leave-outs, DESIGN section 4: 89 + 45 +
-// 84 us of the Linear's data gradient); a second resident workgroup is what the hardware can overlap them with.
-template <int NCB, int XMODE, int S, bool KSPLIT = true, bool HALF = false>
-__global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
+template <int NCB, int XMODE, int S, bool KSPLIT = true>
+__global__ __launch_bounds__(512, 2) void h2gemm_kernel(H2Args g) {
   static_assert(NCB == 2 || NCB == 4 || (NCB == 8 && !KSPLIT), "64, 128 or (unsplit) 256 channels per workgroup");
   static_assert(S == 2 || S == 3 || S == 4, "ring depth");
-  static_assert(!HALF || (NCB == 8 && !KSPLIT && XMODE == H2X_DENSE), "half steps: the dense 256-channel geometry");
   constexpr int NCW = KSPLIT ? NCB : NCB / 2;   // channel blocks per wavefront
-  constexpr int BP = HALF ? 128 : 256;          // positions per workgroup
-  constexpr int PITCH = HALF ? 64 : 128;        // bytes of a row per k-step in LDS
-  constexpr int NWAVES = HALF ? 4 : 8;
+  constexpr int BP = 256;                       // positions per workgroup
+  constexpr int PITCH = 128;                    // bytes of a row per k-step in LDS
+  constexpr int NWAVES = 8;
   constexpr int XT = BP * PITCH, WT = NCB * 32 * PITCH, STAGE = XT + WT;
   constexpr int NXI = XT / 1024 / NWAVES;       // X-tile DMA instructions per wavefront and step (1 KB each)
   constexpr int NWI = WT / 1024 / NWAVES;       // W-tile DMA instructions per wavefront and step
@@ -283,7 +277,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wp = HALF ? wid & 1 : wid & 3, kh = KSPLIT ? wid >> 2 : 0, chalf = KSPLIT ? 0 : (HALF ? wid >> 1 : wid >> 2);
+  const int wp = wid & 3, kh = KSPLIT ? wid >> 2 : 0, chalf = KSPLIT ? 0 : wid >> 2;
   // logical tile id: every XCD owns one contiguous run
   unsigned lid;
   {
@@ -317,9 +311,9 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
   for (int q = 0; q < 4; ++q) xv[q] = 0;
 #pragma unroll
   for (int q = 0; q < NXI; ++q) {
-    // an instruction = 1 KB: 8 rows of 128 bytes (slot = 16-byte piece, XOR (row >> 1) & 7) or, HALF, 16 rows of 64 (XOR (row >> 2) & 3)
-    const int row = HALF ? 16 * (wid + NWAVES * q) + (lane >> 2) : 8 * (wid + NWAVES * q) + (lane >> 3);
-    const int slot = HALF ? (lane & 3) ^ ((row >> 2) & 3) : (lane & 7) ^ ((row >> 1) & 7);
+    // an instruction = 1 KB: 8 rows of 128 bytes (slot = 16-byte piece, XOR (row >> 1) & 7)
+    const int row = 8 * (wid + NWAVES * q) + (lane >> 3);
+    const int slot = (lane & 7) ^ ((row >> 1) & 7);
     long m = m0 + row;
     if (m >= g.M) m = g.M - 1;
     uint32_t base;
@@ -336,8 +330,8 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
   uint32_t wv[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int q = 0; q < NWI; ++q) {
-    const int row = HALF ? 16 * (wid + NWAVES * q) + (lane >> 2) : 8 * (wid + NWAVES * q) + (lane >> 3);
-    const int slot = HALF ? (lane & 3) ^ ((row >> 2) & 3) : (lane & 7) ^ ((row >> 1) & 7);
+    const int row = 8 * (wid + NWAVES * q) + (lane >> 3);
+    const int slot = (lane & 7) ^ ((row >> 1) & 7);
     int ch = c0 + row;
     if (ch >= g.NC) ch = g.NC - 1;
     wv[q] = (uint32_t)ch * g.w_row_bytes + 16u * slot;
@@ -348,7 +342,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
   const uint32_t lds_w = __builtin_amdgcn_readfirstlane(lds0 + XT + wid * 1024);
 
   // ---- k-step sequence
-  int nsteps = HALF ? 2 * g.nk : g.nk;
+  int nsteps = g.nk;
   int step0 = 0;
   if (XMODE == H2X_DENSE && g.ksplits > 1) {
     step0 = (int)((long)ks * nsteps / g.ksplits);
@@ -392,10 +386,8 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
   step_offsets(0, nsx, nsw);
   auto issue_off = [&](uint32_t stage_off, int t) {
     const uint32_t sx = __builtin_amdgcn_readfirstlane(nsx), sw = __builtin_amdgcn_readfirstlane(nsw);
-    if (!(g.dbg & 1)) {
-      h2_dma<NXI, DSTRIDE>(lds_x + stage_off, xv, rx, sx);
-      h2_dma<NWI, DSTRIDE>(lds_w + stage_off, wv, rw, sw);
-    }
+    h2_dma<NXI, DSTRIDE>(lds_x + stage_off, xv, rx, sx);
+    h2_dma<NWI, DSTRIDE>(lds_w + stage_off, wv, rw, sw);
     if (t + 1 < nsteps) step_offsets(t + 1, nsx, nsw);
   };
   auto issue = [&](int stage, int t) { issue_off((uint32_t)stage * STAGE, t); };
@@ -409,18 +401,15 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   // fragment addresses: row r = lane & 31 of a 32-row block, group 2 kh + (lane >> 5), plane p: slot (2 g + p) ^ f(r)
-  // (HALF: a staged row is one k-half, 4 slots: group (lane >> 5), plane p at slot (2 group + p) ^ ((r >> 2) & 3))
-  const int fr_r = lane & 31, fr_f = HALF ? (fr_r >> 2) & 3 : (fr_r >> 1) & 7;
-  auto fr_off = [&](int khh, int pl) {
-    return HALF ? fr_r * 64 + 16 * ((2 * (lane >> 5) + pl) ^ fr_f) : fr_r * 128 + 16 * ((4 * khh + 2 * (lane >> 5) + pl) ^ fr_f);
-  };
+  const int fr_r = lane & 31, fr_f = (fr_r >> 1) & 7;
+  auto fr_off = [&](int khh, int pl) { return fr_r * 128 + 16 * ((4 * khh + 2 * (lane >> 5) + pl) ^ fr_f); };
   constexpr int BLK = 32 * PITCH;   // bytes of a 32-row block of a staged tile
 
   auto compute = [&](uint32_t stage_off) {
     const uint8_t* sx = lds + stage_off + wp * (2 * BLK);
     const uint8_t* sw = lds + stage_off + XT + chalf * (NCW * BLK);
 #pragma unroll
-    for (int k2 = 0; k2 < ((KSPLIT || HALF) ? 1 : 2); ++k2) {
+    for (int k2 = 0; k2 < (KSPLIT ? 1 : 2); ++k2) {
       const int khh = KSPLIT ? kh : k2;
       const int o0 = fr_off(khh, 0), o1 = fr_off(khh, 1);
       h2_f16x8 xf[2][2], wf[NCW][2];
@@ -465,7 +454,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (more) issue_off(st_nxt, t + S - 1);
-    if (!(g.dbg & 2)) compute(st_cur);
+    compute(st_cur);
     st_cur = st_cur + STAGE == S * STAGE ? 0 : st_cur + STAGE;
     st_nxt = st_nxt + STAGE == S * STAGE ? 0 : st_nxt + STAGE;
   }
@@ -582,7 +571,6 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) amax = fmaxf(amax, ok ? fabsf(v[r]) : 0.f);
       }
-      if (g.dbg & 4) continue;
       if (XMODE != H2X_GROUPED) {
         // Whole lines per store instruction.  A lane holds 64 bytes of ITS row (position): stored from there, an instruction
         // wrote 64 pieces of 16 bytes to 64 different lines (the Linear's data gradient: 72 of its 230 us were these stores).
@@ -660,9 +648,9 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void h2gemm_kernel(H2Args g) {
   }
 }
 
-template <int NCB, int XMODE, int S, bool KSPLIT = true, bool HALF = false>
+template <int NCB, int XMODE, int S, bool KSPLIT = true>
 inline int h2gemm_launch(hipStream_t st, H2Args a) {
-  constexpr int BP = HALF ? 128 : 256, PITCH = HALF ? 64 : 128;
+  constexpr int BP = 256, PITCH = 128;
   constexpr int STAGE = BP * PITCH + NCB * 32 * PITCH;
   a.tiles_c = (a.NC + NCB * 32 - 1) / (NCB * 32);
   long tiles_p;
@@ -672,12 +660,12 @@ inline int h2gemm_launch(hipStream_t st, H2Args a) {
   const long nblk = tiles_p * a.tiles_c * a.ksplits;
   if (nblk <= 0 || nblk > 0x7fffffffL) return -22;
   static bool attr_set = false;
-  auto kern = h2gemm_kernel<NCB, XMODE, S, KSPLIT, HALF>;
+  auto kern = h2gemm_kernel<NCB, XMODE, S, KSPLIT>;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S * STAGE);
     attr_set = true;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(HALF ? 256 : 512), S * STAGE, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), S * STAGE, st, a);
   return 0;
 }
 

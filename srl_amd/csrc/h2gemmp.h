@@ -33,8 +33,6 @@ namespace srlh2 {
 
 constexpr int H2P_SLOT = 32768, H2P_NSLOT = 4, H2P_WOFF = 16384, H2P_STG = H2P_NSLOT * H2P_SLOT, H2P_LDS = H2P_STG + 8 * 4096;
 
-// DBG (timing experiments, wrong results): 1 no DMA, 2 no MFMAs, 4 no stores
-template <int DBG>
 __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
   constexpr int NP = 4, NQ = 2;      // accumulator blocks per wavefront: positions x channels
   constexpr int DPP = 8;             // DMA instructions per wavefront and PAIR of k-steps (2 operands x 2 row groups x 2 halves)
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
 
   // ---- DMA stream: tile kd, pair pd of it
   // instruction (operand, q): rows 16 (wid + 8 q) .. + 15 of the tile, lane i -> row + (i >> 2), 16-byte piece (i & 3) ^ ((i >> 4) & 3)
-  // (the row's swizzle, h2gemm.h HALF: (row >> 2) & 3) of the k-step's 64 bytes
+  // (the row's swizzle: (row >> 2) & 3) of the k-step's 64 bytes
   int kd = 0, pd = 0;
   uint32_t xv[2], wv[2];
   h2_i32x4 rx = h2_rsrc(g.x), rw = h2_rsrc(g.w);
@@ -108,7 +106,6 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
   // line are neighbours
   uint32_t dslot2 = 0;    // first slot of the pair being issued (0 or 2)
   auto piece = [&](int i) {
-    if (DBG & 1) return;
     const int op = i >> 2, q = (i >> 1) & 1, half = i & 1;
     const uint32_t m = ldma + (dslot2 + (uint32_t)half) * H2P_SLOT + (uint32_t)op * H2P_WOFF + (uint32_t)q * 8192u;
     const uint32_t soff = (uint32_t)pd * 128u + (uint32_t)half * 64u;
@@ -147,23 +144,18 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
   // second, p0[i] behind its MFMAs of the third, q0 at the end.
   auto mm_step = [&](const uint8_t* sn, auto pre_c, const bool ISS) {
     constexpr bool PRE = decltype(pre_c)::value;
-    constexpr bool mm = !(DBG & 2);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      if (mm) {
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q1[j], p0[i], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < NQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q1[j], p0[i], acc[i][j], 0, 0, 0);
       if (ISS) piece(i);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      if (mm) {
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0[j], p1[i], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < NQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0[j], p1[i], acc[i][j], 0, 0, 0);
       if (PRE) {
         if (i < NQ) q1[i] = ldf(sn, fw + i * 2048 + f1);
         p1[i] = ldf(sn, fx + i * 2048 + f1);
@@ -173,10 +165,8 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
     }
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      if (mm) {
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0[j], p0[i], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < NQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q0[j], p0[i], acc[i][j], 0, 0, 0);
       if (PRE) p0[i] = ldf(sn, fx + i * 2048 + f0);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -290,7 +280,7 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) bits |= (v[r] > 0.f ? 1u : 0u) << ((r & 3) + 8 * (r >> 2) + 4 * hl);
           bits |= (uint32_t)__shfl_xor((int)bits, 32);
-          const uint32_t moff = (ok && hl == 0 && !(DBG & 4)) ? (uint32_t)rowl * (g.out_row_bytes / 32) + (uint32_t)cb * 4u : OOB;
+          const uint32_t moff = (ok && hl == 0) ? (uint32_t)rowl * (g.out_row_bytes / 32) + (uint32_t)cb * 4u : OOB;
           __builtin_amdgcn_raw_buffer_store_b32(bits, r_mo, moff, 0, 0);
         }
         if (g.out_absmax) {
@@ -327,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
         for (int it = 0; it < 4; ++it) {
           const uint4 val = *reinterpret_cast<const uint4*>(tb + (8 * it + rr) * 128 + 16 * (pp ^ rr));
           const int rl = wp * 128 + i * 32 + 8 * it + rr;
-          const uint32_t off = (rl < nrow && okc && !(DBG & 4)) ? (uint32_t)rl * g.out_row_bytes + (uint32_t)cb * 128u + 16u * (uint32_t)pp : OOB;
+          const uint32_t off = (rl < nrow && okc) ? (uint32_t)rl * g.out_row_bytes + (uint32_t)cb * 128u + 16u * (uint32_t)pp : OOB;
           const u32x4 d = {val.x, val.y, val.z, val.w};
           __builtin_amdgcn_raw_buffer_store_b128(d, r_out, off, 0, 0);
         }
@@ -405,7 +395,6 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
   }
 }
 
-template <int DBG = 0>
 inline int h2gemmp_launch(hipStream_t st, H2Args a, int ncu = 256) {
   a.tiles_c = (a.NC + 255) / 256;
   const long nt = ((a.M + 255) / 256) * (long)a.tiles_c;
@@ -413,7 +402,7 @@ inline int h2gemmp_launch(hipStream_t st, H2Args a, int ncu = 256) {
   if ((long)a.out_row_bytes * 256 >= 0x7fffffffL || (long)a.x_row_bytes * 256 >= 0x7fffffffL || (long)a.w_row_bytes * 256 >= 0x7fffffffL) return -22;
   long grid = nt < ncu ? ((nt + 7) / 8) * 8 : ncu;   // a multiple of 8; workgroups beyond their XCD's run leave at once
   static bool attr_set = false;
-  auto kern = h2gemmp_kernel<DBG>;
+  auto kern = h2gemmp_kernel;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, H2P_LDS);
     attr_set = true;

@@ -18,7 +18,6 @@
 //     address is one lane register plus an immediate;
 //   * 8 wavefronts = 2 (A halves) x 4 (B quarters), 4 x 2 accumulator blocks each: 24 transposed reads (12 KB) and 24 MFMAs per
 //     wavefront and k-step; ring of four 33 KB slots, three k-steps in flight, ONE barrier per k-step, counted vmcnt;
-//   (template argument DBG: timing experiments with wrong results -- 1 no DMA, 2 no MFMAs, 4 no stores)
 //   * each workgroup writes its partial products to a float32 slab of its row range (full-matrix layout: a 32 x 32 block's
 //     register is two complete 128-byte lines per store instruction); gemm_core.h's reduce_slabs adds them (no atomics:
 //     bit-reproducible).
@@ -56,7 +55,6 @@ __host__ __device__ constexpr int h2tn_skew(int q) { return (q & 1) * 16 + (q >>
 // LDS byte offset of row r (0..15) inside an operand's region
 __host__ __device__ constexpr int h2tn_row_off(int r) { return ((r & 3) * 4 + (r >> 2)) * 1024 + h2tn_skew(r & 3); }
 
-template <int DBG>
 __global__ __launch_bounds__(512, 2) void h2tn_kernel(H2TnArgs g) {
   constexpr int TA = 4, TB = 2;     // accumulator blocks per wavefront: 128 channels of A x 64 channels of B
   constexpr int DPW = 4;            // DMA instructions per wavefront and k-step (32 rows of 1 KB over 8 wavefronts)
@@ -112,7 +110,6 @@ __global__ __launch_bounds__(512, 2) void h2tn_kernel(H2TnArgs g) {
     return p;
   };
   auto piece = [&](const Pieces& p, int i) {
-    if (DBG & 1) return;
     if (i == 0) dma1(p.l0, va, p.ra, 0u);
     else if (i == 1) dma1(p.l0 + 2048u, va, p.ra, p.sa1);
     else if (i == 2) dma1(p.l0 + (uint32_t)H2TN_OPB, vb, p.rb, 0u);
@@ -204,7 +201,6 @@ __global__ __launch_bounds__(512, 2) void h2tn_kernel(H2TnArgs g) {
     Pieces pc = {};
     if (MORE) pc = pieces(u + H2TN_NSLOT - 1);
     __builtin_amdgcn_sched_barrier(0);
-    constexpr bool mm = !(DBG & 2);
     // twelve MFMA pairs; behind pair k: the fragment reads that pair has freed, and -- one per three pairs, the two wavefronts
     // of a SIMD (w, w + 4) a pair apart -- a DMA instruction of step u + 3 (all four in the first product, the 32 instructions of
     // a CU's step met its DMA path, one 1 KB instruction per ~38 cycles, within ~500 cycles and the issuing wavefronts stalled)
@@ -216,20 +212,16 @@ __global__ __launch_bounds__(512, 2) void h2tn_kernel(H2TnArgs g) {
     // product 1: a0 b1
 #pragma unroll
     for (int i = 0; i < TA; ++i) {
-      if (mm) {
 #pragma unroll
-        for (int j = 0; j < TB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[i], b1[j], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < TB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[i], b1[j], acc[i][j], 0, 0, 0);
       dma_at(i);
       __builtin_amdgcn_sched_barrier(0);
     }
     // product 2: a1 b0; behind a1[i]'s MFMAs its successor, and b1's in the first two gaps
 #pragma unroll
     for (int i = 0; i < TA; ++i) {
-      if (mm) {
 #pragma unroll
-        for (int j = 0; j < TB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[i], b0[j], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < TB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[i], b0[j], acc[i][j], 0, 0, 0);
       if (NXT) {
         if (i < TB) b1[i] = frag(sn + fb + i * 128 + 16);
         a1[i] = frag(sn + fa + i * 128 + 16);
@@ -240,10 +232,8 @@ __global__ __launch_bounds__(512, 2) void h2tn_kernel(H2TnArgs g) {
     // product 3: a0 b0
 #pragma unroll
     for (int i = 0; i < TA; ++i) {
-      if (mm) {
 #pragma unroll
-        for (int j = 0; j < TB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[i], b0[j], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < TB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[i], b0[j], acc[i][j], 0, 0, 0);
       if (NXT) a0[i] = frag(sn + fa + i * 128);
       dma_at(2 * TA + i);
       __builtin_amdgcn_sched_barrier(0);
@@ -263,7 +253,6 @@ __global__ __launch_bounds__(512, 2) void h2tn_kernel(H2TnArgs g) {
 
   // ---- this range's slab: block (i, j), register r, lane l -> dW[o][c], o = A channel of row index (r & 3) + 8 (r >> 2) + 4 h,
   // c = B channel of column l & 31
-  if (DBG & 4) return;
   const float inv = 1.f / (*g.sa * *g.sb);
   float* slab = g.slabs + (size_t)sp * (size_t)g.NA * (size_t)g.NB;
   const int cl = h2tn_ch(lane & 31);
@@ -293,7 +282,6 @@ inline void h2tn_plan(int64_t M, int tiles, int* splits, int64_t* rows_per_split
   *rows_per_split = rp;
 }
 
-template <int DBG = 0>
 inline int h2tn_launch(hipStream_t st, H2TnArgs a) {
   a.tiles_a = (a.NA + 255) / 256;
   a.tiles_b = (a.NB + 255) / 256;
@@ -301,10 +289,10 @@ inline int h2tn_launch(hipStream_t st, H2TnArgs a) {
   if (nblk <= 0 || nblk > 0x7fffffffL) return -22;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h2tn_kernel<DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, H2TN_NSLOT * H2TN_SLOT);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h2tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, H2TN_NSLOT * H2TN_SLOT);
     attr_set = true;
   }
-  hipLaunchKernelGGL(h2tn_kernel<DBG>, dim3((unsigned)nblk), dim3(512), H2TN_NSLOT * H2TN_SLOT, st, a);
+  hipLaunchKernelGGL(h2tn_kernel, dim3((unsigned)nblk), dim3(512), H2TN_NSLOT * H2TN_SLOT, st, a);
   return 0;
 }
 

@@ -48,7 +48,6 @@ struct LhArgs {
   int x_act;
   float* x_out;      // (optional) the finished x is also written here [n, ldxo]: what a backward pass will read
   long ldxo;
-  int dbg;   // timing experiments (wrong results; SRL_LNH_DBG): 1 no final atomics, 2 no LDS meeting either, 4 no row loop
 };
 
 __device__ __forceinline__ float allsum(float v) {
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(64 * kWaves) void ln_heads_bwd_kernel(LhArgs a) {
     for (int k = 0; k < NV; ++k) accw[o][k] = 0.f;
   }
   float amax = 0.f;
-  for (long row = (long)blockIdx.x * kWaves + wave; row < ((a.dbg & 4) ? 0 : a.n); row += (long)gridDim.x * kWaves) {
+  for (long row = (long)blockIdx.x * kWaves + wave; row < a.n; row += (long)gridDim.x * kWaves) {
     float x[NV];
     load_row<NV>(a.x + row * a.ldx, lane, x);
     const float mean = a.mean[row], rstd = a.rstd[row];
@@ -245,9 +244,6 @@ __global__ __launch_bounds__(64 * kWaves) void ln_heads_bwd_kernel(LhArgs a) {
     for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
     if (lane == 0 && amax > 0.f) atomicMax(reinterpret_cast<int*>(a.dx_absmax), __float_as_int(amax));
   }
-  // every wavefront parks its sums in a slot of its own (plain stores), then the workgroup's threads add the slots and send
-  // one atomic per parameter
-  if (a.dbg & 2) return;   // (uniform)
   // The workgroup's sums meet in LDS one PLANE (one head output's dW row set, dgamma, dbeta) at a time: every wavefront parks its D
   // sums of the plane (plain stores), the threads add the eight slots and send one atomic per parameter.  (All planes at once
   // were 147 KB of LDS per workgroup: inside the update such a workgroup waits for a CU that a persistent kernel of another
@@ -264,7 +260,6 @@ __global__ __launch_bounds__(64 * kWaves) void ln_heads_bwd_kernel(LhArgs a) {
       float sum = 0.f;
 #pragma unroll
       for (int wv = 0; wv < kWaves; ++wv) sum += sm[wv * D + c];
-      if (a.dbg & 1) continue;
       float* dst = o == kMaxOut ? a.dgamma + c : (o == kMaxOut + 1 ? a.dbeta + c : (o < A0 ? a.dW[0] + (long)o * D + c : a.dW[1] + (long)(o - A0) * D + c));
       atomicAdd(dst, sum);
     }
@@ -389,8 +384,6 @@ extern "C" int srl_ln_heads_bwd(void* stream, const float* x, int64_t ldx, int64
     SRL_CHECK_ARG(dy[h] && lddy[h] >= head_dims[h] && dW[h], "null head gradient");
     a.W[h] = W[h]; a.A[h] = head_dims[h]; a.dy[h] = dy[h]; a.lddy[h] = lddy[h]; a.dW[h] = dW[h]; a.db[h] = db ? db[h] : nullptr;
   }
-  static const int dbg = [] { const char* e = getenv("SRL_LNH_DBG"); return e ? atoi(e) : 0; }();
-  a.dbg = dbg;
   hipStream_t st = (hipStream_t)stream;
   if (D == 256) launch_bwd<4>(a, st);
   else if (D == 512) launch_bwd<8>(a, st);

@@ -39,7 +39,6 @@ struct MArgs {
   int tb[SRL_MLP_MAX_LAYERS];    // Linear: bias table [nbo * 32]
   int pg[SRL_MLP_MAX_LAYERS];    // backward: offset of the layer's per-lane sums (Linear: bias gradient; LayerNorm: dgamma | dbeta)
   int par_floats, nacc, npg, nlin;
-  int dbg;   // timing experiments (wrong results; SRL_MLP_DBG): 2 no weight-gradient blocks, 4 no data gradient, 8 no final global adds, 16 no column sums, 32 no parameter staging, 64 no global loads, 128 no forward walk
 };
 
 __device__ __forceinline__ int mm_ch(int e, int hb) { return (e & 3) + 8 * (e >> 2) + 4 * hb; }
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
   float* const tiles = sm + m.par_floats + kBwdWaves * (m.npg * 64);
   float* const myT = tiles + wave * kTileF;
   SRL_MLP_STAMP(0);
-  if (!(m.dbg & 32)) mm_stage(m, sm, tid, 64 * kBwdWaves);
+  mm_stage(m, sm, tid, 64 * kBwdWaves);
   for (int e = lane; e < m.npg * 64; e += 64) pgs[e] = 0.f;
   __syncthreads();
   f32x16 W0, W1, W2, W3;   // this wavefront's block of the chain's 1st .. 4th Linear layer (counted from the input side)
@@ -318,7 +317,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
     if (it_ < 16) SRL_MLP_STAMP(8 + it_);
     ++it_;
     const long row = (tile0 + wave) * 32 + r;   // (a tile beyond the rows: zeros all the way, its wavefront keeps the barriers' count)
-    const bool rok = row < a.rows && !(m.dbg & 64);
+    const bool rok = row < a.rows;
     float d[kMB][16], xs[NL][kMB][16];
     {
       const Layer& last = a.L[a.n - 1];
@@ -333,7 +332,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
           for (int ib = 0; ib < kMB; ++ib)
 #pragma unroll
             for (int e = 0; e < 16; ++e) xs[i][ib][e] = cur[ib][e];
-          if (i + 1 < a.n && !(m.dbg & 128)) mm_layer_fwd(m, sm, i, cur, lane, hb);
+          if (i + 1 < a.n) mm_layer_fwd(m, sm, i, cur, lane, hb);
         }
       });
     }
@@ -353,7 +352,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
         for (int ob = 0; ob < kMB; ++ob)
           if (ob < nbo) {
             mm_half_write(myT + ob * 32 * kTh, r, hb, d[ob]);
-            if (L.gb && !(m.dbg & 16)) mm_half_colsum(myT + ob * 32 * kTh, pgs + m.pg[i] * 64 + 32 * ob, lane);  // bias gradient: column sums of dz
+            if (L.gb) mm_half_colsum(myT + ob * 32 * kTh, pgs + m.pg[i] * 64 + 32 * ob, lane);  // bias gradient: column sums of dz
           }
 #pragma unroll
         for (int ib = 0; ib < kMB; ++ib)
@@ -361,7 +360,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
         SRL_MLP_LSTAMP(1);
         __syncthreads();
         SRL_MLP_LSTAMP(2);
-        if (!(m.dbg & 2)) {
+        {
           // this wavefront's block of the layer, over its share of the four tiles: 4 blocks -> every tile; 2 -> two tiles; 1 -> its own
           const int nblk = nbo * nbi, b = wave % nblk, ob = b / nbi, ib = b - ob * nbi;
           const int per = nblk >= kBwdWaves ? kBwdWaves : nblk, t0 = (wave / nblk) * per;
@@ -381,7 +380,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
           for (int ib = 0; ib < kMB; ++ib) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[ib][e] = 0.f;
-            if (ib < nbi && !(m.dbg & 4)) {
+            if (ib < nbi) {
 #pragma unroll
               for (int ob = 0; ob < kMB; ++ob)
                 if (ob < nbo) mm_chain<true>(acc[ib], sm + m.wf[i] + (ob * nbi + ib) * kFB + trow, d[ob], mm_ne(L.out, ob));
@@ -468,7 +467,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
   }
   __syncthreads();
   SRL_MLP_STAMP(3);
-  for (int i = 0; i < ((m.dbg & 8) ? 0 : a.n); ++i) {
+  for (int i = 0; i < a.n; ++i) {
     const Layer L = a.L[i];
     auto psum = [&](int slot, int c) {   // the four wavefronts' per-channel sums
       float s = 0.f;

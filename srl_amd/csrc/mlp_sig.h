@@ -74,7 +74,6 @@ struct XArgs {
   const float* b[kMaxNL];
   float* gw[kMaxNL];
   float* gb[kMaxNL];
-  int dbg;
 };
 
 // channel 32 ib + mm_ch(e, hb) < DIM (a constant wherever DIM is a multiple of 8)
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_sig_kernel(XArgs a)
   const long ntiles = (a.rows + 31) / 32;
   for (long tile0 = (long)blockIdx.x * kBwdWaves; tile0 < ntiles; tile0 += (long)gridDim.x * kBwdWaves) {
     const long row = (tile0 + wave) * 32 + r;   // (a tile beyond the rows: zeros all the way, its wavefront keeps the barriers' count)
-    const bool rok = row < a.rows && !(a.dbg & 64);
+    const bool rok = row < a.rows;
     float d[kMB][16], xs[NL][kMB][16];
     sx_load<S::out_dim>(a.dy, a.lddy, row, rok, hb, d);   // (first: it arrives under the forward walk)
     {
@@ -287,9 +286,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_sig_kernel(XArgs a)
 #pragma unroll
           for (int e = 0; e < 16; ++e)
             if (e < sx_ne(S::in(i), ib)) xs[i][ib][e] = cur[ib][e];
-        if constexpr (i + 1 < NL) {
-          if (!(a.dbg & 128)) sx_layer_fwd<S, i>(sm, cur, lane, hb);
-        }
+        if constexpr (i + 1 < NL) sx_layer_fwd<S, i>(sm, cur, lane, hb);
       });
     }
     mm_static_for<NL>([&](auto IC) __attribute__((always_inline)) {
@@ -304,14 +301,14 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_sig_kernel(XArgs a)
         mm_static_for<nbo>([&](auto OB) __attribute__((always_inline)) {
           constexpr int ob = decltype(OB)::value;
           sx_half_write<sx_ne(out, ob)>(myT + ob * 32 * kTh, r, hb, d[ob]);
-          if (a.gb[i] && !(a.dbg & 16)) mm_half_colsum(myT + ob * 32 * kTh, pgs + S::pg(i) * 64 + 32 * ob, lane);  // bias gradient: column sums of dz
+          if (a.gb[i]) mm_half_colsum(myT + ob * 32 * kTh, pgs + S::pg(i) * 64 + 32 * ob, lane);  // bias gradient: column sums of dz
         });
         mm_static_for<nbi>([&](auto IB) __attribute__((always_inline)) {
           constexpr int ib = decltype(IB)::value;
           sx_half_write<sx_ne(in, ib)>(myT + (kMB + ib) * 32 * kTh, r, hb, xin[ib]);
         });
         __syncthreads();
-        if (!(a.dbg & 2)) {
+        {
           // this wavefront's block of the layer, over its share of the four tiles: 4 blocks -> every tile; 2 -> two tiles; 1 -> its own
           constexpr int nblk = nbo * nbi, per = nblk >= kBwdWaves ? kBwdWaves : nblk;
           const int b = wave % nblk, ob = b / nbi, ib = b - ob * nbi, t0 = (wave / nblk) * per;
@@ -324,11 +321,10 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_sig_kernel(XArgs a)
             constexpr int ib = decltype(IB)::value;
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[ib][e] = 0.f;
-            if (!(a.dbg & 4))
-              mm_static_for<nbo>([&](auto OB) __attribute__((always_inline)) {
-                constexpr int ob = decltype(OB)::value;
-                mm_chain_n<sx_ne(out, ob), true>(acc[ib], sm + S::wf(i) + (ob * nbi + ib) * kFB + trow, d[ob]);
-              });
+            mm_static_for<nbo>([&](auto OB) __attribute__((always_inline)) {
+              constexpr int ob = decltype(OB)::value;
+              mm_chain_n<sx_ne(out, ob), true>(acc[ib], sm + S::wf(i) + (ob * nbi + ib) * kFB + trow, d[ob]);
+            });
             __builtin_amdgcn_sched_barrier(0);
           });
 #pragma unroll
@@ -398,7 +394,6 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_sig_kernel(XArgs a)
     for (int e = 0; e < 16; ++e) slot[e * 64] = Wb[k][e];
   }
   __syncthreads();
-  if (a.dbg & 8) return;
   mm_static_for<NL>([&](auto IC) __attribute__((always_inline)) {
     constexpr int i = decltype(IC)::value;
     constexpr int in = S::in(i), out = S::out(i);
@@ -475,12 +470,11 @@ void sx_launch_bwd(const XArgs& x, long rows, hipStream_t st) {
 // WITH_DX: whether the shape is instantiated with the input gradient too (the chains behind a recurrent layer; the others would
 // only add compile time)
 template <class S, bool WITH_DX>
-bool sx_try_bwd(const Args& a, int dbg, hipStream_t st) {
+bool sx_try_bwd(const Args& a, hipStream_t st) {
   if (!S::matches(a) || (a.dx && !WITH_DX)) return false;
   static_assert(sx_bwd_lds_bytes<S>() <= 158 * 1024, "chain does not fit");
   XArgs x;
   sx_args(a, x);
-  x.dbg = dbg;
   if constexpr (WITH_DX) {
     if (a.dx) {
       sx_launch_bwd<S, true>(x, a.rows, st);
@@ -514,7 +508,7 @@ struct SigE {
 template <class... Es>
 struct SigList {
   static bool fwd(const Args& a, hipStream_t st) { return (sx_try_fwd<typename Es::sig>(a, st) || ...); }
-  static bool bwd(const Args& a, int dbg, hipStream_t st) { return (sx_try_bwd<typename Es::sig, Es::dx>(a, dbg, st) || ...); }
+  static bool bwd(const Args& a, hipStream_t st) { return (sx_try_bwd<typename Es::sig, Es::dx>(a, st) || ...); }
 };
 using Sigs = SigList<SigE<SigC1Actor>, SigE<SigC1Critic>, SigE<SigSmacObs>, SigE<SigSmacState>, SigE<SigSmacActorTail, true>,
                      SigE<SigSmacCriticTail, true>>;
@@ -524,6 +518,6 @@ inline bool sx_enabled() {
   return v;
 }
 inline bool sx_fwd(const Args& a, hipStream_t st) { return sx_enabled() && Sigs::fwd(a, st); }
-inline bool sx_bwd(const Args& a, int dbg, hipStream_t st) { return sx_enabled() && Sigs::bwd(a, dbg, st); }
+inline bool sx_bwd(const Args& a, hipStream_t st) { return sx_enabled() && Sigs::bwd(a, st); }
 
 }  // namespace

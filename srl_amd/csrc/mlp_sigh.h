@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_h_kernel(XArgs a) {
   const long ntiles = (a.rows + 31) / 32;
   for (long tile0 = (long)blockIdx.x * kBwdWaves; tile0 < ntiles; tile0 += (long)gridDim.x * kBwdWaves) {
     const long row = (tile0 + wave) * 32 + r;   // (a tile beyond the rows: zeros all the way, its wavefront keeps the barriers' count)
-    const bool rok = row < a.rows && !(a.dbg & 64);
+    const bool rok = row < a.rows;
     // lane roles of the transposing reads: 16-lane group g = 2 kg + h, lane i of the group = 4 q + p.  From an OPAQUE copy of the
     // lane index, made per tile: the few dozen fragment addresses below are loop-invariant, and the compiler otherwise keeps every
     // one of them in a register across the tile loop (47 spilled registers; the same trap as h2gemmp.h's epilogue)
@@ -373,9 +373,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_h_kernel(XArgs a) {
 #pragma unroll
           for (int e = 0; e < 16; ++e)
             if (e < sx_ne(S::in(i), ib)) xs[i][ib][e] = cur[ib][e];
-        if constexpr (i + 1 < NL) {
-          if (!(a.dbg & 128)) hx_layer_fwd<S, i>(smb, cur, lv, lv >> 5);
-        }
+        if constexpr (i + 1 < NL) hx_layer_fwd<S, i>(smb, cur, lv, lv >> 5);
       });
     }
     mm_static_for<NL>([&](auto IC) __attribute__((always_inline)) {
@@ -420,26 +418,25 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_h_kernel(XArgs a) {
             constexpr int ib = decltype(IB)::value;
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[ib][e] = 0.f;
-            if (!(a.dbg & 4))
-              mm_static_for<nbo>([&](auto OB) __attribute__((always_inline)) {
-                constexpr int ob = decltype(OB)::value;
-                const uint8_t* blk = smb + HP<S>::wb(i) + (ob * nbi + ib) * kHB;
-                mm_static_for<hx_steps(out, ob)>([&](auto SS) __attribute__((always_inline)) {
-                  constexpr int s = decltype(SS)::value;
-                  // rows (out channels) 16 s + 4 kg + q and + 8; this lane's run: k-values 16 h + 4 p .. + 3 of the block
-                  const int o0 = 16 * s + 4 * tkg + tq, o1 = o0 + 8;
-                  const int c0 = (((2 * th + (tp & 1)) ^ ((o0 >> 2) & 3)) << 4) + ((tp >> 1) << 3);
-                  const int c1 = (((2 * th + (tp & 1)) ^ ((o1 >> 2) & 3)) << 4) + ((tp >> 1) << 3);
-                  const hx_f16x8 a0 = hx_tr2(blk + o0 * 64 + c0, blk + o1 * 64 + c1);
-                  const hx_f16x8 a1 = hx_tr2(blk + 2048 + o0 * 64 + c0, blk + 2048 + o1 * 64 + c1);
-                  // B: this lane's own 8 k-values of dz, back from its row of the tile (32 registers less than keeping them)
-                  hx_f16x8 pd0, pd1;
-                  hx_tile_read(myT, lv & 31, lv >> 5, ob, s, pd0, pd1);
-                  acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, pd0, acc[ib], 0, 0, 0);
-                  acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, pd1, acc[ib], 0, 0, 0);
-                  acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, pd0, acc[ib], 0, 0, 0);
-                });
+            mm_static_for<nbo>([&](auto OB) __attribute__((always_inline)) {
+              constexpr int ob = decltype(OB)::value;
+              const uint8_t* blk = smb + HP<S>::wb(i) + (ob * nbi + ib) * kHB;
+              mm_static_for<hx_steps(out, ob)>([&](auto SS) __attribute__((always_inline)) {
+                constexpr int s = decltype(SS)::value;
+                // rows (out channels) 16 s + 4 kg + q and + 8; this lane's run: k-values 16 h + 4 p .. + 3 of the block
+                const int o0 = 16 * s + 4 * tkg + tq, o1 = o0 + 8;
+                const int c0 = (((2 * th + (tp & 1)) ^ ((o0 >> 2) & 3)) << 4) + ((tp >> 1) << 3);
+                const int c1 = (((2 * th + (tp & 1)) ^ ((o1 >> 2) & 3)) << 4) + ((tp >> 1) << 3);
+                const hx_f16x8 a0 = hx_tr2(blk + o0 * 64 + c0, blk + o1 * 64 + c1);
+                const hx_f16x8 a1 = hx_tr2(blk + 2048 + o0 * 64 + c0, blk + 2048 + o1 * 64 + c1);
+                // B: this lane's own 8 k-values of dz, back from its row of the tile (32 registers less than keeping them)
+                hx_f16x8 pd0, pd1;
+                hx_tile_read(myT, lv & 31, lv >> 5, ob, s, pd0, pd1);
+                acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, pd0, acc[ib], 0, 0, 0);
+                acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, pd1, acc[ib], 0, 0, 0);
+                acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, pd0, acc[ib], 0, 0, 0);
               });
+            });
             __builtin_amdgcn_sched_barrier(0);
           });
 #pragma unroll
@@ -449,11 +446,15 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_h_kernel(XArgs a) {
               if (e < sx_ne(in, ib)) d[ib][e] = acc[ib][e] * dinv * act_der(xin[ib][e], pact);
         }
         __syncthreads();
-        if (!(a.dbg & 2)) {
+        // behind a branch the compiler cannot fold, the block stays a region of its own: merged into the layer's code, its
+        // addresses stay live across it and the C1 towers' kernels spill (~570 bytes of scratch per lane)
+        int on = 1;
+        asm volatile("" : "+s"(on));
+        if (on) {
           // this wavefront's block of the layer, over its share of the four tiles: 4 blocks -> every tile; 2 -> two tiles; 1 -> its own
           constexpr int nblk = nbo * nbi, per = nblk >= kBwdWaves ? kBwdWaves : nblk;
           const int b = wave % nblk, ob = b / nbi, ib = b - ob * nbi, t0 = (wave / nblk) * per;
-          const bool bias = a.gb[i] != nullptr && ib == 0 && !(a.dbg & 16);
+          const bool bias = a.gb[i] != nullptr && ib == 0;
           // fragment addresses inside a tile: rows 16 ts + 8 kg + q (+ 4), 8-byte slot 8 blk + 4 h + p of piece 0 (+ 16: piece 1)
 #pragma unroll
           for (int t = 0; t < per; ++t) {
@@ -561,7 +562,6 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_h_kernel(XArgs a) {
     }
   });
   __syncthreads();
-  if (a.dbg & 8) return;
   mm_static_for<NL>([&](auto IC) __attribute__((always_inline)) {
     constexpr int i = decltype(IC)::value;
     constexpr int in = S::in(i), out = S::out(i);
@@ -612,12 +612,11 @@ void hx_launch_bwd(const XArgs& x, long rows, hipStream_t st) {
   hipLaunchKernelGGL((mlp_bwd_h_kernel<S, DX>), dim3((unsigned)(groups < 256 ? groups : 256)), dim3(64 * kBwdWaves), lds, st, x);
 }
 template <class S, bool WITH_DX>
-bool hx_try_bwd(const Args& a, int dbg, hipStream_t st) {
+bool hx_try_bwd(const Args& a, hipStream_t st) {
   if (!S::matches(a) || (a.dx && !WITH_DX)) return false;
   static_assert(hx_bwd_lds_bytes<S>() <= 158 * 1024, "chain does not fit");
   XArgs x;
   sx_args(a, x);
-  x.dbg = dbg;
   if constexpr (WITH_DX) {
     if (a.dx) {
       hx_launch_bwd<S, true>(x, a.rows, st);
@@ -631,7 +630,7 @@ bool hx_try_bwd(const Args& a, int dbg, hipStream_t st) {
 template <class... Es>
 struct HSigList {
   static bool fwd(const Args& a, hipStream_t st) { return (hx_try_fwd<typename Es::sig>(a, st) || ...); }
-  static bool bwd(const Args& a, int dbg, hipStream_t st) { return (hx_try_bwd<typename Es::sig, Es::dx>(a, dbg, st) || ...); }
+  static bool bwd(const Args& a, hipStream_t st) { return (hx_try_bwd<typename Es::sig, Es::dx>(a, st) || ...); }
 };
 using HSigs = HSigList<SigE<SigC1Actor>, SigE<SigC1Critic>, SigE<SigSmacObs>, SigE<SigSmacState>, SigE<SigSmacActorTail, true>,
                        SigE<SigSmacCriticTail, true>>;
@@ -641,6 +640,6 @@ inline int hx_mode() {   // SRL_MLP_F16: 0 float32 kernels; 1 (default) the f16-
   return v;
 }
 inline bool hx_fwd(const Args& a, hipStream_t st) { return sx_enabled() && hx_mode() != 0 && HSigs::fwd(a, st); }
-inline bool hx_bwd(const Args& a, int dbg, hipStream_t st) { return sx_enabled() && (hx_mode() & 1) && !(hx_mode() & 2) && HSigs::bwd(a, dbg, st); }
+inline bool hx_bwd(const Args& a, hipStream_t st) { return sx_enabled() && (hx_mode() & 1) && !(hx_mode() & 2) && HSigs::bwd(a, st); }
 
 }  // namespace

@@ -414,9 +414,7 @@ static int mlp_bwd_impl(void* stream, const srl_mlp_layer* layers, int n, const 
   a.dx = dx; a.lddx = lddx;
   MArgs m;
   if (mfma_takes(a, rows, m)) {
-    static const int dbg = [] { const char* e = getenv("SRL_MLP_DBG"); return e ? atoi(e) : 0; }();
-    m.dbg = dbg;
-    if (hx_bwd(a, dbg, (hipStream_t)stream) || sx_bwd(a, dbg, (hipStream_t)stream)) {
+    if (hx_bwd(a, (hipStream_t)stream) || sx_bwd(a, (hipStream_t)stream)) {
       SRL_LAUNCH_CHECK();
       return 0;
     }

@@ -159,11 +159,9 @@ struct FwdArgs {
 // 16 k-values (A = the samples' bytes, rows = samples; B = weights from LDS, columns = output channels), LayerNorm +
 // bias + activation on the accumulators, whole-line stores.  The next tile's loads are issued before the current
 // tile's arithmetic.
-// DBG (timing experiments only, wrong results; SRL_OBS_DBG): 1 = bytes reinterpreted instead of converted, 2 = no MFMAs,
-// 4 = no stores, 8 = the patch loads of every tile go to the first tile's rows (cache-hot)
 // MASK: also leave the sign bits of the ReLU output (FwdArgs::y_mask).  A template parameter because the kernel sits at the
 // register limit of three wavefronts per SIMD: the variant without it must stay exactly what it was.
-template <int KP, int DBG = 0, bool MASK = false, bool H2OUT = false>
+template <int KP, bool MASK = false, bool H2OUT = false>
 __global__ __launch_bounds__(256, 3) void obs_fwd_bf16_kernel(FwdArgs a) {
   constexpr int NKB = KP / 16, NC = KP / 32;
   __shared__ uint4 Wl[3 * NKB * 64];
@@ -204,7 +202,7 @@ __global__ __launch_bounds__(256, 3) void obs_fwd_bf16_kernel(FwdArgs a) {
   auto rowptr = [&](long tile) {
     long n = tile * 32 + l31;
     if (n >= a.g.n) n = a.g.n - 1;  // clamped: the loads stay in bounds, the stores of such rows are masked
-    return a.g.frames + ((DBG & 8) ? (long)l31 : obs_slot(a.g, n)) * a.g.img_stride + posoff;
+    return a.g.frames + obs_slot(a.g, n) * a.g.img_stride + posoff;
   };
   // (rstd, -(mean - c) rstd) of the accumulator ROWS go through LDS for the wavefront's own later reads (a wavefront's
   // LDS instructions execute in order; no other wavefront touches this slice); returns the integer centre c in [0, 255]
@@ -234,15 +232,7 @@ __global__ __launch_bounds__(256, 3) void obs_fwd_bf16_kernel(FwdArgs a) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) wfr[3 * e + pl] = Wl[(pl * NKB + 2 * c + e) * 64 + lane];
       const uint4 q = raw[c];
-      bf16x8 x0, x1;
-      if (DBG & 1) {
-        union { uint4 u; bf16x8 v; } t0, t1;
-        t0.u = make_uint4(q.x, q.y, q.x, q.y);
-        t1.u = make_uint4(q.z, q.w, q.z, q.w);
-        x0 = t0.v, x1 = t1.v;
-      } else {
-        x0 = bytes_to_bf16x8(q.x, q.y, cen), x1 = bytes_to_bf16x8(q.z, q.w, cen);
-      }
+      const bf16x8 x0 = bytes_to_bf16x8(q.x, q.y, cen), x1 = bytes_to_bf16x8(q.z, q.w, cen);
       // the next tile's loads go out one 128-byte run at a time (its four 32-byte chunks back to back, as soon as the
       // last of their registers is free): issued chunk by chunk, between the MFMAs, the four requests for a line were
       // far enough apart for the line to leave the L1 in between
@@ -256,16 +246,10 @@ __global__ __launch_bounds__(256, 3) void obs_fwd_bf16_kernel(FwdArgs a) {
         for (int pl = 0; pl < 3; ++pl) {
           union { uint4 u; bf16x8 v; } wf;
           wf.u = wfr[3 * e + pl];
-          if (DBG & 2) {
-            union { bf16x8 v; float f[4]; } xx;
-            xx.v = e ? x1 : x0;
-            acc[3 * e + pl] += __uint_as_float(wf.u.x) * xx.f[0];
-          } else {
-            // H2OUT: operands swapped -- D[o][n], lanes = samples: a lane then holds 16 channels of ONE sample, which is what
-            // a 16-byte chunk of h2p is made of
-            if (H2OUT) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf.v, e ? x1 : x0, acc, 0, 0, 0);
-            else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(e ? x1 : x0, wf.v, acc, 0, 0, 0);
-          }
+          // H2OUT: operands swapped -- D[o][n], lanes = samples: a lane then holds 16 channels of ONE sample, which is what
+          // a 16-byte chunk of h2p is made of
+          if (H2OUT) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf.v, e ? x1 : x0, acc, 0, 0, 0);
+          else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(e ? x1 : x0, wf.v, acc, 0, 0, 0);
         }
     }
     // D[n][o]: this lane holds output channel o = l31 of the samples tile * 32 + 8g + 4h + (0..3) in registers 4g .. 4g+3,
@@ -331,7 +315,7 @@ __global__ __launch_bounds__(256, 3) void obs_fwd_bf16_kernel(FwdArgs a) {
         else if (a.act == 2) v = tanhf(v);
         const int row = 8 * g4 + 4 * h + i;
         vv[4 * g4 + i] = v;
-        if ((full || n0 + row < a.g.n) && (!(DBG & 4) || v == 12345.f)) {
+        if (full || n0 + row < a.g.n) {
           yp[row * ldy32] = v;
           amx = fmaxf(amx, fabsf(v));
         }
@@ -407,11 +391,7 @@ __global__ __launch_bounds__(256, 2) void obs_bwd_bf16_kernel(BwdArgs a) {
   float s_rs[2] = {0.f, 0.f}, s_mean[2] = {0.f, 0.f}, s_cen[2] = {0.f, 0.f};
   float rsum[4] = {0.f, 0.f, 0.f, 0.f}, csum[4] = {0.f, 0.f, 0.f, 0.f};
 
-#ifndef SRL_OBSB_DBG
-#define SRL_OBSB_DBG 0  // timing experiments (wrong results): 1 no in-loop global loads, 2 no conversions, 4 no MFMAs, 8 no LDS stores
-#endif
   auto gload = [&](int set, long step) {
-    if ((SRL_OBSB_DBG & 1) && step > s0 + 2) return;
     const long n = step * KS + sr;
     const bool ok = n < a.g.n;
     const long nn = ok ? n : a.g.n - 1;
@@ -444,14 +424,8 @@ __global__ __launch_bounds__(256, 2) void obs_bwd_bf16_kernel(BwdArgs a) {
       // patch bytes 16 j .. 16 j + 15 (j = sub + 8 i) -> bf16 columns: 32 bytes = chunks 2 j, 2 j + 1 of the row
       const int j = sub + 8 * i;
       union { bf16x8 v; uint4 u; } lo, hi;
-      if (SRL_OBSB_DBG & 2) {
-        lo.u = make_uint4(xb[set][i].x, xb[set][i].y, xb[set][i].x, xb[set][i].y);
-        hi.u = make_uint4(xb[set][i].z, xb[set][i].w, xb[set][i].z, xb[set][i].w);
-      } else {
-        lo.v = bytes_to_bf16x8(xb[set][i].x, xb[set][i].y, cen);
-        hi.v = bytes_to_bf16x8(xb[set][i].z, xb[set][i].w, cen);
-      }
-      if (SRL_OBSB_DBG & 8) continue;
+      lo.v = bytes_to_bf16x8(xb[set][i].x, xb[set][i].y, cen);
+      hi.v = bytes_to_bf16x8(xb[set][i].z, xb[set][i].w, cen);
       const int sw = (sr & 3) << 2;  // rows 4 apart in time share banks otherwise: see the transposed reads below
       *reinterpret_cast<uint4*>(bb + 16 * ((2 * j) ^ sw)) = lo.u;
       *reinterpret_cast<uint4*>(bb + 16 * ((2 * j + 1) ^ sw)) = hi.u;
@@ -500,10 +474,7 @@ __global__ __launch_bounds__(256, 2) void obs_bwd_bf16_kernel(BwdArgs a) {
       for (int pl = 0; pl < 3; ++pl) {
         const bf16x8 af = trread(a_addr(buf, pl, kb, 0), a_addr(buf, pl, kb, 1));
 #pragma unroll
-        for (int jt = 0; jt < 2; ++jt) {
-          if (SRL_OBSB_DBG & 4) { union { bf16x8 v; float f[4]; } xa, xb2; xa.v = af; xb2.v = bf[jt]; acc[jt][pl] += xa.f[0] * xb2.f[0]; }
-          else acc[jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf[jt], acc[jt], 0, 0, 0);
-        }
+        for (int jt = 0; jt < 2; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf[jt], acc[jt], 0, 0, 0);
       }
       if (kb == 0 && s + 1 < s1) {  // tile s+1: registers (set CUR^1) -> the other buffer (its readers left at the last barrier)
         lstore(CUR ^ 1, lds + (CUR ^ 1) * BUF);

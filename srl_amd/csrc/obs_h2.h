@@ -56,7 +56,6 @@ struct FwdH2Args {
   uint32_t* y_mask;          // [n][P]
   float* y_absmax;
   int GW, OW, OH, P, act, nsplit;
-  int xcd;   // 1: XCD-contiguous (block, split) numbering (SRL_OBS_XCD=1; default: by blockIdx)
 };
 
 #ifdef __HIPCC__
@@ -166,9 +165,8 @@ __device__ __forceinline__ void obs_bytes_to_f16(uint32_t d, uint32_t negc, uint
 #ifndef SRL_OBS_LINE_STORES
 #define SRL_OBS_LINE_STORES 1
 #endif
-// ACT: the activation (0 none, 1 ReLU, 2 tanh).  DBG (timing experiments, wrong results; SRL_OBS_DBG): 1 = no output stores, 2 = no LDS
-// reads / conversions / MFMAs, 4 = no DMA
-template <int ACT, int DBG = 0>
+// ACT: the activation (0 none, 1 ReLU, 2 tanh)
+template <int ACT>
 __global__ __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) void obs_fwd_h2_kernel(FwdH2Args a) {
   extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
   // [kStages][32 samples][kChunks + 1 chunks][16 B] | meta ring [kMeta][32] x 16 B | tables [kWaves][3][32] float
@@ -180,15 +178,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) void obs_fwd_h2_k
 
   // a workgroup = one block of positions x one of nsplit ranges of the launch's 32-sample tiles
   const int nbx = a.OW / kBlkW;
-  // a.xcd (opt-in, SRL_OBS_XCD=1): every XCD owns one contiguous run of (block, split) pairs -- the ~6 blocks an XCD works on are
-  // neighbours in the frame, so that the window rows and columns they share come out of ITS L2 (workgroup ids go round-robin over
-  // the eight XCDs: numbered by blockIdx alone, the 50 blocks of a sample range are spread over all eight L2s and every frame is
-  // fetched 2.2 times).  A third fewer bytes fetched, no time gained (conv.hip: obs_xcd_order)
-  unsigned lid;
-  {
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7u, xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-    lid = a.xcd ? xcd * q + (xcd < r ? xcd : r) + slot : blockIdx.x;
-  }
+  const unsigned lid = blockIdx.x;
   const int blk = (int)(lid / (unsigned)a.nsplit), split = (int)(lid % (unsigned)a.nsplit);
   const long ntiles = (a.n + kTile - 1) / kTile;
   const long t0 = ntiles * split / a.nsplit, t1 = ntiles * (split + 1) / a.nsplit;
@@ -250,7 +240,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) void obs_fwd_h2_k
   };
   auto issue = [&](int j, int stage_j) __attribute__((always_inline)) {
     issue_meta(j + 3);
-    if (dma_lane && !(DBG & 4)) {
+    if (dma_lane) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         obs_dma_s(lds0 + stage_j * kStageBytes + (4 * wave + i) * kSampleBytes, frames + (long)slot[i] * img_stride, blkoff);
@@ -321,12 +311,12 @@ __global__ __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) void obs_fwd_h2_k
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));                                                       \
         const int smp_ = 8 * i + (lane >> 3);                                                                             \
         const uint4 q_ = *reinterpret_cast<const uint4*>(tr_ + smp_ * 144 + (lane & 7) * 16);                             \
-        const uint32_t oo_ = (n0_ + smp_ < nsamp && !(DBG & 1)) ? (uint32_t)(((n0_ + smp_) * (long)P + ent) * 128 + (lane & 7) * 16) : 0x80000000u; \
+        const uint32_t oo_ = (n0_ + smp_ < nsamp) ? (uint32_t)(((n0_ + smp_) * (long)P + ent) * 128 + (lane & 7) * 16) : 0x80000000u; \
         u32x4 d = {q_.x, q_.y, q_.z, q_.w};                                                                               \
         __builtin_amdgcn_raw_buffer_store_b128(d, r_out, oo_, 0, 0);                                                      \
       }                                                                                                                   \
     } else {                                                                                                              \
-    const uint32_t ooff = (ok_ && !(DBG & 1)) ? (uint32_t)(((n0_ + l31) * (long)P + ent) * 128 + h * 64) : 0x80000000u;    \
+    const uint32_t ooff = ok_ ? (uint32_t)(((n0_ + l31) * (long)P + ent) * 128 + h * 64) : 0x80000000u;                   \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                       \
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));                                                         \
       u32x4 d = {c4[i][0], c4[i][1], c4[i][2], c4[i][3]};                                                                 \
@@ -367,7 +357,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) void obs_fwd_h2_k
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-    for (int c = 0; c < ((DBG & 2) ? 0 : 8); ++c) {
+    for (int c = 0; c < 8; ++c) {
       const uint4 q = *reinterpret_cast<const uint4*>(sb + (c >> 2) * (kRowChunks * 16) + (c & 3) * 32);
       union { uint32_t u[4]; f16x8 v; } x0, x1;
       obs_bytes_to_f16(q.x, ncu, x0.u[0], x0.u[1]);
@@ -432,7 +422,6 @@ struct BwdH2Args {
   float* R;                 // [P][32], atomically accumulated
   float* C;                 // [P][32], atomically accumulated
   int GW, OW, OH, P, nsplit;
-  int xcd;
 };
 
 #ifdef __HIPCC__
@@ -441,8 +430,6 @@ struct BwdH2Args {
 // the barrier opens; in their gaps the conversions of the next B operands, dz(it + 1): float32 rows -> f16 planes -> the next
 // tile's A fragments, and the LDS reads of what comes after].  Every tile issues the SAME number of memory operations in the same
 // order (past the end: the last tile again), which makes the s_waitcnt of a tile a compile-time constant.
-// DBG (timing experiments, wrong results): 1 no frame DMA, 2 no dz DMA, 4 no MFMAs, 8 dz staged as zeros, 16 no vector work between the MFMAs
-template <int DBG = 0>
 __global__ __launch_bounds__(512, 1) void obs_bwd_h2_kernel(BwdH2Args a) {
   extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
   // [4][16 samples][62 chunks][16 B] | record ring [8][16] x 16 B | per wavefront: 3 planes [16 samples][32 channels] f16 | per
@@ -457,11 +444,7 @@ __global__ __launch_bounds__(512, 1) void obs_bwd_h2_kernel(BwdH2Args a) {
   const uint32_t ldsraw = lds0 + kRaw0 + wave * (kStagesB * 2048);
 
   const int nbx = a.OW / kBlkW;
-  unsigned lid;   // (XCD-contiguous numbering: see the forward kernel)
-  {
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7u, xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-    lid = a.xcd ? xcd * q + (xcd < r ? xcd : r) + slot : blockIdx.x;
-  }
+  const unsigned lid = blockIdx.x;
   const int blk = (int)(lid / (unsigned)a.nsplit), split = (int)(lid % (unsigned)a.nsplit);
   const long ntiles = (a.n + kTileB - 1) / kTileB;
   const long t0 = ntiles * split / a.nsplit, t1 = ntiles * (split + 1) / a.nsplit;
@@ -521,7 +504,7 @@ __global__ __launch_bounds__(512, 1) void obs_bwd_h2_kernel(BwdH2Args a) {
   // tile j: records of j + 4, frames (2 samples per wavefront, slots read before), dz rows (2 x 8 samples x 128 bytes)
   auto issue = [&](int j) __attribute__((always_inline)) {
     issue_meta(j + 4);
-    if (dma_lane && !((DBG & 1) && j > 3)) {
+    if (dma_lane) {
       obs_dma_s(lds0 + (j & 3) * kStageBytesB + (2 * wave) * kSampleBytesB, frames + (long)slot0 * img_stride, blkoff);
       obs_dma_s(lds0 + (j & 3) * kStageBytesB + (2 * wave + 1) * kSampleBytesB, frames + (long)slot1 * img_stride, blkoff);
     }
@@ -530,7 +513,7 @@ __global__ __launch_bounds__(512, 1) void obs_bwd_h2_kernel(BwdH2Args a) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const uint32_t smp = smp0 + 8 * i < last ? smp0 + 8 * i : last;
-      if (!((DBG & 2) && j > 3)) obs_dma_s(ldsraw + (j & 3) * 2048 + i * 1024, dzpos, smp * ldzb + dzlane);
+      obs_dma_s(ldsraw + (j & 3) * 2048 + i * 1024, dzpos, smp * ldzb + dzlane);
     }
   };
   // dz rows of tile j (raw image j & 3) -> three f16 planes; R / C sums.  In three steps (loads | 4 x a pair of channels | stores)
@@ -540,7 +523,7 @@ __global__ __launch_bounds__(512, 1) void obs_bwd_h2_kernel(BwdH2Args a) {
   uint32_t st_pl[kPiecesB][4];
   auto stage_load = [&](int j) __attribute__((always_inline)) {
     const uint4 mrec = metal[(j & 7) * kTileB + ds_s];
-    const bool ok = (t0 + j) * kTileB + ds_s < nsamp && j < nu && !((DBG & 8) && j > 3);
+    const bool ok = (t0 + j) * kTileB + ds_s < nsamp && j < nu;
     const float mean_n = __uint_as_float(mrec.z);
     st_rss = ok ? __uint_as_float(mrec.y) * scale : 0.f;   // dz -> scaled dz'; 0 past the end
     st_mcs = (mean_n - rintf(mean_n)) * inv_scale;         // scaled dz' -> its share of C
@@ -676,13 +659,11 @@ __global__ __launch_bounds__(512, 1) void obs_bwd_h2_kernel(BwdH2Args a) {
       const int k = g / 6, j = g % 6;
       XB* const cur = (k & 1) ? xbB : xbA;
       XB* const nxt = (k & 1) ? xbA : xbB;
-      if (!(DBG & 4) && (j >> 1) < kPiecesB) acc[2 * k + (j & 1)] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af.p[j >> 1], cur[j & 1].v, acc[2 * k + (j & 1)], 0, 0, 0);
-      if (DBG & 16) {
-      } else if (j < 4) conv_unit(nxt, j);                                     // group k + 1 (k = 3: group 0 of tile it + 1)
+      if ((j >> 1) < kPiecesB) acc[2 * k + (j & 1)] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af.p[j >> 1], cur[j & 1].v, acc[2 * k + (j & 1)], 0, 0, 0);
+      if (j < 4) conv_unit(nxt, j);                                     // group k + 1 (k = 3: group 0 of tile it + 1)
       else if (j == 4) read_raw(k < 2 ? it : it + 1, (k + 2) & 3);             // the bytes of group k + 2
       // staging of dz(it + 1), three units per pair of channels; the centres of tile it + 1 before its first conversions
-      if (DBG & 16) {
-      } else if (g == 0) stage_load(it + 1);
+      if (g == 0) stage_load(it + 1);
       else if (g == 1) stage_unit(0, 0);
       else if (g == 3) stage_unit(0, 1);
       else if (g == 4) stage_unit(0, 2);
