@@ -345,7 +345,7 @@ class OracleSMACNet(OracleActorCritic):
     def __init__(self, obs_dim, state_dim, act_dim, hidden_dim, chunk_len, num_rnn_layers=1, agent_shared=True, **_ignored):
         super().__init__(obs_dim={"local_obs": obs_dim}, action_dim=act_dim, hidden_dim=hidden_dim,
                          state_dim={"state": state_dim}, chunk_len=chunk_len, num_rnn_layers=num_rnn_layers,
-                         rnn_type="lstm", popart=True, shared_backbone=False)
+                         rnn_type="lstm", popart=True, shared_backbone=False, dtype=_ignored.get("dtype", torch.float32))
         self.agent_shared = agent_shared
 
     def _rnn_key(self, prefix, n, layer):

@@ -756,6 +756,7 @@ class HipNet:
             dc = [self._buf(f"{tag}{G.prefix}.dc{i}", N, H) for i in range(2)]
             ch = cc = None
             seq = hip.rnn_seq_supported("lstm", H)
+            assert seq or dout.ld == H, "the per-step cells read d y in rows of H"
             if seq:
                 hip.lstm_seq_bwd(dout.ptr, dout.ld, pre.ptr, w_hh, cin.ptr, cnew.ptr, rptr(0), N, H, C)
             for c in range(-1 if seq else C - 1, -1, -1):
@@ -782,6 +783,7 @@ class HipNet:
             dh = [self._buf(f"{tag}{G.prefix}.dh{i}", N, H) for i in range(2)]
             carry = None
             seq = hip.rnn_seq_supported("gru", H)
+            assert seq or dout.ld == H, "the per-step cells read d y in rows of H"
             if seq:
                 hip.gru_seq_bwd(dout.ptr, dout.ld, gi.ptr, gh.ptr, w_hh, hin.ptr, rptr(0), N, H, C)
             for c in range(-1 if seq else C - 1, -1, -1):

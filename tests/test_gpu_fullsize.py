@@ -291,11 +291,24 @@ def test_smac_config_full_size_step_vs_oracle():
                                               p_done=1 / 60, policy_state={"actor_hx": (1, 2 * H), "critic_hx": (1, 2 * H)})
     shared = trainer_api.make(config.Trainer("mappo", args=tr_args), config.Policy("smac_rnn", args=pol))
     onet = OracleSMACNet(30, 48, 9, H, 10)
-    onet.load_state_dict({k: v.numpy() for k, v in shared.policy.get_checkpoint()["state_dict"].items()})
+    sd0 = {k: v.numpy() for k, v in shared.policy.get_checkpoint()["state_dict"].items()}
+    onet.load_state_dict(sd0)
     oracle = OracleMappo(onet, **tr_args)
     sample = synthetic.to_sample_batch({k: v.copy() for k, v in arrays.items()})
     res = shared.step(sample)
     ostats, oout = oracle.step(arrays)
+    # the same step against the float64 oracle (30 720 LSTM rows per chunk on the time-loop kernels): loss terms, and the LSTM,
+    # rnn_norm and encoder gradients, within 3x the float32 oracle's error + 2e-6 of the largest element.  Bias gradients are column
+    # sums over all 307 200 rows; the actor LSTM's cancel to 2e-5 and carry 4.3e-6 of that from the float32 row reduction on both
+    # recurrent paths alike (SRL_RNN_SEQ=0 measures the same), where the float32 oracle's pairwise sums carry 5e-7: floor 1e-5
+    from rnn_ref import check_vs_float64
+    onet64 = OracleSMACNet(30, 48, 9, H, 10, dtype=torch.float64)
+    onet64.load_state_dict(sd0)
+    ostats64, _ = OracleMappo(onet64, **tr_args).step(arrays)
+    assert onet64.params["actor_rnn._AutoResetRNN__net.weight_hh_l0"].dtype == torch.float64
+    check_vs_float64(res.stats, shared.policy.net.flat_to_reference(shared.policy.net.grad.detach().cpu()),
+                     {torch.float32: (onet, ostats), torch.float64: (onet64, ostats64)}, ("policy_loss", "value_loss", "entropy"),
+                     bias_floor=1e-5)
     assert sample.analyzed_result.ret.shape == (Ts + 1, Bs, A, 1)
     err = np.abs(sample.analyzed_result.ret - oout["ret"]) / np.maximum(np.abs(oout["ret"]), 1.0)
     assert err.max() <= 1e-5, err.max()
