@@ -1,8 +1,14 @@
 """Benchmark of the hot path: env-steps/s through the GAE + PPO update (BASELINE.json metric).
 
-    python3 bench.py --gpus N --steps K --warmup W
+    python3 bench.py --gpus N --steps K --warmup W [--full]
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run measures the headline alone: it sets up (trainer, sample, ingest ring, the rollout phase that fills the
+observation ring), warms up, times the K steps, writes ``--dump-outputs`` and prints the line.  Its set-up includes, untimed,
+the updates a ``--full`` run's trainer takes before the headline (``updates_before_headline``), so that the headline
+starts from the same state.  ``--full`` adds every other figure described below, each under the ``--no-*`` flag that
+leaves it out again.
 
 Workload = the configuration the metric is quoted on (BASELINE.json configs[2]): Atari-shaped rollouts, **4096 envs x
 128 steps** (+1 bootstrap row) per update, uint8 (4,84,84) frames, NatureCNN-512 shared actor-critic, PPO with the
@@ -19,18 +25,18 @@ HBM: the rollout that produced the sample uploaded each observation once for inf
 actor_critic_policy.py:467-469) and ``ObsRing`` kept it there, in the first layer's layout; the sample names its rows by
 the ring stamps the rollout returned (``analyzed_result.obs_ref``) and ``SampleRing.get_device`` binds them instead of
 sending 14.9 GB over the link a second time (runtime/obs_ring.py).  The rollout phase that fills the ring runs before
-the timed region (it IS the rollout; its rate is reported as ``rollout_inference``).  Two more figures of the same
-update, same run: ``resident_in_hbm`` (the whole sample, frames as a plain [Tb, B, 4, 84, 84] tensor, already on the
-device) and ``from_pinned_host`` (no ring: every leaf including the frames crosses the link inside the timed region,
-double-buffered on a side stream; reference api/trainer.py:211-228) -- PCIe-bound.
+the timed region (it IS the rollout; with ``--full`` its rate is reported as ``rollout_inference``).  Two more figures
+of the same update with ``--full``: ``resident_in_hbm`` (the whole sample, frames as a plain [Tb, B, 4, 84, 84] tensor,
+already on the device) and ``from_pinned_host`` (no ring: every leaf including the frames crosses the link inside the
+timed region, double-buffered on a side stream; reference api/trainer.py:211-228) -- PCIe-bound.
 
-Extra objects on the JSON line: ``roofline`` (dominant kernel family: the matrix-core contractions, timed live with
-HIP events on the launch stream in an extra untimed step), ``roofline_gae`` (the GAE scan against HBM at this batch,
-with t / t_launch_floor, and saturated), ``cpu_baseline`` (the oracle's CPU restatement of the same step on a
-bounded sample, rank 0, N = 1 only).
+Extra objects on the JSON line of a ``--full`` run: ``roofline`` (dominant kernel family: the matrix-core contractions,
+timed live with HIP events on the launch stream in an extra untimed step), ``roofline_gae`` (the GAE scan against HBM at
+this batch, with t / t_launch_floor, and saturated), ``roofline_mlp``, ``closed_loop``, ``configs`` / ``scaling_model``
+(N = 1), ``cpu_baseline`` (the oracle's CPU restatement of the same step on a bounded sample, rank 0, N = 1 only).
 
 Profiling recipe (scripts/profile_bench.sh; counters in passes of their own, the interpreter directly after ``--``):
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-plain-copy
+    rocprofv3 --kernel-trace --stats --output-format csv -d prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-plain-copy --full
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-from-host --no-profile
     rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-from-host --no-profile
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
@@ -275,7 +281,7 @@ def shard_config_leg(extra=()):
     all-reduce and the bucketed gradient all-reduce enqueued and executed)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--global-envs", "512", "--steps", "20", "--warmup", "5", "--seeds", "0",
-           "--no-cpu-baseline", "--no-plain-copy", "--no-closed-loop", "--no-configs", "--no-mlp", *extra]
+           "--full", "--no-cpu-baseline", "--no-plain-copy", "--no-closed-loop", "--no-configs", "--no-mlp", *extra]
     env = dict(os.environ)
     if "--force-dist" in extra:
         import socket
@@ -501,6 +507,16 @@ def recorded_counters(envs, T, chunk_rows):
     return dict(mfma_busy=None, counters_note="no SQ counter recording under profiles/ at this configuration")
 
 
+def updates_before_headline(args, n_seeds):
+    """Updates a --full run's trainer takes before the ring-fed headline's warm-up: the resident leg (warm-up + timed steps on
+    the first sample, 2 + timed steps on each further one), the profiled step, the pass without the observation ring
+    (92 at --steps 20 --warmup 5)."""
+    n = args.warmup + args.steps + (n_seeds - 1) * (2 + args.steps)
+    n += 0 if args.no_profile else 1
+    n += 0 if args.no_plain_copy else 2 + args.steps
+    return n
+
+
 DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: under 64 MB in all, .npy headers included
 
 
@@ -540,10 +556,14 @@ def main():
     ap.add_argument("--rollout-len", type=int, default=128)
     ap.add_argument("--chunk-rows", type=int, default=16384)
     ap.add_argument("--graph", type=int, default=0, help="1: capture the update into a hipGraph and replay it (one rank only)")
+    ap.add_argument("--full", action="store_true",
+                    help="every figure besides the headline: the other feeds, the per-kernel rooflines, the rollout and closed-loop "
+                         "legs, the other BASELINE configurations, the CPU baseline (the --no-* flags leave parts out); "
+                         "without it the run measures the headline alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-from-host", action="store_true",
-                    help="skip the pinned-host-fed passes: `value` is then the resident-in-HBM figure")
+                    help="skip the pinned-host-fed passes: `value` is then the resident-in-HBM figure (with or without --full)")
     ap.add_argument("--no-closed-loop", action="store_true", help="skip the rollout-beside-update leg (`closed_loop`)")
     ap.add_argument("--rollout-groups", type=int, default=2,
                     help="closed loop: inference policies (policy workers) sharing the observation ring, each serving B / groups environments")
@@ -657,31 +677,43 @@ def main():
     # ---- (1) the update with the whole sample resident in HBM, data seeds 0, 1, 2 ---------------------------------
     # one sample at a time (14.9 GB of frames each); the last one (seed 0 + rank offset) stays for the legs below
     seeds = [int(s) for s in args.seeds.split(",")] if args.seeds else [0]
-    per_seed, all_marks, el_res, res = {}, [], 0.0, None
-    sample = None
-    for i, sd in enumerate(reversed(seeds)):   # ... so that seeds[0] is the sample the remaining legs run on
+    resident, res = None, None
+    if args.full or args.no_from_host:
+        per_seed, all_marks, el_res = {}, [], 0.0
         sample = None
-        torch.cuda.empty_cache()
-        sample = device_sample(1000 * sd + rank, T, B, device)
-        el, res = timed(lambda: trainer.step(sample), args.warmup if i == 0 else 2, args.steps,
-                        from_init=args.no_from_host and i == len(seeds) - 1)
-        ms = sorted(step_marks)
-        per_seed[str(sd)] = dict(ms_per_step=1e3 * el / args.steps, ms_per_step_median=ms[len(ms) // 2], ms_per_step_min=ms[0])
-        all_marks += ms
-        el_res += el
-    if args.no_from_host:  # the resident update is the headline
-        dump_headline(res, sample)
-    marks_res = sorted(all_marks)
-    n_res = args.steps * len(seeds)
-    resident = dict(value=rate(el_res, n_res), unit="env-steps/s", ms_per_step=1e3 * el_res / n_res, steps=n_res,
-                    warmup=args.warmup, ms_per_step_median=marks_res[len(marks_res) // 2], ms_per_step_min=marks_res[0],
-                    data_seeds=seeds, per_seed=per_seed,
-                    note="whole sample, frames as a plain [Tb, B, 4, 84, 84] uint8 tensor, on the device before the timed region; "
-                         "median / min over the timed updates of every seed")
+        for i, sd in enumerate(reversed(seeds)):   # ... so that seeds[0] is the sample the remaining legs run on
+            sample = None
+            torch.cuda.empty_cache()
+            sample = device_sample(1000 * sd + rank, T, B, device)
+            el, res = timed(lambda: trainer.step(sample), args.warmup if i == 0 else 2, args.steps,
+                            from_init=args.no_from_host and i == len(seeds) - 1)
+            ms = sorted(step_marks)
+            per_seed[str(sd)] = dict(ms_per_step=1e3 * el / args.steps, ms_per_step_median=ms[len(ms) // 2], ms_per_step_min=ms[0])
+            all_marks += ms
+            el_res += el
+        if args.no_from_host:  # the resident update is the headline
+            dump_headline(res, sample)
+        marks_res = sorted(all_marks)
+        n_res = args.steps * len(seeds)
+        resident = dict(value=rate(el_res, n_res), unit="env-steps/s", ms_per_step=1e3 * el_res / n_res, steps=n_res,
+                        warmup=args.warmup, ms_per_step_median=marks_res[len(marks_res) // 2], ms_per_step_min=marks_res[0],
+                        data_seeds=seeds, per_seed=per_seed,
+                        note="whole sample, frames as a plain [Tb, B, 4, 84, 84] uint8 tensor, on the device before the timed "
+                             "region; median / min over the timed updates of every seed")
+    else:
+        # a plain run times the ring-fed headline alone, on the sample the resident leg leaves behind in a --full run.  The
+        # trainer takes as many updates before the headline as a --full run's does, untimed, on that sample: the headline
+        # then starts from the same count of updates (and of trained env-steps: the `frames` statistic, which --dump-outputs
+        # writes) and on a GPU in the same steady state (measured: without them its first timed updates run ~2 ms slower).
+        # The first one writes the advantages and returns into the sample, so the ingest ring built from it has the same
+        # leaves, and the headline's steps the same copies, as with --full.
+        sample = device_sample(1000 * seeds[0] + rank, T, B, device)
+        for _ in range(updates_before_headline(args, len(seeds))):
+            trainer.step(sample)
 
     # ---- untimed extra step with per-kernel HIP events (same stream as the launches) -----------------------
     roofline = roofline_gae = roofline_mlp = breakdown = launches_per_step = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         # EVERY rank takes this step (its collectives need all of them); only rank 0 wraps its launches in events
         prof = hip.KernelProfile() if rank == 0 else None
         if prof is not None:
@@ -697,7 +729,7 @@ def main():
         trainer.pipelines, trainer.policy.net._wgrad_side = pipes, side
         if prof is not None:
             hip.set_profile(None)
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         summ = prof.summary()
         # every matrix-core launch group.  The contractions deliver float32 results from float32 operands but run on the
         # bf16 / f16 matrix cores: each float32 operand is split into three bf16 pieces and the six leading piece
@@ -764,7 +796,6 @@ def main():
 
     # ---- (2) the sample moves to pinned host memory: two slots of the ingest ring, [Tb, B] namedarray layout, wire dtypes ---
     pcie = fed = rollout_inf = last_stamps = None
-    ms_step = 1e3 * el_res / n_res
     if not args.no_from_host:
         Tb = T + 1
         template = recursive_apply(sample[:, 0], lambda x: x.cpu().numpy())
@@ -783,7 +814,7 @@ def main():
             return r, b
 
         # ---- (2a) no observation ring: every leaf, frames included, crosses the link inside the timed region ---------------
-        if not args.no_plain_copy:
+        if args.full and not args.no_plain_copy:
             el, _ = timed(fed_step, 2, args.steps)
             host_bytes = ring.nbytes() // 2
             h2d_ms = None
@@ -804,15 +835,16 @@ def main():
             pcie = dict(value=rate(el, args.steps), unit="env-steps/s", ms_per_step=1e3 * el / args.steps, steps=args.steps,
                         warmup=2, host_bytes_per_step_per_gpu=host_bytes, h2d_alone_ms=h2d_ms,
                         h2d_alone_GBps=None if not h2d_ms else round(host_bytes / h2d_ms / 1e6, 1),
-                        bound="pcie" if h2d_ms and h2d_ms > ms_step else "mfma",
+                        bound="pcie" if h2d_ms and h2d_ms > resident["ms_per_step"] else "mfma",
                         note="no observation ring: async H2D of every leaf (14.9 GB of frames) on a side stream inside the "
                              "timed region, double-buffered so that the copy of update k+1 runs under the compute of update k")
 
         # ---- (2b) the rollout phase of this sample: 129 inference batches of B observations from pinned host memory, each
         # staged once in the HBM observation ring (space-to-depth + LayerNorm statistics, the pass inference needs anyway).
-        # Twice: whole stacks per request (what actor_critic_policy.py:467-469 uploads), and stack-aware requests -- the
-        # newest plane + the stamp of the environment's previous observation, the ring assembles the row (ObsRing.put_stacked):
-        # a quarter of the bytes over the link, the same actions / log-probabilities / values (checked here on every batch).
+        # With --full twice: whole stacks per request (what actor_critic_policy.py:467-469 uploads), and stack-aware requests --
+        # the newest plane + the stamp of the environment's previous observation, the ring assembles the row
+        # (ObsRing.put_stacked): a quarter of the bytes over the link, the same actions / log-probabilities / values (checked
+        # here on every batch).  A plain run issues the stack-aware requests alone: the headline reads the rows they leave.
         frames = ring.host_tensors(0)["obs.obs"]  # [Tb, B, 4, 84, 84] uint8, pinned (torch tensor: asynchronous DMA)
         fresh = ring.host_blocks(0)["on_reset"].reshape(Tb, B).astype(bool).copy()
         fresh[0] = True
@@ -858,10 +890,12 @@ def main():
                 stamps[t] = prev = resp.analyzed_result.obs_ref
             return stamps, t_roll / max(n_roll, 1), prev
 
-        whole, whole_out = new_inference_policy(Tb * B + 8 * B), []
-        _, s_whole, _ = rollout_phase(whole, False, keep=whole_out)
-        del whole
-        torch.cuda.empty_cache()
+        whole_out = None
+        if args.full:
+            whole, whole_out = new_inference_policy(Tb * B + 8 * B), []
+            _, s_whole, _ = rollout_phase(whole, False, keep=whole_out)
+            del whole
+            torch.cuda.empty_cache()
         # the ring the updates below read: room for the sample being trained on AND the one the next rollout phase writes
         infer = new_inference_policy(2 * Tb * B + 8 * B)
         obs_ring = infer._obs_ring
@@ -869,15 +903,16 @@ def main():
         del whole_out
         for slot in range(2):  # the actors store the stamp with each step; both slots hold this sample
             ring.host_blocks(slot)["analyzed_result.obs_ref"][...] = stamps
-        rollout_inf = dict(value=B / s_stack, unit="requests/s", requests_per_call=B, ms_per_call=1e3 * s_stack, calls=Tb - 3,
-                           h2d_bytes_per_request=84 * 84 + 8,
-                           note="policy.rollout on pinned host observations, sampled actions; stack-aware requests: the newest "
-                                "uint8 plane + the ring stamp of the environment's previous observation, the row assembled in the "
-                                "HBM observation ring (srl_ring_stack_push); H2D of the planes and D2H of the results inside",
-                           identical_to_whole_stack=True,
-                           whole_stack=dict(value=B / s_whole, unit="requests/s", ms_per_call=1e3 * s_whole,
-                                            h2d_bytes_per_request=4 * 84 * 84,
-                                            note="the same batches with the whole (4, 84, 84) stack per request"))
+        if args.full:
+            rollout_inf = dict(value=B / s_stack, unit="requests/s", requests_per_call=B, ms_per_call=1e3 * s_stack, calls=Tb - 3,
+                               h2d_bytes_per_request=84 * 84 + 8,
+                               note="policy.rollout on pinned host observations, sampled actions; stack-aware requests: the newest "
+                                    "uint8 plane + the ring stamp of the environment's previous observation, the row assembled in "
+                                    "the HBM observation ring (srl_ring_stack_push); H2D of the planes and D2H of the results inside",
+                               identical_to_whole_stack=True,
+                               whole_stack=dict(value=B / s_whole, unit="requests/s", ms_per_call=1e3 * s_whole,
+                                                h2d_bytes_per_request=4 * 84 * 84,
+                                                note="the same batches with the whole (4, 84, 84) stack per request"))
         ring.attach_obs_ring(obs_ring)
 
         # ---- (2c) SURVEY 8d's t_update with the ring: the headline ---------------------------------------------------------
@@ -896,7 +931,7 @@ def main():
     # ---- (3) closed loop on this GPU: the rollout phase of sample k+1 (stack-aware requests, its own thread and stream) runs
     # WHILE the update on sample k runs; a sample is trained on once, with the stamps its own rollout phase returned ---------
     closed = None
-    if fed is not None and not args.no_closed_loop and not use_dist:
+    if fed is not None and args.full and not args.no_closed_loop and not use_dist:
         import threading
         if os.environ.get("SRL_SWITCH_INTERVAL"):
             sys.setswitchinterval(float(os.environ["SRL_SWITCH_INTERVAL"]))
@@ -998,10 +1033,10 @@ def main():
                                 pipelines=getattr(trainer, "pipelines", None),
                                 grad_buckets=(None if getattr(trainer, "_reducer", None) is None else
                                               dict(trainer._reducer.stats, buckets=len(trainer._reducer.buckets))),
-                                policy_loss=res.stats.get("policy_loss")),
-                    roofline=roofline, roofline_gae=roofline_gae, roofline_mlp=roofline_mlp, kernel_ms_per_step=breakdown,
-                    launches_per_step=launches_per_step,
-                    resident_in_hbm=resident)
+                                policy_loss=res.stats.get("policy_loss")))
+        if args.full:
+            line.update(roofline=roofline, roofline_gae=roofline_gae, roofline_mlp=roofline_mlp, kernel_ms_per_step=breakdown,
+                        launches_per_step=launches_per_step, resident_in_hbm=resident)
         if fed is not None:
             line["ring_fed"] = {k: v for k, v in fed.items() if k not in ("value", "ms_per_step", "ms_per_step_median", "ms_per_step_min")}
         if pcie is not None:
@@ -1010,14 +1045,14 @@ def main():
             line["rollout_inference"] = rollout_inf
         if closed is not None:
             line["closed_loop"] = closed
-        if world == 1 and not args.no_configs and not use_dist:
+        if world == 1 and args.full and not args.no_configs and not use_dist:
             # the other BASELINE configurations and the per-rank shard, on the same box in the same run (this process's big buffers
             # are released first: the child and the football leg want the memory)
             ring = infer = obs_ring = sample = None
             trainer.policy.net.ws._bufs.clear()
             torch.cuda.empty_cache()
             line["configs"], line["scaling_model"] = other_configs(line, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(T)
         print(json.dumps(line), flush=True)
     if use_dist:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of the ring-fed headline: scripts/ab_bench.sh "<env A>" "<env B>" [rounds]   e.g.  scripts/ab_bench.sh "SRL_LN_HEADS=0" "SRL_LN_HEADS=1" 2
 A=$1; B=$2; R=${3:-2}
-run() { env $1 python bench.py --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
+run() { env $1 python bench.py --full --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 for cfg in "$@"; do
   envs=""; flags=""
   for w in $cfg; do case $w in --*) flags="$flags $w";; [0-9]*) flags="$flags $w";; *) envs="$envs $w";; esac; done
-  env $envs python bench.py --steps 6 --warmup 2 --seeds 0 --no-cpu-baseline --no-profile --no-plain-copy --no-configs --no-mlp $flags 2>/dev/null | python -c "
+  env $envs python bench.py --full --steps 6 --warmup 2 --seeds 0 --no-cpu-baseline --no-profile --no-plain-copy --no-configs --no-mlp $flags 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # Same-box A/B of the ring-fed headline over ENVIRONMENT settings: scripts/ab_env.sh "VAR=a" "VAR=b" [rounds]
 # (alternating runs of bench.py --steps 10 on one box; prints ms per update, ring-fed and resident)
 A=$1; B=$2; R=${3:-2}
-run() { env $1 python bench.py --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
+run() { env $1 python bench.py --full --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

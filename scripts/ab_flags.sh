@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of the ring-fed headline over bench.py FLAGS: scripts/ab_flags.sh "<flags A>" "<flags B>" [rounds]
 A=$1; B=$2; R=${3:-2}
-run() { python bench.py --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp $1 2>/dev/null | python -c "
+run() { python bench.py --full --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp $1 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@
 A=$1; B=$2; R=${3:-2}
 X=""
 if [ -n "$DIST" ]; then X="--force-dist"; export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29541; fi
-run() { env $1 python bench.py --global-envs 512 --steps 40 --warmup 8 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp $X 2>/dev/null | python -c "
+run() { env $1 python bench.py --full --global-envs 512 --steps 40 --warmup 8 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp $X 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ import sys
 
 for c in [int(a) for a in sys.argv[1:]] or [16384, 24576, 32768, 40960]:
     out = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--chunk-rows", str(c), "--no-cpu-baseline",
-                          "--no-from-host"], capture_output=True, text=True)
+                          "--no-from-host", "--full"], capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:
         print(c, "failed", out.stderr[-400:])

@@ -1,7 +1,7 @@
 """cProfile of the benchmark script's Python side (ring-fed and resident updates, rollout legs): which host functions the steps spend
 their time in (cumulative, srl_amd's own files).  python scripts/prof_step.py"""
 import cProfile, pstats, sys, os, io
-sys.argv = ["bench.py", "--steps", "6", "--warmup", "2", "--seeds", "0", "--no-cpu-baseline", "--no-profile", "--no-plain-copy", "--no-closed-loop"]
+sys.argv = ["bench.py", "--steps", "6", "--warmup", "2", "--seeds", "0", "--no-cpu-baseline", "--no-profile", "--no-plain-copy", "--no-closed-loop", "--full"]
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import runpy
 pr = cProfile.Profile()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the 512-env shard (one rank of an 8-GPU run) without and with a one-rank RCCL process group, then a kernel trace of the latter
 cd "$GRAFT_REPO_ROOT"
-A="--global-envs 512 --steps 20 --warmup 5 --seeds 0 --no-cpu-baseline --no-plain-copy --no-closed-loop --no-configs --no-mlp --no-profile"
+A="--full --global-envs 512 --steps 20 --warmup 5 --seeds 0 --no-cpu-baseline --no-plain-copy --no-closed-loop --no-configs --no-mlp --no-profile"
 python3 bench.py $A | python3 -c "import json,sys; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('plain', d['ms_per_step'], d['resident_in_hbm']['ms_per_step'])"
 export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533
 python3 bench.py $A --force-dist | python3 -c "import json,sys; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('dist ', d['ms_per_step'], d['resident_in_hbm']['ms_per_step'], d['config']['grad_buckets'])"

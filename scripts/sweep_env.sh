@@ -7,7 +7,7 @@ X="--steps 10 --warmup 3"
 if [ "$LEG" = dist ]; then X="$X --force-dist"; export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29543; fi
 for i in $(seq $R); do for v in $VALS; do
   if [ "$v" = "-" ]; then unset $V; else export $V=$v; fi
-  python bench.py $X --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
+  python bench.py --full $X --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

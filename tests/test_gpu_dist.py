@@ -199,7 +199,7 @@ def test_two_rank_ppg_auxiliary_phase_matches_ddp_semantics():
 
 
 def test_bench_script_with_two_ranks():
-    """bench.py exactly as the driver launches it for N = 2 (torch.distributed.run, one process per rank), except that
+    """bench.py --full as the driver launches it for N = 2 (torch.distributed.run, one process per rank), except that
     the two ranks share this box's GPU over gloo: every rank must reach the same collectives in the same order (warm-up,
     timed steps, the untimed profiled step, the final barrier) and rank 0 must print one JSON line."""
     import json
@@ -210,7 +210,7 @@ def test_bench_script_with_two_ranks():
     env = dict(os.environ, SRL_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--global-envs", "32", "--rollout-len", "8", "--chunk-rows", "64"]  # 128 rows per rank: one chunk per pipeline
+           "--global-envs", "32", "--rollout-len", "8", "--chunk-rows", "64", "--full"]  # 128 rows per rank: one chunk per pipeline
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
