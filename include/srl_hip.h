@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SRL_HIP_ABI_VERSION 18
+#define SRL_HIP_ABI_VERSION 19
 
 int srl_abi_version(void);
 const char* srl_last_error(void);
@@ -785,6 +785,58 @@ int srl_sgd_step(void* stream, float* p, const float* g, float* momentum_buf, in
 int srl_rmsprop_step(void* stream, float* p, const float* g, float* square_avg, float* momentum_buf, float* grad_avg,
                      int64_t n, float lr, float alpha, float eps, float weight_decay, float momentum, int centered,
                      float grad_scale, float max_norm, const double* sumsq, float* grad_norm_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Agent-specific attention encoder of SMACNet (csrc/entity_attn.hip; ABI 19): everything in front of the dense tail of
+ * SMACAgentwiseEncoder (legacy/algorithm/ppo/game_policies/smac_rnn.py:29-84, modules/attention.py:7-92,116-122) as ONE launch
+ * per direction, float32 throughout.  Per row: LayerNorm (eps 1e-5, affine) of the self vector [S] and of every entity
+ * [f_k] of up to three entity leaves; self_emb = relu(W_s a_s + b_s) [D]; emb_e = relu(W_k cat(a_s, a_e) + b_k) [D] for
+ * the E = sum n_k entities in leaf order; pre_norm LayerNorm over D; q, k, v = Linear(D, D); 4 heads of D / 4;
+ * softmax(q k^T / sqrt(D / 4)) over the keys whose mask byte is non-zero (a masked key has probability 0; a row without
+ * any key yields 0); pooled = sum_e mask_e out_e / (sum_e mask_e + 1e-5).
+ * srl_entity_attn_fwd: out [rows, ldo], self_emb in columns [0, D), pooled in [D, 2D).
+ * srl_entity_attn_bwd: given d_out [rows, lddo] (2D columns read) ADDS the gradient of every parameter, the LayerNorm
+ *   affines included, into g[] (float atomics, once per workgroup for what it summed in LDS).  No tape: it walks forward again
+ *   from the leaves, which must still hold the rows the forward call saw, under the same parameters.  No input gradient
+ *   is formed (the inputs are observations).
+ * The descriptor is passed by value to the kernel: no allocation, no copy, no synchronisation -- capturable.
+ * srl_entity_attn_supported: 1 when D is 16, 32 or 64, 1 <= nkeys <= 3, 1 <= E <= 64, 1 <= S <= 128 and 1 <= f_k <= 64
+ * (one row's intermediates then fit the 160 KiB of LDS; parameters and gradient sums are staged there too when room is
+ * left, else read from / added to global memory), else 0.  The pointers are not looked at. */
+#define SRL_EATTN_MAX_KEYS 3
+enum {                      /* parameter slots of srl_entity_attn::p / ::g (k = entity leaf 0..2) */
+  SRL_EATTN_LN_SELF_W = 0,  /* [S] */
+  SRL_EATTN_LN_SELF_B = 1,
+  SRL_EATTN_LN_KEY_W = 2,   /* + k: [f_k] */
+  SRL_EATTN_LN_KEY_B = 5,   /* + k */
+  SRL_EATTN_SELF_W = 8,     /* [D, S] row-major */
+  SRL_EATTN_SELF_B = 9,     /* [D] */
+  SRL_EATTN_KEY_W = 10,     /* + k: [D, S + f_k], the self columns first */
+  SRL_EATTN_KEY_B = 13,     /* + k: [D] */
+  SRL_EATTN_PRE_W = 16,     /* pre_norm [D] */
+  SRL_EATTN_PRE_B = 17,
+  SRL_EATTN_Q_W = 18,       /* [D, D] */
+  SRL_EATTN_Q_B = 19,
+  SRL_EATTN_K_W = 20,
+  SRL_EATTN_K_B = 21,
+  SRL_EATTN_V_W = 22,
+  SRL_EATTN_V_B = 23,
+  SRL_EATTN_SLOTS = 24
+};
+typedef struct srl_entity_attn {
+  int32_t D, S, nkeys, E;                 /* E = sum cnt[k] = width of the mask */
+  int32_t cnt[SRL_EATTN_MAX_KEYS];        /* entities per leaf */
+  int32_t f[SRL_EATTN_MAX_KEYS];          /* features per entity */
+  const float* p[SRL_EATTN_SLOTS];        /* parameters (slots of absent leaves: NULL) */
+  float* g[SRL_EATTN_SLOTS];              /* their gradients, accumulated into (srl_entity_attn_bwd only) */
+  const float* x_self;                    /* [rows, ld_self], S columns read */
+  const float* x_key[SRL_EATTN_MAX_KEYS]; /* [rows, ld_key[k]], cnt[k] * f[k] columns read (entity-major) */
+  const uint8_t* mask;                    /* [rows, ld_mask], E bytes read */
+  int64_t ld_self, ld_key[SRL_EATTN_MAX_KEYS], ld_mask;
+} srl_entity_attn;
+int srl_entity_attn_supported(const srl_entity_attn* d);
+int srl_entity_attn_fwd(void* stream, const srl_entity_attn* d, int64_t rows, float* out, int64_t ldo);
+int srl_entity_attn_bwd(void* stream, const srl_entity_attn* d, int64_t rows, const float* d_out, int64_t lddo);
 
 /* ------------------------------------------------------------------------------------------------
  * Native step driver (launch-bound configurations).  The device part of MultiAgentPPO.step (mappo.py:219-328) is

@@ -59,6 +59,18 @@ def to_device_leaf(x, device, kind: str) -> torch.Tensor:
     return t.to(device, non_blocking=True).contiguous()
 
 
+def obs_leaves(obs):
+    """``(key, leaf, kind)`` of every leaf of an observation struct.  A nested struct (the agent-specific SMAC observations:
+    ``local_obs`` / ``state`` as NamedArrays of per-entity leaves) gives dotted keys, ``local_obs.obs_allies``; its ``*_mask`` leaves
+    travel as bytes (``kind`` "flag"), which is how the attention kernel reads them."""
+    for k, v in obs.items():
+        if isinstance(v, NamedArray):
+            for kk, vv, _ in obs_leaves(v):
+                yield f"{k}.{kk}", vv, ("flag" if kk.endswith("_mask") else "obs")
+        else:
+            yield k, v, "obs"
+
+
 def wire_leaf(x, kind: str):
     """Like ``to_device_leaf`` but a host leaf STAYS on the host: a contiguous numpy array in the dtype the kernels read
     (what the native step driver copies straight into a captured step's static inputs).  Device tensors pass through."""
@@ -616,10 +628,10 @@ class ActorCriticPolicy(policy_api.Policy):
         T = Tall - burn  # analysed rows: [burn, Tall) (:346-349)
         n = T * B
         obs, full_obs = {}, {}
-        for k, v in sample.obs.items():
+        for k, v, kind in obs_leaves(sample.obs):
             if v is None:
                 continue
-            t = mg(to_device_leaf(v, self.device, "obs"))
+            t = mg(to_device_leaf(v, self.device, kind))
             full_obs[k] = t
             obs[k] = t[burn:].reshape(n, *t.shape[2:])
         avail = obs.pop("available_action", None)

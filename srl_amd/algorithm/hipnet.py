@@ -12,6 +12,7 @@ LayerNorm         ``srl_layernorm_fwd``                      ``srl_layernorm_bwd
 first Conv2d      ``srl_obs_ln_stats`` + ``srl_im2col_obs_ln``  GEMMs + ``srl_obs_ln_affine_bwd``
                   (uint8 -> LN -> patches) + ``srl_gemm``
 later Conv2d      ``srl_im2col_nhwc`` + ``srl_gemm``             GEMMs + ``srl_col2im_nhwc`` (act' fused)
+entity attention  ``srl_entity_attn_fwd`` (several leaves)   ``srl_entity_attn_bwd`` (walks forward again, no tape)
 ================  =========================================  ==========================================
 
 The gradient handed to a layer's ``backward`` is always w.r.t. its *pre-activation* output: whoever
@@ -255,6 +256,8 @@ class HipNet:
         LayerNorm statistics of every row), ("raw",) otherwise."""
         out = {}
         for enc in self._encoders():
+            if isinstance(enc.shape, dict):  # several leaves of a nested observation (entity attention): not staged in a ring
+                continue
             conv = next((L for L in enc.layers if isinstance(L, ns.ConvSpec) and L.first), None)
             lay = ("s2d", int(conv.s2d)) if conv is not None and conv.s2d and not self.force_explicit_conv else ("raw",)
             if out.setdefault(enc.key, lay) != lay:
@@ -262,7 +265,8 @@ class HipNet:
         return out
 
     def obs_raw_shapes(self) -> Dict[str, tuple]:
-        return {enc.key: ((enc.shape,) if isinstance(enc.shape, int) else tuple(enc.shape)) for enc in self._encoders()}
+        return {enc.key: ((enc.shape,) if isinstance(enc.shape, int) else tuple(enc.shape)) for enc in self._encoders()
+                if not isinstance(enc.shape, dict)}
 
     # ------------------------------------------------------------------ operand ranges (two-plane f16 forward products)
     RANGE_SLOTS = 1024  # tracked activations / gradients per pass (a piece-wise encoder pass of a deep tower uses dozens)
@@ -860,7 +864,24 @@ class HipNet:
                                  x_out=cur.ptr if (slabs and not self._infer) else None, ldxo=cur.ld)
                 tape.append(("lnheads", L, cur, (mean, rstd, heads), cur_act))
                 return None
-            if isinstance(L, ns.LayerNormSpec):
+            if isinstance(L, ns.EntityAttnSpec):
+                leaves = self._eattn_leaves(L, obs, n, enc.key)
+                y = self._buf(f"{tag}{L.prefix}.eattn.y", n, 2 * L.dim)
+                hip.entity_attn_fwd(self._eattn_desc(L), *leaves, n, y.ptr, y.ld)
+                # no tape: the backward launch walks forward again from the leaves (kept alive by the record)
+                tape.append(("eattn", L, leaves, obs, 0))
+                cur, cur_act, cur_range = y, 0, None
+                # the dense tail behind the block (LayerNorm -> Linear -> LayerNorm) as one launch per direction, like the flat
+                # encoders above; its backward also forms d loss / d (self_emb | pooled) for the block (chains that keep no tape)
+                rest = list(enc.layers[1:])
+                if (self._mlp_fused and self._enc_fused and n >= 512 and rest and lnheads is None
+                        and all(isinstance(M, (ns.LayerNormSpec, ns.LinearSpec)) for M in rest)
+                        and (isinstance(rest[-1], ns.LayerNormSpec) or rest[-1].act == 0)):
+                    rec = self._fused_layers_fwd((tag, "enc", enc.key), f"{tag}enc.{enc.key}.", rest, y, n, need_dx=True)
+                    if rec is not None:
+                        tape.append(("fusedtail", rec, None, None, 0))
+                        return rec["feat"]
+            elif isinstance(L, ns.LayerNormSpec):
                 if cur is None:
                     if obs.dtype != torch.float32:
                         raise hip.HipError(f"vector observation `{enc.key}` must be float32, got {obs.dtype}")
@@ -1056,6 +1077,11 @@ class HipNet:
                 g = self._linear_bwd(L, x, g, in_act, need_dx, tag, x_range=x_range,
                                      dz_range=g_range if x_range is not None else None, dx_range=dx_range)
                 g_range = dx_range
+            elif kind == "eattn":   # one launch: every parameter of the block is final behind it
+                hip.entity_attn_bwd(self._eattn_desc(L), *x, g.rows, g.ptr, g.ld)
+                self._release(L.prefixes)
+                g, g_range = None, None
+                continue
             elif kind == "fusedenc":
                 self._fused_bwd(L, g.ptr, g.ld)   # (releases its layers' buckets itself)
                 g, g_range = None, None
@@ -1235,6 +1261,8 @@ class HipNet:
             return L["feat"].cols
         if kind == "lnheads":
             return L.dim
+        if kind == "eattn":
+            return 2 * L.dim
         if kind == "linear":
             return L.out_features
         if kind == "gru":
@@ -1259,8 +1287,9 @@ class HipNet:
         last recurrent layer are LayerNorm / Linear no wider than 64, they and the head run as ONE launch per direction
         (`fusedtail`; the tape's last field says whether the head went in)."""
         for enc in encoders:
-            if enc.key not in obs:
-                raise KeyError(f"observation key `{enc.key}` missing from the sample (has {list(obs)})")
+            for key in self._enc_keys(enc):
+                if key not in obs:
+                    raise KeyError(f"observation key `{key}` missing from the sample (has {list(obs)})")
         # the encoders see independent rows: more rows than one launch may address (recurrent nets hand over every
         # row of the sample at once) go through in pieces, each piece with its own tape; the features of all pieces
         # are gathered into one [n, width] block for the backbone, which walks the time axis
@@ -1275,7 +1304,7 @@ class HipNet:
             tapes, outs = [], []
             for enc in encoders:
                 tape = []
-                outs.append(self._encoder_fwd(enc, obs[enc.key][r0:r1], r1 - r0, ptag, tape, lnheads=lnheads))
+                outs.append(self._encoder_fwd(enc, self._enc_obs(enc, obs, r0, r1), r1 - r0, ptag, tape, lnheads=lnheads))
                 tapes.append(tape)
             enc_tapes.append(tapes)
             if lnheads is not None and tapes[0] and tapes[0][-1][0] == "lnheads":   # (one piece, one encoder: _lnheads_ok)
@@ -1331,6 +1360,50 @@ class HipNet:
                 self._join_side()  # the pieces share their backward buffers: the next one must not overtake this one's
                 # weight gradients on the second stream
         self.grad_ready_hook = hook
+
+    # ------------------------------------------------------------------ entity attention over the leaves of a nested observation
+    @staticmethod
+    def _enc_keys(enc):
+        """The sample keys an encoder reads: its own, or -- an encoder over a nested observation -- `<key>.<leaf>` per leaf."""
+        A = enc.layers[0] if enc.layers and isinstance(enc.layers[0], ns.EntityAttnSpec) else None
+        return [enc.key] if A is None else [f"{enc.key}.{leaf}" for leaf in A.leaves]
+
+    def _enc_obs(self, enc, obs, r0, r1):
+        keys = self._enc_keys(enc)
+        if keys == [enc.key]:
+            return obs[enc.key][r0:r1]
+        return {k[len(enc.key) + 1:]: obs[k][r0:r1] for k in keys}
+
+    def _eattn_leaves(self, A: ns.EntityAttnSpec, obs, n: int, key: str):
+        """((self pointer, pitch), [(leaf pointer, pitch), ...], (mask pointer, pitch)) after checking every leaf against the spec:
+        the kernel takes sizes from the spec and never reads past a leaf."""
+        def leaf(name, shape, dtype):
+            t = obs[name]
+            if isinstance(t, torch.Tensor) and name == A.mask_key and t.dtype != torch.uint8:
+                t = (t != 0).to(torch.uint8)   # the kernel reads the mask as bytes (the policies upload it that way)
+                obs[name] = t
+            if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n, *shape) or not t.is_contiguous()):
+                raise hip.HipError(f"observation `{key}.{name}`: expected a contiguous {dtype} leaf of shape {(n, *shape)}, got "
+                                   f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+            return t.data_ptr(), int(math.prod(shape))
+        return (leaf(A.self_key, (A.self_dim,), torch.float32), [leaf(k, (c, f), torch.float32) for k, c, f in A.keys],
+                leaf(A.mask_key, (A.entities,), torch.uint8))
+
+    def _eattn_desc(self, A: ns.EntityAttnSpec):
+        """The block's descriptor over this executor's parameters and gradients (a host struct, passed to the kernel by value)."""
+        key = ("eattn", A.prefix, self.flat.data_ptr(), self.grad.data_ptr())
+        d = self._mlp_cache.get(key)
+        if d is None:
+            base = {"LN_SELF": (hip.EATTN_LN_SELF_W, hip.EATTN_LN_SELF_B), "LN_KEY": (hip.EATTN_LN_KEY_W, hip.EATTN_LN_KEY_B),
+                    "SELF": (hip.EATTN_SELF_W, hip.EATTN_SELF_B), "KEY": (hip.EATTN_KEY_W, hip.EATTN_KEY_B),
+                    "PRE": (hip.EATTN_PRE_W, hip.EATTN_PRE_B), "Q": (hip.EATTN_Q_W, hip.EATTN_Q_B),
+                    "K": (hip.EATTN_K_W, hip.EATTN_K_B), "V": (hip.EATTN_V_W, hip.EATTN_V_B)}
+            params, grads = {}, {}
+            for prefix, (kind, k) in A.slot_names().items():
+                for slot, what in zip(base[kind], ("weight", "bias")):
+                    params[slot + k], grads[slot + k] = self._p(f"{prefix}.{what}"), self._g(f"{prefix}.{what}")
+            d = self._mlp_cache[key] = hip.entity_attn_desc(A.dim, A.self_dim, [(c, f) for _, c, f in A.keys], params, grads)
+        return d
 
     # ------------------------------------------------------------------ small MLP chains in one launch per direction
     def _fused_fwd(self, tag, encoders, backbone, head, obs, n: int, out: Optional[torch.Tensor] = None):

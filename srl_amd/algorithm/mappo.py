@@ -32,7 +32,7 @@ import torch.distributed as dist
 
 from srl_amd import hip
 from srl_amd.algorithm import netspec as ns
-from srl_amd.algorithm.actor_critic import ActorCriticPolicy, to_device_leaf, wire_leaf
+from srl_amd.algorithm.actor_critic import ActorCriticPolicy, obs_leaves, to_device_leaf, wire_leaf
 from srl_amd.api.trainer import PytorchTrainer, TrainerStepResult, register
 from srl_amd.namedarray import recursive_apply
 from srl_amd.runtime.obs_ring import RingObs
@@ -450,15 +450,15 @@ class MultiAgentPPO(PytorchTrainer):
         # ---- the sample's leaves in their wire dtypes: on the device -- or, for a captured step (use_graph), wherever they
         # are: the native step driver copies them straight into the graph's static inputs ---------------------------------
         graphed = (self.use_graph and not self._dist and self._opt in ('adam', 'adamw')
-                   and not any(isinstance(v, RingObs) for v in sample.obs.values()))  # ring rows are bound per sample
+                   and not any(isinstance(v, RingObs) for _, v, _ in obs_leaves(sample.obs)))  # ring rows are bound per sample
         leaf = (lambda x, kind: wire_leaf(x, kind)) if graphed else (lambda x, kind: to_device_leaf(x, dev, kind))
         L = dict(on_reset=leaf(sample.on_reset, "flag"), done=leaf(sample.done, "flag"),
                  truncated=leaf(sample.truncated, "flag"), reward=leaf(sample.reward, "real"),
                  old_value=leaf(sample.analyzed_result.value, "real"), old_lp=leaf(sample.analyzed_result.log_probs, "real"),
                  action=leaf(sample.action.x, self.policy.action_kind()))
-        for k, v in sample.obs.items():
+        for k, v, kind in obs_leaves(sample.obs):  # (nested observations: one leaf per dotted key)
             if v is not None:
-                L[f"obs.{k}"] = leaf(v, "obs")
+                L[f"obs.{k}"] = leaf(v, kind)
         have_adv = sample.analyzed_result.adv is not None
         if have_adv:
             L["adv"] = leaf(sample.analyzed_result.adv, "real")

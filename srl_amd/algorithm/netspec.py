@@ -177,6 +177,47 @@ class ObsLayerNormSpec:
 
 
 @dataclasses.dataclass
+class EntityAttnSpec:
+    """Everything in front of the dense tail of ``SMACAgentwiseObsEncoder`` / ``...StateEncoder`` (``smac_rnn.py:29-84``): per-leaf
+    LayerNorms, ``CatSelfEmbedding``, ``MultiHeadSelfAttention`` (4 heads of ``dim / 4``) and ``masked_avg_pooling``
+    (``modules/attention.py:7-92,116-122``), one launch per direction (csrc/entity_attn.hip).  Output: ``[n, 2 * dim]`` =
+    ``cat(self_emb, pooled)``.  The entity leaves are concatenated along the entity axis in ``keys`` order (the sorted order in
+    which the reference's NamedArray hands them over)."""
+    prefix: str  # "actor_base" | "critic_base"
+    dim: int  # D = hidden_dim // 2
+    self_key: str  # leaf [n, S]
+    self_dim: int
+    keys: List[Tuple[str, int, int]]  # (leaf name, entities, features per entity): leaf [n, entities, features]
+    mask_key: str  # leaf [n, E]
+
+    @property
+    def entities(self):
+        return sum(c for _, c, _ in self.keys)
+
+    @property
+    def leaves(self):
+        return [self.self_key] + [k for k, _, _ in self.keys] + [self.mask_key]
+
+    def slot_names(self) -> Dict[str, Tuple[str, int]]:
+        """parameter name -> (slot base of srl_entity_attn::p, leaf index); names in the reference's state_dict."""
+        r, out = self.prefix, {}
+        out[f"{r}.{self.self_key}_norm"] = ("LN_SELF", 0)
+        for k, (name, _, _) in enumerate(self.keys):
+            out[f"{r}.{name}_norm"] = ("LN_KEY", k)
+        out[f"{r}.encoder.embedding.self_embedding.0"] = ("SELF", 0)
+        for k, (name, _, _) in enumerate(self.keys):
+            out[f"{r}.encoder.embedding.{name}_fc.0"] = ("KEY", k)
+        out[f"{r}.encoder.attn.pre_norm"] = ("PRE", 0)
+        for m in "qkv":
+            out[f"{r}.encoder.attn.{m}_linear"] = (m.upper(), 0)
+        return out
+
+    @property
+    def prefixes(self):
+        return list(self.slot_names())
+
+
+@dataclasses.dataclass
 class EncoderSpec:
     key: str
     shape: Union[int, Tuple[int, ...]]
@@ -585,11 +626,55 @@ def popart_keys_of(head: str):
     return (rms + "mean", rms + "mean_sq", rms + "debiasing_term")
 
 
-def build_smac_netspec(obs_dim: int, state_dim: int, act_dim: int, hidden_dim: int, num_rnn_layers: int = 1,
+def _smac_attn_base(b: "_Builder", root: str, side: str, shapes: Dict, H: int):
+    """``SMACAgentwiseObsEncoder`` / ``SMACAgentwiseStateEncoder`` (``smac_rnn.py:47-84``) in the reference's registration order,
+    with ``MultiHeadSelfAttention(H/2, 4, H/8)`` -- the evident intent of ``smac_rnn.py:35``, whose arguments are swapped (see
+    smac_policy.py).  ``shapes``: ``{side}_self (S,)``, ``{side}_mask (E,)`` and any of ``{side}_allies / _enemies / _move``
+    ``(entities, features)``."""
+    shapes = {k: tuple(int(x) for x in (v if isinstance(v, (tuple, list)) else (v,))) for k, v in dict(shapes).items()}
+    self_key, mask_key = f"{side}_self", f"{side}_mask"
+    others = sorted(k for k in shapes if k not in (self_key, mask_key))  # CatSelfEmbedding.others_keys / NamedArray order
+    allowed = [f"{side}_allies", f"{side}_enemies", f"{side}_move"]
+    if self_key not in shapes or mask_key not in shapes or not others or any(k not in allowed for k in others):
+        raise NotImplementedError(f"agent-specific `{side}` shapes need `{self_key}`, `{mask_key}` and entity leaves among {allowed}; "
+                                  f"got {sorted(shapes)}")
+    if H % 8 or len(shapes[self_key]) != 1 or len(shapes[mask_key]) != 1 or any(len(shapes[k]) != 2 for k in others):
+        raise NotImplementedError(f"agent-specific `{side}`: hidden_dim must be a multiple of 8, `{self_key}` (S,), `{mask_key}` (E,) "
+                                  "and every entity leaf (entities, features)")
+    D, S = H // 2, shapes[self_key][0]
+    keys = [(k, shapes[k][0], shapes[k][1]) for k in others]
+    if sum(c for _, c, _ in keys) != shapes[mask_key][0]:
+        raise ValueError(f"`{mask_key}` is {shapes[mask_key][0]} wide, the entity leaves hold {sum(c for _, c, _ in keys)} entities")
+    for k in [self_key, f"{side}_move", f"{side}_allies", f"{side}_enemies"]:  # normalize_keys order (:51-54, :71-74)
+        if k in shapes:
+            b.layernorm(f"{root}.{k}_norm", shapes[k][-1])
+
+    def fc(prefix, fin, init):  # nn.Linear's default reset, then the module's own initialiser (which consumes the generator)
+        b.linear(prefix, fin, D)
+        if b.init:
+            init(b.values[f"{prefix}.weight"])
+
+    xavier = torch.nn.init.xavier_uniform_
+    fc(f"{root}.encoder.embedding.self_embedding.0", S, xavier)  # attention.py:15-24
+    for k, _, f in keys:
+        fc(f"{root}.encoder.embedding.{k}_fc.0", S + f, xavier)
+    b.layernorm(f"{root}.encoder.attn.pre_norm", D)  # attention.py:69-76
+    for m in "qkv":
+        fc(f"{root}.encoder.attn.{m}_linear", D, lambda w: torch.nn.init.normal_(w, std=math.sqrt(0.125 / D)))
+    b.layernorm(f"{root}.encoder.dense.0", H)  # smac_rnn.py:36-37
+    b.linear(f"{root}.encoder.dense.1", H, H)
+    b.layernorm(f"{root}.encoder.dense.3", H)
+    layers = [EntityAttnSpec(root, D, self_key, S, keys, mask_key), LayerNormSpec(f"{root}.encoder.dense.0", H),
+              LinearSpec(f"{root}.encoder.dense.1", H, H, 1), LayerNormSpec(f"{root}.encoder.dense.3", H)]
+    return layers, shapes
+
+
+def build_smac_netspec(obs_dim: Union[int, Dict], state_dim: Union[int, Dict], act_dim: int, hidden_dim: int, num_rnn_layers: int = 1,
                        act_init_gain: float = 0.01, seed: Optional[int] = None):
-    """``SMACNet`` with flat (not agent-specific) observations (``game_policies/smac_rnn.py:88-167``): actor on
-    ``local_obs``, critic on ``state``, each ``LayerNorm -> mlp([d, H, H], ReLU, layernorm=True)`` -> ``AutoResetRNN``
-    -> ``LayerNorm``; heads ``policy_head`` and the PopArt ``value_head``.  The recurrent cell is an **LSTM**:
+    """``SMACNet`` (``game_policies/smac_rnn.py:88-167``): actor on ``local_obs``, critic on ``state``.  A flat side (an int
+    width) is ``LayerNorm -> mlp([d, H, H], ReLU, layernorm=True)``; an agent-specific side (an ordered dict of leaf shapes,
+    ``_smac_attn_base``) is the attention encoder ``EntityAttnSpec -> LayerNorm -> Linear -> ReLU -> LayerNorm``.  Then
+    ``AutoResetRNN`` -> ``LayerNorm``; heads ``policy_head`` and the PopArt ``value_head``.  The recurrent cell is an **LSTM**:
     ``AutoResetRNN``'s default ``rnn_type`` (``autoreset_rnn.py:9``) is what ``SMACNet`` gets (``:125-126``), so the
     stored state is ``cat(h, c)``, ``2 * hidden_dim`` wide.  Parameters are registered in the reference's
     ``state_dict`` order and initialised by replaying its constructor (``:137-160``)."""
@@ -600,14 +685,16 @@ def build_smac_netspec(obs_dim: int, state_dim: int, act_dim: int, hidden_dim: i
     try:
         b = _Builder(seed)
 
-        def base(root, din):
+        def base(root, side, din):
+            if isinstance(din, dict):
+                return _smac_attn_base(b, root, side, din, H)
             b.layernorm(f"{root}.0", din)
             b.linear(f"{root}.1.0", din, H)
             b.layernorm(f"{root}.1.2", H)
             b.linear(f"{root}.1.3", H, H)
             b.layernorm(f"{root}.1.5", H)
             return [LayerNormSpec(f"{root}.0", din), LinearSpec(f"{root}.1.0", din, H, 1), LayerNormSpec(f"{root}.1.2", H),
-                    LinearSpec(f"{root}.1.3", H, H, 1), LayerNormSpec(f"{root}.1.5", H)]
+                    LinearSpec(f"{root}.1.3", H, H, 1), LayerNormSpec(f"{root}.1.5", H)], din
 
         def rnn(root):
             bound = 1.0 / math.sqrt(H)
@@ -617,8 +704,9 @@ def build_smac_netspec(obs_dim: int, state_dim: int, act_dim: int, hidden_dim: i
                 b.uniform(f"{root}.bias_ih_l{l}", (4 * H,), bound)
                 b.uniform(f"{root}.bias_hh_l{l}", (4 * H,), bound)
 
-        a_layers = base("actor_base", obs_dim)
-        c_layers = base("critic_base", state_dim)
+        a_layers, obs_shape = base("actor_base", "obs", obs_dim)
+        c_layers, state_shape = base("critic_base", "state", state_dim)
+        base_names = list(b.params)  # actor_base's parameters, then critic_base's, in named_parameters() order
         a_bb = c_bb = []
         if num_rnn_layers:
             ar, cr = "actor_rnn._AutoResetRNN__net", "critic_rnn._AutoResetRNN__net"
@@ -635,11 +723,12 @@ def build_smac_netspec(obs_dim: int, state_dim: int, act_dim: int, hidden_dim: i
             b.values[pkeys[0]] = torch.zeros(1, dtype=torch.float64)
             b.values[pkeys[1]] = torch.zeros(1, dtype=torch.float64)
             b.values[pkeys[2]] = torch.zeros(1, dtype=torch.float64)
-        # re-initialisation in the reference's order (:137-160)
-        for root in ("actor_base", "critic_base"):
-            for lin in (f"{root}.1.0", f"{root}.1.3"):
-                b.orthogonal(f"{lin}.weight", math.sqrt(2))
-                b.zero(f"{lin}.bias")
+        # re-initialisation in the reference's order (:137-160): every >= 2-D `weight` of the two bases orthogonal, every `bias` zero
+        for name in base_names:
+            if name.endswith("weight") and len(b.params[name].ref_shape) >= 2:
+                b.orthogonal(name, math.sqrt(2))
+            if name.endswith("bias"):
+                b.zero(name)
         if num_rnn_layers:
             for root in (ar, cr):
                 for l in range(num_rnn_layers):
@@ -655,7 +744,7 @@ def build_smac_netspec(obs_dim: int, state_dim: int, act_dim: int, hidden_dim: i
     for info in b.params.values():
         info.offset = off
         off += (info.numel + 3) // 4 * 4
-    spec = NetSpec([EncoderSpec("local_obs", obs_dim, a_layers, H)], a_bb, [EncoderSpec("state", state_dim, c_layers, H)], c_bb,
+    spec = NetSpec([EncoderSpec("local_obs", obs_shape, a_layers, H)], a_bb, [EncoderSpec("state", state_shape, c_layers, H)], c_bb,
                    LinearSpec("policy_head", H, act_dim, 0), LinearSpec("value_head", H, 1, 0), [act_dim], H, 1, False,
                    b.params, off, True, num_rnn_layers, None, 2 * H if num_rnn_layers else 0, pkeys)
     return spec, (b.values if b.init else None)

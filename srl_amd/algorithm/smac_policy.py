@@ -8,7 +8,7 @@ rollout requests; the agents are folded into the batch axis for the network and 
 ``:349-353``, ``:390-392``), and steps of dead agents (``obs.is_alive == 0``) get a new log-probability of ``-inf`` so
 that no policy gradient flows through them (``:309-311``).
 
-Two things differ from the reference file, both because it cannot run as shipped:
+Three things differ from the reference file, all because it cannot run as shipped:
 
 * **state width.**  ``SMACNet`` builds ``AutoResetRNN(hidden, hidden, num_layers)`` without an ``rnn_type``, so it gets
   that module's default, an LSTM (``autoreset_rnn.py:9``), whose state is ``cat(h, c)`` -- ``2 * hidden_dim`` wide.  The
@@ -19,9 +19,26 @@ Two things differ from the reference file, both because it cannot run as shipped
 * **shapes.**  The reference asks a live ``StarCraft2Env`` for the observation sizes (``smac_env.py:17-20``).  There is
   no StarCraft here: sizes come from the ``obs_shape / state_shape / act_dim / n_agents`` keywords, or from
   ``SMAC_SHAPES`` for the maps listed there (the standard SMAC feature sizes).
+* **attention heads.**  ``SMACAgentwiseEncoder`` builds ``MultiHeadSelfAttention(hidden_dim // 2, hidden_dim // 2, 4)``
+  (``:35``) where the module's signature is ``(input_dim, heads, d_head)`` (``modules/attention.py:62``): ``H/2`` heads of width
+  4, a ``2H``-wide output, and ``nn.LayerNorm(hidden_dim)`` raises on the ``2.5 H``-wide concatenation (``:36,43-44``).  The
+  evident intent -- input ``H/2``, model width ``H/2``, 4 heads, the argument order ``hns_policy.py:49`` uses -- is
+  ``MultiHeadSelfAttention(H/2, 4, H/8)``; that is what runs here and what the golden fixtures pin
+  (``tests/golden/gen_smac_attn.py`` swaps the arguments in the harness while the reference builds its policy).
 
-Agent-specific (attention) encoders are not on the HIP path.
+Agent-specific (attention) encoders (``agent_specific_obs`` / ``agent_specific_state``, independently; ``:29-84``) take the
+per-entity split of that side as an ordered dict in ``obs_shape`` / ``state_shape``::
+
+    obs_shape = dict(obs_allies=(n_allies, f_a), obs_enemies=(n_enemies, f_e), obs_move=(1, f_m), obs_self=(S,), obs_mask=(E,))
+
+(``state_*`` likewise; any of the three entity leaves may be absent; ``E`` is the number of entities, in the order allies,
+enemies, move -- the sorted order in which the reference's NamedArray hands the leaves over).  ``obs.local_obs`` /
+``obs.state`` are then nested NamedArrays of those leaves, ``[T, B, agents, ...]`` in samples and ``[N, agents, ...]`` in
+requests.  Everything in front of the encoder's dense tail is one HIP launch per direction (``csrc/entity_attn.hip``); a split
+it does not take (``hip.entity_attn_supported``) raises ``NotImplementedError`` at construction.  ``SMAC_SHAPES`` records flat
+widths only, so ``map_name`` alone cannot turn the attention encoders on.
 """
+from collections.abc import Mapping
 from typing import Optional
 
 import numpy as np
@@ -29,7 +46,7 @@ import torch
 
 from srl_amd import hip
 from srl_amd.algorithm import netspec as ns
-from srl_amd.algorithm.actor_critic import ActorCriticPolicy, to_device_leaf
+from srl_amd.algorithm.actor_critic import ActorCriticPolicy, obs_leaves, to_device_leaf
 from srl_amd.algorithm.ppo_types import PPORolloutAnalyzedResult
 from srl_amd.api import policy as policy_api
 from srl_amd.api.env_utils import DiscreteAction
@@ -79,15 +96,30 @@ class SMACPolicy(ActorCriticPolicy):
                  n_agents: Optional[int] = None,
                  **kwargs):
         policy_api.Policy.__init__(self)
-        if agent_specific_obs or agent_specific_state:
-            raise NotImplementedError("agent-specific (attention) SMAC encoders are not on the HIP path")
-        if obs_shape is None or state_shape is None or act_dim is None or n_agents is None:
+        for flag, shape, what in ((agent_specific_obs, obs_shape, "obs"), (agent_specific_state, state_shape, "state")):
+            if flag and not isinstance(shape, Mapping):
+                raise NotImplementedError(
+                    f"agent-specific (attention) SMAC encoders need the per-entity split of the observation: pass {what}_shape as "
+                    f"an ordered dict ({what}_allies=(n, f), {what}_enemies=(n, f), {what}_move=(1, f), {what}_self=(S,), "
+                    f"{what}_mask=(E,)); the sizes recorded for a map name are flat widths only")
+            if not flag and isinstance(shape, Mapping):
+                raise ValueError(f"{what}_shape is a dict of leaves but agent_specific_{what} is not set")
+        given = [obs_shape, state_shape, act_dim, n_agents]
+        if any(x is None for x in given):
             if map_name not in SMAC_SHAPES:
                 raise ValueError(f"SMAC map `{map_name}`: no StarCraft here to ask for the observation sizes; pass "
                                  f"obs_shape, state_shape, act_dim and n_agents (known maps: {sorted(SMAC_SHAPES)})")
-            obs_shape, state_shape, act_dim, n_agents = SMAC_SHAPES[map_name]
-        self.spec, init = ns.build_smac_netspec(_width(obs_shape), _width(state_shape), int(act_dim), hidden_dim,
-                                                num_rnn_layers=num_rnn_layers, act_init_gain=act_init_gain, seed=seed)
+            obs_shape, state_shape, act_dim, n_agents = (k if x is None else x for x, k in zip(given, SMAC_SHAPES[map_name]))
+        self.spec, init = ns.build_smac_netspec(dict(obs_shape) if agent_specific_obs else _width(obs_shape),
+                                                dict(state_shape) if agent_specific_state else _width(state_shape), int(act_dim),
+                                                hidden_dim, num_rnn_layers=num_rnn_layers, act_init_gain=act_init_gain, seed=seed)
+        for enc in self.spec.obs_encoders + self.spec.state_encoders:
+            A = enc.layers[0]
+            if isinstance(A, ns.EntityAttnSpec) and not hip.entity_attn_supported(A.dim, A.self_dim, [(c, f) for _, c, f in A.keys]):
+                raise NotImplementedError(
+                    f"agent-specific `{enc.key}`: the fused attention encoder takes hidden_dim 32, 64 or 128, up to 3 entity leaves, "
+                    f"at most 64 entities of at most 64 features and a self vector of at most 128; got hidden_dim {hidden_dim}, "
+                    f"self {A.self_dim}, leaves {A.keys}")
         self._setup(init, chunk_len, seed, denormalize_value_during_rollout)
         self._popart_beta = float(popart_beta)
         self._popart_burn_in = 1000 if unbiased_popart else float("inf")  # smac_rnn.py:133-135
@@ -106,7 +138,7 @@ class SMACPolicy(ActorCriticPolicy):
     def rollout(self, requests: policy_api.RolloutRequest, **kwargs) -> policy_api.RolloutResult:
         hip.require_gpu()
         fold = (lambda t: t.reshape(t.shape[0] * t.shape[1], *t.shape[2:])) if self._shared else (lambda t: t)
-        obs = {k: fold(to_device_leaf(v, self.device, "obs")) for k, v in requests.obs.items() if v is not None}
+        obs = {k: fold(to_device_leaf(v, self.device, kind)) for k, v, kind in obs_leaves(requests.obs) if v is not None}
         obs.pop("is_alive", None)
         bs = int(np.asarray(requests.on_reset).shape[0])
         n = bs * (self._n_agents if self._shared else 1)
