@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box A/B of the ring-fed headline: scripts/ab_bench.sh "<env A>" "<env B>" [rounds]   e.g.  scripts/ab_bench.sh "SRL_LN_HEADS=0" "SRL_LN_HEADS=1" 2
+# Same-box A/B of the ring-fed headline: scripts/ab_bench.sh "<env A>" "<env B>" [rounds]   e.g.  scripts/ab_bench.sh "SRL_HIP_LIB=$PWD/srl_amd/csrc/libsrlhip.so" "SRL_HIP_LIB=$PWD/srl_amd/csrc/libsrlhip_nolines.so" 2   (scripts/build_variant.sh)
 A=$1; B=$2; R=${3:-2}
 run() { env $1 python bench.py --full --steps 10 --warmup 3 --seeds 0 --no-cpu-baseline --no-profile --no-closed-loop --no-plain-copy --no-configs --no-mlp 2>/dev/null | python -c "
 import sys, json

@@ -1,12 +1,11 @@
 """Gradients of a football-shaped step (full 676 M-parameter net, few rows) on the wide-dense pre-split path and on the
 layer-by-layer kernels, both against the float64 CPU oracle's backward pass.  FB_T x FB_B rows (default 20 x 26);
-SRL_H2_DENSE_MIN_ROWS must be <= that many rows for the pre-split path to engage."""
+``HipNet.H2D_MIN_ROWS`` is lowered to 256 so that the pre-split path engages at that many rows."""
 import math
 import os
 import sys
 import time
 
-os.environ.setdefault("SRL_H2_DENSE_MIN_ROWS", "256")
 import numpy as np
 import torch
 
@@ -29,6 +28,7 @@ from srl_amd.api import config, trainer as trainer_api
 from srl_amd.runtime import synthetic
 
 srl_amd.register_all()
+HipNet.H2D_MIN_ROWS = 256
 T, B, H = int(os.environ.get("FB_T", 20)), int(os.environ.get("FB_B", 26)), 128
 TR = dict(popart=True, clip_value=True, value_loss="huber", value_loss_config=dict(delta=10.0), max_grad_norm=10.0,
           optimizer_config=dict(lr=5e-4, eps=1e-5))

@@ -1,5 +1,5 @@
-"""Fused MLP chain (srl_mlp_fwd + srl_mlp_bwd) on the 2 x 64 nets of BASELINE configs[0] at 65 536 rows:
-SRL_MLP_MFMA=0 -> the FMA chain (mlp_small.hip), default -> the float32 matrix-core chain (mlp_mfma.h)."""
+"""Fused MLP chain (srl_mlp_fwd + srl_mlp_bwd) on the 2 x 64 nets of BASELINE configs[0], 65 536 rows by default (argv[1]):
+from 512 rows the float32 matrix-core chain (mlp_mfma.h), below that the FMA chain (mlp_small.hip)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,4 +34,4 @@ e.record()
 torch.cuda.synchronize()
 us = a.elapsed_time(e) / 50 * 1e3
 flops = 6 * rows * sum(dims[i] * dims[i + 1] for i in range(len(dims) - 1)) - 2 * rows * dims[0] * dims[1]
-print(f"rows {rows}: fwd + bwd {us:8.1f} us, {flops / us / 1e6:6.2f} TFLOP/s (float32), SRL_MLP_MFMA={os.environ.get('SRL_MLP_MFMA', 'default')}", flush=True)
+print(f"rows {rows}: fwd + bwd {us:8.1f} us, {flops / us / 1e6:6.2f} TFLOP/s (float32)", flush=True)

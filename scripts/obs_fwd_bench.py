@@ -1,5 +1,5 @@
-"""Timing of the first layer's forward kernels on one 16 384-frame chunk (HIP events, the launch stream):
-SRL_OBS_H2BLOCK=0/1 selects obs_bf16.h's per-position kernel or obs_h2.h's block kernel."""
+"""Timing of the first layer's forward on one 16 384-frame chunk of the Atari geometry (HIP events, the launch stream):
+obs_h2.h's block kernel, consecutive and permuted slots."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,4 +35,4 @@ for order in ("index", "span"):
     e.record()
     torch.cuda.synchronize()
     us = a.elapsed_time(e) / 20 * 1e3
-    print(f"obs fwd h2 ({order}, block={os.environ.get('SRL_OBS_H2BLOCK', '1')}): {us:8.1f} us  {2 * n * 400 * 32 * 256 / us / 1e6:7.1f} TFLOP/s algorithmic", flush=True)
+    print(f"obs fwd h2 ({order}): {us:8.1f} us  {2 * n * 400 * 32 * 256 / us / 1e6:7.1f} TFLOP/s algorithmic", flush=True)

@@ -13,7 +13,7 @@ the encoder read); ``backward`` takes the gradient with respect to it.  Formats 
     a3  --Linear (h2gemm)-->  y float32 [n, 512] + sign words
     dy (float32) --pack--> h2p rows --Linear dgrad (h2gemm, mask a3)--> dz3: h2p rows --conv3 dgrad (mask a2)--> dz2: planar
     dz2 --conv2 dgrad (mask a1)--> dz1: float32 NHWC --> the first layer's backward (obs_bwd, round 2)
-    weight gradients: conv3 (a2, dz3), conv2 (a1, dz2) image-stationary; the Linear's through the round-3 kernel.
+    weight gradients: conv3 (a2, dz3), conv2 (a1, dz2) image-stationary; the Linear's on (dyh, a3) through csrc/h2tn.h.
 """
 import os
 import weakref
@@ -139,11 +139,11 @@ class H2Cnn:
     # Inference batches: the Linear's 3136-long reduction split over FC_SPLITK workgroups per tile -- the rows alone leave most CUs
     # idle (2048 rows are 32 tiles: 104 us; in 8 k-ranges 27 + 4 us for adding the slabs).  The SAME eight k-ranges for every row
     # count that takes this path: a row's result must not depend on the batch it arrives in (the streamed pieces of a large batch
-    # and one small batch sample the same actions, bit for bit).  SRL_FC_SPLITK=1 switches it off (A/B).
-    FC_SPLITK = int(os.environ.get("SRL_FC_SPLITK", "8"))
+    # and one small batch sample the same actions, bit for bit).
+    FC_SPLITK = 8
 
     def fc_splits(self, n: int) -> int:
-        return self.FC_SPLITK if (n <= 8192 and self.H % 128 == 0 and self.FC_SPLITK > 1) else 1
+        return self.FC_SPLITK if (n <= 8192 and self.H % 128 == 0) else 1
 
     # Training chunks with the closing LayerNorm + heads as the consumer (opt-in, SRL_FC_TRAIN_SPLITK=2): 256 channels per workgroup
     # stage a third fewer bytes per multiply-add (the forward is bound by its ring fill) but are only 128 tiles at 16 384
@@ -227,7 +227,7 @@ class H2Cnn:
             # dy -> h2p rows (its range from one pass: the producer is a float32 kernel that did not track it)
             hip.absmax(dy.ptr, n * self.H, P(M_DY))
         dyh = self._bytes(f"{t}dy", n * self.H * 4)
-        if self.FC_WGRAD_TN and self.H <= 2048:
+        if self.H <= 2048:
             # the Linear's bias gradient = the column sums of dy, from the pass that splits it (a pass of its own: 32 us per chunk)
             pws = ws.get("h2pack_colsum", hip.h2_pack_rows_colsum_workspace(n, self.H)).data_ptr()
             hip.h2_pack_rows_colsum(dy.ptr, self.H, n, self.H, dyh, pws, g(f"{self.fc.prefix}.bias"), absmax=P(M_DY), scale_out=P(S_DY))
@@ -290,29 +290,15 @@ class H2Cnn:
                            dz_absmax_ptr=dz_absmax_ptr)
 
     # The Linear's weight gradient on the pre-split operands both products of the data-gradient chain read anyway (dyh, a3) through
-    # csrc/h2tn.h (round 6: DMA in, transposing reads out); SRL_FC_WGRAD_TN=0: round 3's kernel on the float32 dy (A/B).
-    FC_WGRAD_TN = os.environ.get("SRL_FC_WGRAD_TN", "1") != "0"
-
+    # csrc/h2tn.h (round 6: DMA in, transposing reads out)
     def _fc_wgrad(self, n, dy, dyh, a3, tag):
         net, g = self.net, self.net._g
         H = self.H
         side = net._side_stream is not None and torch.cuda.current_stream() == net._side_stream
-        gb = g(f"{self.fc.prefix}.bias")
-        if self.FC_WGRAD_TN:
-            wsp = net.ws.get("h2tn_side" if side else "h2tn", hip.h2_wgrad_dense_workspace(n, H, 3136)).data_ptr()
-            hip.h2_wgrad_dense(dyh, a3, self._slot(S_DY, tag), self._slot(S_A3, tag), n, H, 3136, wsp, g(f"{self.fc.prefix}.weight"))
-            if H > 2048:   # (else: summed by the pack launch, `backward`)
-                hip.colsum(dy.ptr, dy.ld, n, H, gb, accumulate=True)
-            return
-        tiles = ((H + 127) // 128) * ((3136 + 127) // 128)
-        from srl_amd.algorithm.hipnet import _split_for
-        split = _split_for(n, tiles)
-        wsp = net.ws.get("splitk_side" if side else "splitk", split * H * 3136).data_ptr() if split > 1 else None
-        fused = hip.gemm_colsum_ok(H, 3136, n, dy.ptr, dy.ld, a3, 3136, 1)
-        hip.gemm(H, 3136, n, dy.ptr, dy.ld, 1, a3, 3136, 1, g(f"{self.fc.prefix}.weight"), 3136, accumulate=True, split_k=split,
-                 workspace=wsp, a_colsum=gb if fused else None, a_absmax=self._slot(M_DY, tag), b_h2_scale=self._slot(S_A3, tag))
-        if not fused:
-            hip.colsum(dy.ptr, dy.ld, n, H, gb, accumulate=True)
+        wsp = net.ws.get("h2tn_side" if side else "h2tn", hip.h2_wgrad_dense_workspace(n, H, 3136)).data_ptr()
+        hip.h2_wgrad_dense(dyh, a3, self._slot(S_DY, tag), self._slot(S_A3, tag), n, H, 3136, wsp, g(f"{self.fc.prefix}.weight"))
+        if H > 2048:   # (else: summed by the pack launch, `backward`)
+            hip.colsum(dy.ptr, dy.ld, n, H, g(f"{self.fc.prefix}.bias"), accumulate=True)
 
     def prefixes(self):
         return [self.ln.prefix, self.c1.prefix, self.c2.prefix, self.c3.prefix, self.fc.prefix]

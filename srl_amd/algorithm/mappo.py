@@ -60,9 +60,8 @@ class _BucketReducer:
     The LAST bucket to become final (the first layers' parameters, at the very end of the backward pass) has nothing left to
     overlap with: the clip and the optimiser step need it.  `finish` closes it ON the compute stream -- wait for the pipelines'
     tails, fold, all-reduce, all in stream order -- instead of through the reduction stream and the communicator's side stream
-    and back (three cross-stream dependencies in a row at the one place of an update where the GPU has nothing else to run;
-    SRL_LAST_BUCKET_INLINE=0: as before, A/B)."""
-    LAST_INLINE = os.environ.get("SRL_LAST_BUCKET_INLINE", "1") != "0"
+    and back (three cross-stream dependencies in a row at the one place of an update where the GPU has nothing else to run)."""
+    LAST_INLINE = True   # tests/test_dist_gloo.py clears it for the reduction-stream reference side
 
     def __init__(self, net, bucket_bytes, comm=None):
         self.net = net

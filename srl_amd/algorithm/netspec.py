@@ -345,11 +345,6 @@ def _pad_mode(padding, padding_mode, extents) -> int:
     return PAD_MODES[padding_mode] if padding else 0
 
 
-def _small_first_on() -> bool:
-    import os
-    return os.environ.get("SRL_CONV_SMALL", "1") != "0" and os.environ.get("SRL_CONV_SMALL_FIRST", "1") != "0"
-
-
 def _build_encoders(b: _Builder, root: str, dims: Dict, hidden: int, act: int, act_name: str, cnn_layers: Dict,
                     use_maxpool: Optional[Dict] = None):
     encs = []
@@ -387,7 +382,7 @@ def _build_encoders(b: _Builder, root: str, dims: Dict, hidden: int, act: int, a
         # 4- or 8-plane observation (the football preset) -- runs as a direct vector-unit convolution on the written-out LayerNorm
         # (csrc/conv_small.hip, round 6; mirrors srl_conv2d_small_supported): the fused first-layer kernels put its 4 output
         # channels on 256 x 32 matrix-core tiles (59 + 122 ms per football-sized update against ~25 GB of activations)
-        if (not generic and _small_first_on() and s0 == 1 and k0 in (3, 5) and c in (4, 8) and cfg[0][0] in (4, 8)
+        if (not generic and s0 == 1 and k0 in (3, 5) and c in (4, 8) and cfg[0][0] in (4, 8)
                 and not (k0 == 5 and c == 8)):
             generic = True
         s2d = s0 if (not generic and _allow_s2d() and s0 >= 1 and k0 % s0 == 0 and h % s0 == 0 and w % s0 == 0 and

@@ -271,9 +271,7 @@ srlobs::ObsGeom obs_geom(const srl_conv_desc* d, const void* obs, const float* m
 int obs_bf16_split(long n, int P, int per_cu) {
   const long slots = 256L * per_cu;
   long want = (4 * slots + P - 1) / P;
-  static const long rows_min = [] { const char* e = getenv("SRL_OBS_SPLIT_ROWS"); return e ? atol(e) : 512L; }();  // tuning knob
-  if (rows_min < 512) want = n / rows_min;
-  const long cap = n / rows_min > 1 ? n / rows_min : 1;
+  const long cap = n / 512 > 1 ? n / 512 : 1;
   if (want > cap) want = cap;
   return (int)(want < 1 ? 1 : want);
 }
@@ -328,21 +326,15 @@ static long images_per_launch(const srl_conv_desc* d, int in_esize) {
 // pixels are therefore made neighbours: for stride S the taps of one parity class (kh % S, kw % S) read one pixel class, so
 // the classes are visited one after the other, the taps of a class back to back; inside, the two 16-channel blocks that
 // share a 128-byte line stay adjacent, and for more than 32 channels the line index is the outermost key (each phase then
-// touches 1 / lines-per-pixel of the region).  SRL_KPERM=0: ascending order (A/B switch).
+// touches 1 / lines-per-pixel of the region).
 static void fwd_kstep_order(const srl_conv_desc* d, GemmArgs* g) {
-  static const bool on = [] { const char* e = getenv("SRL_KPERM"); return !(e && e[0] == '0'); }();
   const int C = (int)d->Cin, n = (int)(d->KH * d->KW * C / 16);
-  if (!on || C % 16 != 0 || n < 2) return;
+  if (C % 16 != 0 || n < 2) return;
   g->kp_s = (int)d->stride; g->kp_kh = (int)d->KH; g->kp_kw = (int)d->KW; g->kp_cb = C / 16;
 }
 
 // 192 x 64 forward tiles (2 x 2 wavefronts of 96 x 32): 49 KB of LDS, 3 workgroups per CU where 256 x 64 fits 2 -- conv2 /
-// conv3 forward 0.75 / 0.42 -> 0.73 / 0.40 ms (same box).  SRL_TILE192=0: the 256 x 64 tiles (A/B switch)
-static bool tile192() {
-  static const bool on = [] { const char* e = getenv("SRL_TILE192"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
+// conv3 forward 0.75 / 0.42 -> 0.73 / 0.40 ms (same box): the bf16 forward products with 33 to 64 output channels below.
 static int conv2d_nhwc_fwd_run(void* stream, const srl_conv_desc* d, const float* x, const float* w,
                                const float* bias, float* y, const float* x_absmax, const float* w_absmax,
                                float* y_absmax, uint32_t* y_mask, int w_presplit) {
@@ -372,13 +364,11 @@ static int conv2d_nhwc_fwd_run(void* stream, const srl_conv_desc* d, const float
   if (x3 && x_absmax && w_absmax && use_f16x2() && d->Cout > 32) {
     // both operands' ranges are known: two f16 pieces each, three products (gemm_bf16x3.h, NP == 2)
     rc = d->Cout > 64 ? launch3<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3, 2>(st, g, 1, 1)
-                      : (tile192() ? launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3, 2>(st, g, 1, 1)
-                                   : launch3<256, 64, 4, 1, false, false, SRC_CONV, SRC_PLAIN, K3, 2>(st, g, 1, 1));
+                      : launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3, 2>(st, g, 1, 1);
   } else
   if (d->Cout > 64) rc = x3 ? launch3<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1)
                             : launch<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
-  else if (d->Cout > 32) rc = x3 ? (tile192() ? launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1)
-                                                : launch3<256, 64, 4, 1, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1))
+  else if (d->Cout > 32) rc = x3 ? launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1)
                                  : launch<256, 64, 4, 1, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
   else rc = launch<256, 32, 4, 1, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
   SRL_CHECK_ARG(rc == 0, "grid too large");
@@ -666,8 +656,7 @@ static int conv2d_obs_fwd_run(void* stream, const srl_conv_desc* d, const void* 
     const ObsIndex ix{d->Cin, d->H, d->W, d->KH, d->KW, d->stride, OW, 1};
     float* bound = b2 + (long)P * d->Cout;  // one of the workspace's 64 spare floats: upper bound of |y| from the folded weights
     // h2 output on the Atari geometry: blocks of 2 x 4 positions per workgroup, two f16 weight pieces in registers (obs_h2.h)
-    static const bool blocks_on = [] { const char* e = getenv("SRL_OBS_H2BLOCK"); return !(e && e[0] == '0'); }();
-    if (y_h2 && blocks_on && ent_order == 2 && obs_h2_block_geometry(d) && d->n * (long)P * 128 < 0x7fffffffL &&
+    if (y_h2 && ent_order == 2 && obs_h2_block_geometry(d) && d->n * (long)P * 128 < 0x7fffffffL &&
         (records || 4 * (d->n + 32) + (long)P * d->Cout <= (long)P * d->Cout * Kp / 2)) {  // (the records fit behind the two planes)
       float* winv = workspace + (long)P * d->Cout * Kp;  // behind the two f16 planes, inside the room of the three bf16 ones
       if (!reuse_folded) obs_h2_fold(st, d, gamma, beta, w, bias, workspace);
@@ -788,8 +777,7 @@ extern "C" int srl_conv2d_obs_fwd(void* stream, const srl_conv_desc* d, const vo
 
 extern "C" int srl_conv2d_obs_fold_h2(void* stream, const srl_conv_desc* d, const float* gamma, const float* beta, const float* w,
                                       const float* bias, float* workspace) {
-  static const bool blocks_on = [] { const char* e = getenv("SRL_OBS_H2BLOCK"); return !(e && e[0] == '0'); }();
-  if (check_desc(d) != 0 || !blocks_on || !obs_h2_block_geometry(d)) return 1;  // not the block kernel's layer: nothing written
+  if (check_desc(d) != 0 || !obs_h2_block_geometry(d)) return 1;  // not the block kernel's layer: nothing written
   SRL_CHECK_ARG(gamma && beta && w && workspace && aligned16(workspace) && aligned16(gamma) && aligned16(beta), "null / unaligned tensor");
   obs_h2_fold((hipStream_t)stream, d, gamma, beta, w, bias, workspace);
   SRL_LAUNCH_CHECK();
@@ -869,8 +857,7 @@ static int conv2d_obs_bwd_run(void* stream, const srl_conv_desc* d, const void* 
   if (first && hipMemsetAsync(R, 0, sizeof(float) * 2 * P * d->Cout, st) != hipSuccess) return -EIO;
   const ObsIndex ix{d->Cin, d->H, d->W, d->KH, d->KW, d->stride, OW, channels_last ? 1 : 0};
   // the Atari geometry with a measured bound of |dz|: blocks of 2 x 4 positions per workgroup, frames and dz by LDS-DMA (obs_h2.h)
-  static const bool blocks_on = [] { const char* e = getenv("SRL_OBS_BWD_H2BLOCK"); return !(e && e[0] == '0'); }();
-  if (dz_absmax && blocks_on && obs_bf16_ok(d, is_u8, channels_last, obs) && d->Cin == 64 && d->KH == 2 && d->KW == 2 &&
+  if (dz_absmax && obs_bf16_ok(d, is_u8, channels_last, obs) && d->Cin == 64 && d->KH == 2 && d->KW == 2 &&
       d->stride == 1 && d->Cout == 32 && OH % srlobs::kBlkH == 0 && OW % srlobs::kBlkW == 0 && d->n * (long)P * 128 < 0xffffffffL) {
     srlobs::BwdH2Args a{};
     const long n_pad = srl_ceil_div(d->n, (long)srlobs::kTile) * srlobs::kTile;

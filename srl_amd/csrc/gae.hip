@@ -491,17 +491,6 @@ extern "C" int srl_gae_scan(void* stream, const float* reward, const float* valu
                      aligned_to(truncated, 4) && aligned_to(on_reset, 4) && (!imp_ratio || aligned_to(imp_ratio, 16));
   if (quads) {
     const bool vt = imp_ratio != nullptr;
-    static const char* tune = getenv("SRL_GAE_TILE");  // "<cq><l>" tuning knob for scripts/gae_sweep.py
-    if (tune && tune[0] && tune[1]) {
-      const int lmax = tune[1] - '0';
-      if (tune[0] == '4') return launch_gae_reg_l<4>(st, p, vt, lmax);
-      if (tune[0] == '8') return launch_gae_reg_l<8>(st, p, vt, lmax);
-      if (tune[0] == '3') return launch_gae_reg_l<32>(st, p, vt, lmax);
-      if (tune[0] == '6') return launch_gae_reg_l<64>(st, p, vt, lmax);
-      if (tune[0] == 'a') return launch_gae_reg_l<128>(st, p, vt, lmax);
-      if (tune[0] == 'b') return launch_gae_reg_l<256>(st, p, vt, lmax);
-      return launch_gae_reg_l<16>(st, p, vt, lmax);
-    }
     // Row width per workgroup grows with the batch (measured on MI355X, scripts/gae_sweep.py): wide
     // rows stream best (1 KiB = 8 whole cache lines per wave load) but need B/256 >> 256 workgroups.
     if (ncols < 2048) return launch_gae_reg_l<4>(st, p, vt);

@@ -420,11 +420,6 @@ __global__ __launch_bounds__(WM * WN * 64, min_waves3(BM, BN, KB, NP)) void gemm
   gemm_epilogue<TM, TN, EPI, MK>(g, acc, m0, n0, wm, wn, l31, h, by, kz, interior);
 }
 
-inline bool tile_groups() {  // SRL_TILE_GROUP=0: row-major tile numbering everywhere (A/B switch)
-  static const bool on = [] { const char* e = getenv("SRL_TILE_GROUP"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int AMODE, int BMODE, int KB = 32, int NP = 3>
 inline int launch3(hipStream_t st, GemmArgs a, int batch, int nsplit) {
   if (!(a.vec_a && a.vec_b)) return -EINVAL;
@@ -435,7 +430,7 @@ inline int launch3(hipStream_t st, GemmArgs a, int batch, int nsplit) {
   if (nblk * nsplit > 0x7fffffffL) return -EINVAL;
   a.tiles_all = (unsigned)nblk;
   a.grp_n = (unsigned)a.tiles_n;
-  if (AMODE == SRC_PLAIN && BMODE == SRC_PLAIN && a.nbatch == 1 && tile_groups()) {
+  if (AMODE == SRC_PLAIN && BMODE == SRC_PLAIN && a.nbatch == 1) {
     // A dense product whose XCD share of tiles (one contiguous run of the numbering) exceeds the XCD's workgroup slots is
     // worked off row after row; in row-major numbering every new tile row streams ALL of B again, from HBM once B is
     // larger than the L2 (FC data gradient, 16384 x 3136 x 512: B = 6.4 MB re-read by each of the 16 tile rows of every

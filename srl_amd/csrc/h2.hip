@@ -236,8 +236,7 @@ extern "C" int srl_h2_gemm(void* stream, const srl_h2_gemm_desc* d) {
   a.mask_out = d->mask_out; a.mask_in = d->mask_in; a.mask_in_h2 = d->mask_in_h2order;
   // a wide output over a short reduction (the Linear's data gradient: 3136 channels, K = 512): 256 channels per workgroup, both
   // k-halves in every wavefront -- a third less staged per multiply-add, on a two-stage ring (240 -> 220 us per 16 384 rows)
-  static const bool wide_on = [] { const char* e = getenv("SRL_H2GEMM_WIDE"); return !(e && e[0] == '0'); }();
-  const bool wide = wide_on && d->NC >= 1024 && d->K <= 1024;
+  const bool wide = d->NC >= 1024 && d->K <= 1024;
   // round 6: the wide product as a PERSISTENT kernel (h2gemmp.h: one workgroup per CU walks its tiles, the ring never drains, a
   // tile's stores are not waited for) -- same operands, same piece products in the same order: bit-identical output.  207 -> 191 us
   // per 16 384 rows of the Linear's data gradient on one box, launched alone.

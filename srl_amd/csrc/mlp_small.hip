@@ -303,11 +303,8 @@ int fill(Args& a, const srl_mlp_layer* layers, int n) {
 #include "mlp_sig.h"
 #include "mlp_sigh.h"
 
-// rows from which the matrix-core chain (mlp_mfma.h) takes over from the FMA chain; SRL_MLP_MFMA=0 switches it off (A/B)
-static long mfma_min_rows() {
-  static const long v = [] { const char* e = getenv("SRL_MLP_MFMA"); return e ? (e[0] == '0' ? (1L << 62) : atol(e)) : 512L; }();
-  return v;
-}
+// rows from which the matrix-core chain (mlp_mfma.h) takes over from the FMA chain
+constexpr long kMfmaMinRows = 512;
 
 extern "C" int64_t srl_mlp_bwd_max_rows(const srl_mlp_layer* layers, int n) {
   Args a{};
@@ -315,9 +312,9 @@ extern "C" int64_t srl_mlp_bwd_max_rows(const srl_mlp_layer* layers, int n) {
   {
     MArgs m{};
     m.a = a;
-    if (mfma_min_rows() < (1L << 40) && mm_plan(m)) return 1L << 30;  // the matrix-core chain: any row count
+    if (mm_plan(m)) return 1L << 30;  // the matrix-core chain: any row count
   }
-  // Measured against the layer-by-layer kernels on 2 x 64 nets (scripts/mlp_rows_sweep.py): 0.30 against 0.64 ms per update at
+  // Measured against the layer-by-layer kernels on 2 x 64 nets: 0.30 against 0.64 ms per update at
   // 256 rows, 0.54 against 0.89 at 16 384, 1.30 against 1.03 at 65 536 -- 256 threads per CU are too few once the row count
   // fills the chip (scripts/mlp_probe.py: a 64 x 64 Linear's backward 105 us, a LayerNorm's 84 us at 65 536 rows).  Without
   // the LDS sums every 16-row block adds its partial sums with float atomics: a few thousand rows only.
@@ -334,7 +331,7 @@ extern "C" int64_t srl_mlp_tape_floats(const srl_mlp_layer* layers, int n) {
 static bool mfma_takes(const Args& a, long rows, MArgs& m) {
   m = MArgs{};
   m.a = a;
-  return rows >= mfma_min_rows() && mm_plan(m);
+  return rows >= kMfmaMinRows && mm_plan(m);
 }
 
 extern "C" int64_t srl_mlp_tape_floats_at(const srl_mlp_layer* layers, int n, int64_t rows) {

@@ -298,7 +298,7 @@ extern "C" int srl_ppo_loss_fwd_bwd(void* stream, const float* new_lp, const flo
              done, truncated, d_new_lp, d_value, d_entropy, loss_terms};
   // (every block ends in SRL_LT_COUNT float64 atomics on ONE line, which the L2 serialises at ~10 ns each: 2048 blocks
   // spent 0.2 ms there at 524 288 rows; the grid is capped where the loop's loads still cover the latency)
-  static const long cap = getenv("SRL_LOSS_GRID") ? atol(getenv("SRL_LOSS_GRID")) : 512;
+  const long cap = 512;
   const unsigned grid = (unsigned)(srl_ceil_div(n, 256) < cap ? srl_ceil_div(n, 256) : cap);
   hipLaunchKernelGGL(ppo_loss_kernel, dim3(grid), dim3(256), 0, st, a);
   SRL_LAUNCH_CHECK();

@@ -353,7 +353,7 @@ def piece_products(kind: str = "x3") -> float:
     if kind == "obs":
         return 1.0 if os.environ.get("SRL_OBS_BF16", "")[:1] == "0" else 3.0
     if kind == "obs2":  # csrc/obs_h2.h: byte operand x two f16 weight pieces
-        return 2.0 if os.environ.get("SRL_OBS_H2BLOCK", "")[:1] != "0" else 3.0
+        return 2.0
     if os.environ.get("SRL_MFMA", "")[:1] == "f":
         return 1.0
     return 3.0 if kind == "2h" else 6.0
@@ -1178,7 +1178,7 @@ def conv2d_obs_bwd(d: ConvDesc, obs_ptr, is_u8, mean_ptr, rstd_ptr, gamma_ptr, b
     chunks of one update then share one finalisation; ``srl_hip.h``).  ``dz_absmax_ptr``: device float >= max |dz| (selects the
     block kernel of ``csrc/obs_h2.h`` on the Atari geometry)."""
     # with a bound of |dz| the Atari geometry runs obs_h2.h's weight gradient: bytes x two f16 pieces of dz'
-    with _scope("conv_obs_bwd", _conv_flops(d), "obs2" if dz_absmax_ptr and os.environ.get("SRL_OBS_BWD_H2BLOCK", "")[:1] != "0" else "obs"):
+    with _scope("conv_obs_bwd", _conv_flops(d), "obs2" if dz_absmax_ptr else "obs"):
         _check(
             lib().srl_conv2d_obs_bwd(_stream(), ctypes.byref(d), obs_ptr, int(is_u8), int(channels_last), mean_ptr,
                                      rstd_ptr, gamma_ptr, beta_ptr, w_ptr, dz_ptr, dw_ptr, db_ptr, dgamma_ptr, dbeta_ptr,

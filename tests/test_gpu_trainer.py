@@ -282,7 +282,7 @@ def test_wide_dense_layers_on_presplit_operands_vs_oracle(kind, monkeypatch):
     `vector`: LayerNorm -> Linear 1056 -> 256 (no ReLU mask below it); `image`: the reference's default convolution stack
     (cnn.py:96-98: 4 / 8 / 4 channels -- no sign words from the convolutions, `srl_relu_mask` makes them) in front of
     Linear 1024 -> 512 + the rest of the halving tower.  One step against the CPU oracle (returns, loss terms, gradient norm, every
-    tensor's gradient to 2 % of its rms), and both this step's and the layer-by-layer kernels' (SRL_H2_DENSE=0) gradients against the
+    tensor's gradient to 2 % of its rms), and both this step's and the layer-by-layer kernels' (HipNet.H2_DENSE = False) gradients against the
     float64 oracle: every tensor's error at most 3 x the layer-by-layer kernels' (+ 2e-6 of the tensor's largest element)."""
     from srl_amd import hip
     from srl_amd.algorithm.hipnet import HipNet

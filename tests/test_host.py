@@ -300,3 +300,29 @@ def test_host_side_queries_of_the_fused_kernels():
     assert hip.ln_heads_supported(512, (6, 1)) and hip.ln_heads_supported(256, (8,)) and hip.ln_heads_supported(1024, (2, 1))
     assert not hip.ln_heads_supported(512, (8, 1))     # nine outputs
     assert not hip.ln_heads_supported(384, (6, 1)) and not hip.ln_heads_supported(512, ())
+
+
+# every switch `srl_amd/` reads from the environment; a new one is added here and to INTEGRATION.md's table on purpose
+ENV_SWITCHES = frozenset({
+    "SRL_HIP_LIB", "SRL_COMM", "SRL_PIPELINES", "SRL_WGRAD_STREAM", "SRL_EXPLICIT_CONV", "SRL_H2", "SRL_FC_TRAIN_SPLITK",
+    "SRL_OBS_BWD_DEFER", "SRL_RNN_SEQ", "SRL_MFMA", "SRL_F16X2", "SRL_OBS_BF16", "SRL_SMALL_GEMM", "SRL_MLP_F16", "SRL_MLP_SIG",
+    "SRL_H2GEMM_P", "SRL_CONV_RUN_IMAGES"})
+
+
+def test_environment_switches_match_the_documented_table():
+    """The `SRL_*` names inside `os.environ...(` / `getenv(` calls of srl_amd/**/*.py and srl_amd/csrc/* are exactly the rows of
+    INTEGRATION.md's switch table, and no more of them than the set above (source text only, nothing is launched)."""
+    import glob
+    paths = glob.glob(os.path.join(ROOT, "srl_amd", "**", "*.py"), recursive=True)
+    paths += [p for p in glob.glob(os.path.join(ROOT, "srl_amd", "csrc", "*")) if p.endswith((".hip", ".h"))]
+    read = set()
+    for path in paths:
+        read |= set(re.findall(r"(?:os\.environ[.\w]*[\[(]|getenv\()\s*[\"'](SRL_[A-Z0-9_]+)[\"']", open(path).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("Switches read from the environment"):]
+    rows = [ln for ln in table[:table.index("\n\n", table.index("|---|"))].splitlines() if ln.startswith("| `")]
+    documented = set()
+    for ln in rows:
+        documented |= set(re.findall(r"SRL_[A-Z0-9_]+", ln.split("|")[1]))
+    assert read == documented, (sorted(read - documented), sorted(documented - read))
+    assert read <= ENV_SWITCHES and len(read) <= len(ENV_SWITCHES), sorted(read - ENV_SWITCHES)
