@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SRL_HIP_ABI_VERSION 19
+#define SRL_HIP_ABI_VERSION 20
 
 int srl_abi_version(void);
 const char* srl_last_error(void);
@@ -837,6 +837,44 @@ typedef struct srl_entity_attn {
 int srl_entity_attn_supported(const srl_entity_attn* d);
 int srl_entity_attn_fwd(void* stream, const srl_entity_attn* d, int64_t rows, float* out, int64_t ldo);
 int srl_entity_attn_bwd(void* stream, const srl_entity_attn* d, int64_t rows, const float* d_out, int64_t lddo);
+
+/* ------------------------------------------------------------------------------------------------
+ * Language encoder of the DMLab agent (csrc/instr_lstm.hip; ABI 20): DMLabActorCritic.forward's instruction branch
+ * (legacy/algorithm/ppo/game_policies/dmlab_policy.py:144-158) as ONE launch per direction, float32 throughout.  Per row of
+ * tokens [L]: a token is the value truncated towards zero (float32 tokens) or the value itself (int32); len = max(1, number of
+ * non-zero tokens) -- a count, not the position of the last one; the sequence is the FIRST len tokens, zeros inside that prefix
+ * included; x_t = emb[token_t] (row 0 is read like any other row); an LSTM in torch's layout (gate order i|f|g|o, both biases
+ * added) runs over it from a zero state; the feature is h at step len - 1.
+ * DIFFERENCE: a token outside [0, V) (or not a number) is treated as padding (0) where nn.Embedding raises: it is not counted,
+ * embeds to row 0 inside a prefix and receives no gradient.  Nothing is read or written out of bounds.
+ * srl_instr_lstm_fwd: writes columns [0, H) of out [rows, ldo]; the other columns are left as they are (ldo >= H), so `out`
+ *   may point into a wider concatenation buffer.
+ * srl_instr_lstm_bwd: given d_out [rows, lddo] (H columns read) ADDS the gradients of the five parameters into g_* (float
+ *   atomics: d W_ih, d W_hh and both d b once per workgroup, summed over all its rows in registers; d emb per (row, step) of a
+ *   non-zero token).  g_emb's row 0 is never written.  No tape: it walks forward again from the tokens, which must still hold
+ *   what the forward call saw, under the same parameters, and keeps h_t, c_t of its own walk in `workspace` (at least
+ *   srl_instr_lstm_bwd_workspace(d, rows) bytes for the full grid; a smaller one, down to one workgroup's 2 L H 32 floats, only
+ *   narrows the grid).  No input gradient is formed (the inputs are token ids).
+ * The descriptor is passed by value to the kernel: no allocation, no copy, no synchronisation -- capturable.
+ * srl_instr_lstm_supported: 1 when 1 <= V <= 65536, 1 <= Ed <= 32, H is 32 or 64 and 1 <= L <= 64 (W_ih | W_hh, staged once per
+ * workgroup, and one 32-row tile's operands then fit the 160 KiB of LDS), else 0.  The pointers are not looked at. */
+typedef struct srl_instr_lstm {
+  int32_t V, Ed, H, L;      /* vocabulary, embedding width, LSTM units, tokens per row */
+  int32_t tok_i32, pad_;    /* tokens are int32 (else float32) */
+  const float* emb;         /* [V, Ed] */
+  const float* w_ih;        /* [4H, Ed] */
+  const float* w_hh;        /* [4H, H] */
+  const float* b_ih;        /* [4H] */
+  const float* b_hh;        /* [4H] */
+  float *g_emb, *g_w_ih, *g_w_hh, *g_b_ih, *g_b_hh; /* their gradients, accumulated into (srl_instr_lstm_bwd only) */
+  const void* tok;          /* [rows, ld_tok], L columns read */
+  int64_t ld_tok;
+} srl_instr_lstm;
+int srl_instr_lstm_supported(const srl_instr_lstm* d);
+int64_t srl_instr_lstm_bwd_workspace(const srl_instr_lstm* d, int64_t rows);
+int srl_instr_lstm_fwd(void* stream, const srl_instr_lstm* d, int64_t rows, float* out, int64_t ldo);
+int srl_instr_lstm_bwd(void* stream, const srl_instr_lstm* d, int64_t rows, const float* d_out, int64_t lddo, void* workspace,
+                       int64_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Native step driver (launch-bound configurations).  The device part of MultiAgentPPO.step (mappo.py:219-328) is

@@ -13,6 +13,7 @@ first Conv2d      ``srl_obs_ln_stats`` + ``srl_im2col_obs_ln``  GEMMs + ``srl_ob
                   (uint8 -> LN -> patches) + ``srl_gemm``
 later Conv2d      ``srl_im2col_nhwc`` + ``srl_gemm``             GEMMs + ``srl_col2im_nhwc`` (act' fused)
 entity attention  ``srl_entity_attn_fwd`` (several leaves)   ``srl_entity_attn_bwd`` (walks forward again, no tape)
+instruction LSTM  ``srl_instr_lstm_fwd`` (token ids)         ``srl_instr_lstm_bwd`` (walks forward again, no tape)
 ================  =========================================  ==========================================
 
 The gradient handed to a layer's ``backward`` is always w.r.t. its *pre-activation* output: whoever
@@ -653,13 +654,13 @@ class HipNet:
         ctx = self._rnn
         if ctx is None:
             raise hip.HipError("recurrent backbone: forward() needs the `rnn` context (chunking, states, on_reset)")
-        T, B, C, H = ctx.T, ctx.B, ctx.C, G.hidden
+        T, B, C, H, I0 = ctx.T, ctx.B, ctx.C, G.hidden, G.input_dim   # (layer 0 reads I0 columns, the others H)
         n, K = T * B, T // C
         N = K * B
-        assert x.rows == n and x.cols == H and x.ld == H and T % C == 0
+        assert x.rows == n and x.cols == I0 and x.ld == I0 and T % C == 0
         if K > 1 and not self._cm:
-            xc = self._buf(f"{tag}{G.prefix}.xc", n, H)
-            hip.chunk_rows(x.ptr, xc.ptr, T, B, C, H)
+            xc = self._buf(f"{tag}{G.prefix}.xc", n, I0)
+            hip.chunk_rows(x.ptr, xc.ptr, T, B, C, I0)
         else:  # (one chunk, or the whole pass runs on chunk-major rows already)
             xc = x
         h0 = ctx.h0[tag]
@@ -677,7 +678,7 @@ class HipNet:
             cin = self._buf(f"{tag}{G.prefix}.cin{l}", n, H)
             cnew = self._buf(f"{tag}{G.prefix}.cnew{l}", n, H)
             y = self._buf(f"{tag}{G.prefix}.y{l}", n, H)
-            hip.gemm(n, 4 * H, H, inp.ptr, inp.ld, 0, w_ih, H, 0, pre.ptr, 4 * H, bias=b_ih)  # every step at once
+            hip.gemm(n, 4 * H, inp.cols, inp.ptr, inp.ld, 0, w_ih, inp.cols, 0, pre.ptr, 4 * H, bias=b_ih)  # every step at once
             # the stored state is cat(h, c) per row (autoreset_rnn.py:31-39); both halves are reset together
             hip.copy2d(h0[l].data_ptr(), SW, y.ptr, H, N, H)
             hip.gru_mask_state(y.ptr, rptr(0), N, H, hin.ptr)
@@ -704,7 +705,7 @@ class HipNet:
             gh = self._buf(f"{tag}{G.prefix}.gh{l}", n, 3 * H)
             hin = self._buf(f"{tag}{G.prefix}.hin{l}", n, H)
             y = self._buf(f"{tag}{G.prefix}.y{l}", n, H)
-            hip.gemm(n, 3 * H, H, inp.ptr, inp.ld, 0, w_ih, H, 0, gi.ptr, 3 * H, bias=b_ih)  # every step at once
+            hip.gemm(n, 3 * H, inp.cols, inp.ptr, inp.ld, 0, w_ih, inp.cols, 0, gi.ptr, 3 * H, bias=b_ih)  # every step at once
             hip.gru_mask_state(h0[l].data_ptr(), rptr(0), N, H, hin.ptr)
             seq = hip.rnn_seq_supported("gru", H)
             if seq:
@@ -758,13 +759,13 @@ class HipNet:
             # bias gradients (column sums of d pre) come out of the weight-gradient kernels
             self._wgrad(4 * H, H, n, pre, hin.ptr, H, self._g(f"{G.prefix}.weight_hh_l{l}"),
                         self._g(f"{G.prefix}.bias_hh_l{l}"))
-            self._wgrad(4 * H, H, n, pre, inp.ptr, inp.ld, self._g(f"{G.prefix}.weight_ih_l{l}"),
+            self._wgrad(4 * H, inp.cols, n, pre, inp.ptr, inp.ld, self._g(f"{G.prefix}.weight_ih_l{l}"),
                         self._g(f"{G.prefix}.bias_ih_l{l}"))
             if l == 0 and not need_dx:
                 return None
-            dx = self._buf(f"{tag}{G.prefix}.dx{l}", n, H)
+            dx = self._buf(f"{tag}{G.prefix}.dx{l}", n, inp.cols)
             act = in_act if l == 0 else 0
-            hip.gemm(n, H, 4 * H, pre.ptr, 4 * H, 0, w_ih, H, 1, dx.ptr, H, dact_src=inp.ptr if act else None,
+            hip.gemm(n, inp.cols, 4 * H, pre.ptr, 4 * H, 0, w_ih, inp.cols, 1, dx.ptr, inp.cols, dact_src=inp.ptr if act else None,
                      ld_dact=inp.ld, dact=act)
             dout = dx
         for l in range(G.layers - 1 if G.kind == "gru" else -1, -1, -1):
@@ -787,23 +788,23 @@ class HipNet:
             # parameter gradients over all steps at once (gi / gh now hold d gi / d gh)
             self._wgrad(3 * H, H, n, gh, hin.ptr, H, self._g(f"{G.prefix}.weight_hh_l{l}"),
                         self._g(f"{G.prefix}.bias_hh_l{l}"))
-            self._wgrad(3 * H, H, n, gi, inp.ptr, inp.ld, self._g(f"{G.prefix}.weight_ih_l{l}"),
+            self._wgrad(3 * H, inp.cols, n, gi, inp.ptr, inp.ld, self._g(f"{G.prefix}.weight_ih_l{l}"),
                         self._g(f"{G.prefix}.bias_ih_l{l}"))
             if l == 0 and not need_dx:
                 return None
-            dx = self._buf(f"{tag}{G.prefix}.dx{l}", n, H)
+            dx = self._buf(f"{tag}{G.prefix}.dx{l}", n, inp.cols)
             act = in_act if l == 0 else 0  # layer 0 reads the (activated) output of the dense stack
-            hip.gemm(n, H, 3 * H, gi.ptr, 3 * H, 0, w_ih, H, 1, dx.ptr, H, dact_src=inp.ptr if act else None, ld_dact=inp.ld,
-                     dact=act)
+            hip.gemm(n, inp.cols, 3 * H, gi.ptr, 3 * H, 0, w_ih, inp.cols, 1, dx.ptr, inp.cols, dact_src=inp.ptr if act else None,
+                     ld_dact=inp.ld, dact=act)
             dout = dx
         if K > 1 and not self._cm:
-            dxt = self._buf(f"{tag}{G.prefix}.dxt", n, H)
-            hip.chunk_rows(dout.ptr, dxt.ptr, T, B, C, H, inverse=True)
+            dxt = self._buf(f"{tag}{G.prefix}.dxt", n, dout.cols)
+            hip.chunk_rows(dout.ptr, dxt.ptr, T, B, C, dout.cols, inverse=True)
             return dxt
         return dout
 
     # ------------------------------------------------------------------ encoders
-    def _encoder_fwd(self, enc: ns.EncoderSpec, obs: torch.Tensor, n: int, tag: str, tape: list, lnheads=None) -> Buf:
+    def _encoder_fwd(self, enc: ns.EncoderSpec, obs: torch.Tensor, n: int, tag: str, tape: list, lnheads=None, into=None) -> Buf:
         """obs: device tensor [n, *shape] (float32 vectors; uint8 or float32 images).  ``lnheads``: ``(heads, outs)`` when the
         encoder's closing LayerNorm and the heads behind it are to run as one launch (`_lnheads_ok`): the record `lnheads` then
         closes the tape and the heads' outputs are in ``outs``."""
@@ -850,7 +851,29 @@ class HipNet:
                                  x_out=cur.ptr if (slabs and not self._infer) else None, ldxo=cur.ld)
                 tape.append(("lnheads", L, cur, (mean, rstd, heads), cur_act))
                 return None
-            if isinstance(L, ns.EntityAttnSpec):
+            if isinstance(L, ns.InstrLstmSpec):
+                tok = self._instr_tokens(L, obs, n, enc.key)
+                # `into`: (pointer, pitch) of this encoder's columns in the trunk's concatenation buffer -- no copy follows
+                y = Buf(into[0], into[1], n, L.units) if into is not None else self._buf(f"{tag}{L.prefix}.y", n, L.units)
+                hip.instr_lstm_fwd(self._instr_desc(L), tok.data_ptr(), L.length, tok.dtype == torch.int32, n, y.ptr, y.ld)
+                # no tape: the backward launch walks forward again from the tokens (kept alive by the record)
+                tape.append(("instr", L, tok, None, 0))
+                cur, cur_act, cur_range = y, 0, None
+            elif isinstance(L, ns.ObsScaleSpec):
+                c, h, w = L.shape
+                if not isinstance(obs, torch.Tensor) or obs.dim() < 2 or obs.shape[0] != n or math.prod(obs.shape[1:]) != c * h * w:
+                    raise hip.HipError(f"image observation `{enc.key}`: sample rows of shape {tuple(getattr(obs, 'shape', ()))[1:]} "
+                                       f"for a network built for {tuple(L.shape)} ({n} rows expected)")
+                is_u8 = obs.dtype == torch.uint8
+                if not is_u8 and obs.dtype != torch.float32:
+                    raise hip.HipError(f"image observation `{enc.key}` must be uint8 or float32, got {obs.dtype}")
+                zero, scale, one = self._scale_consts(L, n)
+                y = self._buf(f"{tag}{L.prefix}.y", n * h * w, c)
+                # (x - 0) * scale * 1 + 0, channels-last: the observation LayerNorm's writer with constant tables.  Not on the tape:
+                # nothing is learnt here and the frames take no gradient
+                hip.obs_ln_nhwc(obs.data_ptr(), is_u8, zero, scale, one, zero, n, c, h, w, y.ptr)
+                cur, cur_act, cur_range = y, 0, None
+            elif isinstance(L, ns.EntityAttnSpec):
                 leaves = self._eattn_leaves(L, obs, n, enc.key)
                 y = self._buf(f"{tag}{L.prefix}.eattn.y", n, 2 * L.dim)
                 hip.entity_attn_fwd(self._eattn_desc(L), *leaves, n, y.ptr, y.ld)
@@ -1068,6 +1091,14 @@ class HipNet:
                 self._release(L.prefixes)
                 g, g_range = None, None
                 continue
+            elif kind == "instr":   # one launch: every parameter of the block is final behind it
+                d = self._instr_desc(L)
+                nbytes = hip.instr_lstm_bwd_workspace(d, g.rows)
+                wsp = self.ws.get(f"{tag}{L.prefix}.states", nbytes // 4)
+                hip.instr_lstm_bwd(d, x.data_ptr(), L.length, x.dtype == torch.int32, g.rows, g.ptr, g.ld, wsp.data_ptr(), nbytes)
+                self._release(L.prefixes)
+                g, g_range = None, None
+                continue
             elif kind == "fusedenc":
                 self._fused_bwd(L, g.ptr, g.ld)   # (releases its layers' buckets itself)
                 g, g_range = None, None
@@ -1156,6 +1187,10 @@ class HipNet:
                     elif self._conv_small(L, desc):
                         wws = self.ws.get("conv_small_wgrad", hip.conv2d_small_wgrad_workspace(desc)).data_ptr()
                         self._on_side(lambda d=desc, xp=x.ptr, gp=g.ptr: hip.conv2d_small_wgrad(d, xp, gp, wws, gw, gb))
+                        if not need_dx:   # the chain's first record on a written-out observation (ObsScaleSpec): nobody takes dx
+                            g = None
+                            self._notify_ready(kind, L, saved)
+                            continue
                         h, w = L.in_hw
                         dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
                         hip.conv2d_small_dgrad(desc, g.ptr, wp, x.ptr if in_act else None, in_act, dx.ptr)
@@ -1169,6 +1204,10 @@ class HipNet:
                         self._on_side(lambda d=desc, xp=x.ptr, gp=g.ptr, xr=x_range if two else None,
                                       gr=g_range if two and x_range is not None else None: hip.conv2d_nhwc_wgrad(
                                           d, xp, gp, gw, wgrad_ws, gb, x_absmax=xr, dz_absmax=gr))
+                        if not need_dx:   # (as above)
+                            g = None
+                            self._notify_ready(kind, L, saved)
+                            continue
                         wt = self.ws.get(f"{L.prefix}.wt", hip.conv2d_dgrad_weight_elems(desc))
                         if not self._derived_fresh(f"{L.prefix}.wt", wt.data_ptr()):  # once per update, not per chunk
                             hip.conv2d_dgrad_repack(desc, wp, wt.data_ptr())
@@ -1193,6 +1232,10 @@ class HipNet:
                     continue
                 self._wgrad(L.cout, kdim, m, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
                 hip.colsum(g.ptr, g.ld, m, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
+                if not L.first and not need_dx:   # (as above; the patch-matrix path)
+                    g = None
+                    self._notify_ready(kind, L, saved)
+                    continue
                 # dP = dZ W, written over the patch matrix (its last reader was the weight gradient above)
                 hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)
                 if L.first:
@@ -1249,6 +1292,8 @@ class HipNet:
             return L.dim
         if kind == "eattn":
             return 2 * L.dim
+        if kind == "instr":
+            return L.units
         if kind == "linear":
             return L.out_features
         if kind == "gru":
@@ -1288,10 +1333,17 @@ class HipNet:
         for pi, (r0, r1) in enumerate(pieces):
             ptag = tag if len(pieces) == 1 else f"{tag}piece{pi}:"
             tapes, outs = [], []
+            col = 0
             for enc in encoders:
                 tape = []
-                outs.append(self._encoder_fwd(enc, self._enc_obs(enc, obs, r0, r1), r1 - r0, ptag, tape, lnheads=lnheads))
+                into = None
+                if len(enc.layers) == 1 and isinstance(enc.layers[0], ns.InstrLstmSpec) and (len(encoders) > 1 or len(pieces) > 1):
+                    if feat is None:
+                        feat = self._buf(f"{tag}concat", n, width)
+                    into = (feat.ptr + 4 * (r0 * width + col), width)   # the block writes its columns of the concatenation itself
+                outs.append(self._encoder_fwd(enc, self._enc_obs(enc, obs, r0, r1), r1 - r0, ptag, tape, lnheads=lnheads, into=into))
                 tapes.append(tape)
+                col += enc.out_dim
             enc_tapes.append(tapes)
             if lnheads is not None and tapes[0] and tapes[0][-1][0] == "lnheads":   # (one piece, one encoder: _lnheads_ok)
                 return None, 0, (enc_tapes, [], widths, pieces, "lnheads")
@@ -1302,7 +1354,8 @@ class HipNet:
                 feat = self._buf(f"{tag}concat", n, width)
             col = 0
             for o in outs:
-                hip.copy2d(o.ptr, o.ld, feat.ptr + 4 * (r0 * width + col), width, r1 - r0, o.cols)
+                if o.ptr != feat.ptr + 4 * (r0 * width + col):
+                    hip.copy2d(o.ptr, o.ld, feat.ptr + 4 * (r0 * width + col), width, r1 - r0, o.cols)
                 col += o.cols
         bb_tape = []
         cur, cur_act = feat, 0
@@ -1374,6 +1427,40 @@ class HipNet:
             return t.data_ptr(), int(math.prod(shape))
         return (leaf(A.self_key, (A.self_dim,), torch.float32), [leaf(k, (c, f), torch.float32) for k, c, f in A.keys],
                 leaf(A.mask_key, (A.entities,), torch.uint8))
+
+    # ------------------------------------------------------------------ instruction LSTM (the DMLab agent's language encoder)
+    def _instr_tokens(self, A: ns.InstrLstmSpec, obs, n: int, key: str) -> torch.Tensor:
+        """The token leaf as the kernel reads it: contiguous float32 or int32 [n, L] (other integer widths are widened here)."""
+        t = obs
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n, A.length):
+            raise hip.HipError(f"observation `{key}`: expected token ids of shape {(n, A.length)}, got "
+                               f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.dtype not in (torch.float32, torch.int32):
+            t = t.to(torch.float32 if t.dtype.is_floating_point else torch.int32)
+        return t.contiguous()
+
+    def _instr_desc(self, A: ns.InstrLstmSpec):
+        """The block's descriptor over this executor's parameters and gradients (a host struct, passed to the kernel by value)."""
+        key = ("instr", A.prefix, self.flat.data_ptr(), self.grad.data_ptr())
+        d = self._mlp_cache.get(key)
+        if d is None:
+            names = A.param_names()
+            d = self._mlp_cache[key] = hip.instr_lstm_desc(A.vocab, A.embed, A.units, A.length, {f: self._p(p) for f, p in names.items()},
+                                                           {f: self._g(p) for f, p in names.items()})
+        return d
+
+    def _scale_consts(self, L: ns.ObsScaleSpec, n: int):
+        """Device constants of an ObsScaleSpec: pointers of >= max(n, C H W) zeros, of n times the scale, of C H W ones."""
+        m = max(n, int(math.prod(L.shape)))
+        ent = self._mlp_cache.get(("scale", L.prefix))
+        if ent is None or ent[0].numel() < m:
+            dev = self.flat.device
+            if ent is not None:   # a launch in flight may still read the outgrown tables: they are kept
+                self._mlp_cache.setdefault(("scale.outgrown", L.prefix), []).append(ent)
+            ent = self._mlp_cache[("scale", L.prefix)] = (torch.zeros(m, dtype=torch.float32, device=dev),
+                                                          torch.full((m,), L.scale, dtype=torch.float32, device=dev),
+                                                          torch.ones(m, dtype=torch.float32, device=dev))
+        return tuple(t.data_ptr() for t in ent)
 
     def _eattn_desc(self, A: ns.EntityAttnSpec):
         """The block's descriptor over this executor's parameters and gradients (a host struct, passed to the kernel by value)."""

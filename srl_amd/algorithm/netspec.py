@@ -105,6 +105,11 @@ class GruSpec:
     hidden: int
     layers: int
     kind: str = "gru"  # "lstm": gates i|f|g|o ([4H, H] weights); the stored state is cat(h, c) (autoreset_rnn.py:31-39)
+    in_dim: int = 0  # width of layer 0's input when it differs from ``hidden`` (weight_ih_l0 is [gates * H, in_dim]); 0: hidden
+
+    @property
+    def input_dim(self):
+        return self.in_dim or self.hidden
 
     @property
     def gates(self):
@@ -218,6 +223,43 @@ class EntityAttnSpec:
 
 
 @dataclasses.dataclass
+class ObsScaleSpec:
+    """An image observation (C, H, W) times a constant, written out once as a float32 channels-last image: the DMLab agent's
+    ``obs / 255`` (dmlab_policy.py:141), which has no observation LayerNorm.  No parameters."""
+    prefix: str
+    shape: Tuple[int, int, int]
+    scale: float
+
+
+@dataclasses.dataclass
+class InstrLstmSpec:
+    """The DMLab agent's language encoder (dmlab_policy.py:49-57,144-158): ``nn.Embedding(vocab, embed, padding_idx=0)`` and a
+    length-masked ``nn.LSTM(embed, units)`` over each row's first max(1, #non-zero) tokens, one launch per direction
+    (csrc/instr_lstm.hip).  Parameters ``<emb_prefix>.weight`` and ``<lstm_prefix>.{weight_ih,weight_hh,bias_ih,bias_hh}_l0``.
+    Output ``[n, units]``."""
+    emb_prefix: str  # "word_embedding"
+    lstm_prefix: str  # "instructions_lstm"
+    vocab: int
+    embed: int
+    units: int
+    length: int  # tokens per row
+
+    @property
+    def prefix(self):
+        return self.lstm_prefix
+
+    def param_names(self) -> Dict[str, str]:
+        """field of srl_instr_lstm -> parameter name"""
+        r = self.lstm_prefix
+        return {"emb": f"{self.emb_prefix}.weight", "w_ih": f"{r}.weight_ih_l0", "w_hh": f"{r}.weight_hh_l0",
+                "b_ih": f"{r}.bias_ih_l0", "b_hh": f"{r}.bias_hh_l0"}
+
+    @property
+    def prefixes(self):
+        return [self.emb_prefix, self.lstm_prefix]
+
+
+@dataclasses.dataclass
 class EncoderSpec:
     key: str
     shape: Union[int, Tuple[int, ...]]
@@ -317,6 +359,15 @@ class _Builder:
             v = torch.empty(shape)
             torch.nn.init.uniform_(v, -bound, bound)
         self._add(name, shape, v)
+
+    def embedding(self, name, rows, cols):
+        """nn.Embedding(rows, cols, padding_idx=0).reset_parameters: N(0, 1), then row 0 zeroed."""
+        v = None
+        if self.init:
+            v = torch.empty((rows, cols))
+            torch.nn.init.normal_(v)
+            v[0].zero_()
+        self._add(name, (rows, cols), v)
 
     def orthogonal(self, name, gain):
         if self.init:
@@ -742,4 +793,103 @@ def build_smac_netspec(obs_dim: Union[int, Dict], state_dim: Union[int, Dict], a
     spec = NetSpec([EncoderSpec("local_obs", obs_shape, a_layers, H)], a_bb, [EncoderSpec("state", state_shape, c_layers, H)], c_bb,
                    LinearSpec("policy_head", H, act_dim, 0), LinearSpec("value_head", H, 1, 0), [act_dim], H, 1, False,
                    b.params, off, True, num_rnn_layers, None, 2 * H if num_rnn_layers else 0, pkeys)
+    return spec, (b.values if b.init else None)
+
+
+DMLAB_VOCABULARY_SIZE = 1000  # dmlab_policy.py:21
+
+
+def build_dmlab_netspec(obs_shapes: Dict, action_dim: int, hidden_dim: int = 512, num_dense_layers: int = 0, rnn_type: str = "lstm",
+                        num_rnn_layers: int = 1, popart: bool = True, activation: str = "relu", layernorm: bool = False,
+                        seed: Optional[int] = None, embedding_size: int = 20, instrunctions_lstm_units: int = 64,
+                        instruction_lstm_layers: int = 1, **_unused):
+    """``DMLabActorCritic`` (``game_policies/dmlab_policy.py:24-168``), IMPALA's DMLab-30 agent, as a shared-trunk ``NetSpec`` with
+    two encoders: the pixels (``obs / 255 -> Conv2d(C, 16, 8, 4) -> act -> Conv2d(16, 32, 4, 2) -> act -> Flatten -> Linear``, no
+    LayerNorm anywhere) and the instruction (``InstrLstmSpec``).  Their concatenation, ``hidden_dim + units`` wide, feeds
+    ``AutoResetRNN(hidden_dim + units -> hidden_dim // 2)`` with no ``rnn_norm`` behind it; the heads read its output (or the
+    concatenation, with ``num_rnn_layers=0``).  Parameters are registered in the reference's ``state_dict`` order and initialised by
+    replaying its constructor.  ``num_dense_layers > 0`` (two MLP branches behind a shared core) is not built."""
+    if rnn_type not in ("gru", "lstm", "gtrxl"):
+        raise ValueError(f"Unknown rnn_type {rnn_type} for ActorCriticPolicy.")  # dmlab_policy.py:198
+    if rnn_type == "gtrxl":
+        raise NotImplementedError("rnn_type `gtrxl`: only the GRU and LSTM cells of AutoResetRNN are on the HIP path")
+    if activation not in ACTS:
+        raise NotImplementedError(f"Activation function {activation} not implemented.")
+    if num_dense_layers > 0:
+        raise NotImplementedError("dmlab: num_dense_layers > 0 (separate actor / critic MLPs behind the shared core) is not "
+                                  "implemented on the HIP path")
+    if instruction_lstm_layers != 1:
+        raise NotImplementedError("dmlab: the fused language encoder runs one LSTM layer")
+    act = ACTS[activation]
+    shapes = {k: tuple(int(x) for x in v) for k, v in dict(obs_shapes).items()}
+    if "obs" not in shapes or "INSTR" not in shapes or len(shapes["obs"]) != 3 or len(shapes["INSTR"]) != 1:
+        raise NotImplementedError(f"dmlab: obs_shapes needs `obs` (C, H, W) and `INSTR` (L,), got {shapes}")
+    c, h, w = shapes["obs"]
+    L, Ed, U, H = shapes["INSTR"][0], int(embedding_size), int(instrunctions_lstm_units), int(hidden_dim)
+    threads = torch.get_num_threads()
+    if seed is not None:
+        torch.set_num_threads(1)
+    try:
+        b = _Builder(seed)
+        b.embedding("word_embedding.weight", DMLAB_VOCABULARY_SIZE, Ed)
+        bound = 1.0 / math.sqrt(U)  # nn.LSTM.reset_parameters
+        b.uniform("instructions_lstm.weight_ih_l0", (4 * U, Ed), bound)
+        b.uniform("instructions_lstm.weight_hh_l0", (4 * U, U), bound)
+        b.uniform("instructions_lstm.bias_ih_l0", (4 * U,), bound)
+        b.uniform("instructions_lstm.bias_hh_l0", (4 * U,), bound)
+        px = [ObsScaleSpec("pixel_encoder.scale", (c, h, w), 1.0 / 255.0)]
+        convs = []
+        for idx, (cout, k, stride) in ((0, (16, 8, 4)), (2, (32, 4, 2))):
+            oh, ow = _conv_out(h, k, stride), _conv_out(w, k, stride)
+            if oh <= 0 or ow <= 0:
+                raise ValueError(f"CNN Dimension error, got {(oh, ow)} after convolution")
+            b.conv(f"pixel_encoder.{idx}", c, cout, k, "conv_nhwc")
+            convs.append(f"pixel_encoder.{idx}")
+            px.append(ConvSpec(f"pixel_encoder.{idx}", c, cout, k, stride, (h, w), (oh, ow), act, first=False))
+            c, h, w = cout, oh, ow
+        b.linear("pixel_encoder.5", c * h * w, H, "fc_from_chw", (c, h, w))
+        px.append(LinearSpec("pixel_encoder.5", c * h * w, H, 0))
+        for name in convs:  # dmlab_policy.py:85-90: orthogonal (gain 1) on the 4-D weights, every bias of the encoder zero
+            b.orthogonal(f"{name}.weight", 1.0)
+            b.zero(f"{name}.bias")
+        b.zero("pixel_encoder.5.bias")
+        feat = H + U
+        backbone = []
+        if num_rnn_layers:
+            R = H // 2
+            rp = "rnn._AutoResetRNN__net"
+            bound = 1.0 / math.sqrt(R)
+            ng = 4 if rnn_type == "lstm" else 3
+            for l in range(num_rnn_layers):  # torch's default reset stays (no orthogonal pass in this policy)
+                b.uniform(f"{rp}.weight_ih_l{l}", (ng * R, feat if l == 0 else R), bound)
+                b.uniform(f"{rp}.weight_hh_l{l}", (ng * R, R), bound)
+                b.uniform(f"{rp}.bias_ih_l{l}", (ng * R,), bound)
+                b.uniform(f"{rp}.bias_hh_l{l}", (ng * R,), bound)
+            backbone.append(GruSpec(rp, R, num_rnn_layers, rnn_type, in_dim=feat))
+            feat = R
+        b.linear("actor_head", feat, action_dim)
+        b.orthogonal("actor_head.weight", 0.01)
+        b.zero("actor_head.bias")
+        if popart:
+            b.linear("critic_head", feat, 1, ref_names=(POPART_W, POPART_B))
+            if b.init:
+                b.values[POPART_KEYS[0]] = torch.zeros(1, dtype=torch.float64)
+                b.values[POPART_KEYS[1]] = torch.zeros(1, dtype=torch.float64)
+                b.values[POPART_KEYS[2]] = torch.zeros(1, dtype=torch.float64)
+        else:
+            b.linear("critic_head", feat, 1)
+    finally:
+        torch.set_num_threads(threads)
+    off = 0
+    for info in b.params.values():
+        info.offset = off
+        off += (info.numel + 3) // 4 * 4
+    encs = [EncoderSpec("obs", shapes["obs"], px, H),
+            EncoderSpec("INSTR", shapes["INSTR"], [InstrLstmSpec("word_embedding", "instructions_lstm", DMLAB_VOCABULARY_SIZE, Ed, U, L)], U)]
+    width = 0
+    if num_rnn_layers:
+        width = H if rnn_type == "lstm" else H // 2
+    # ``hidden_dim`` of a NetSpec is the width the heads read
+    spec = NetSpec(encs, backbone, None, None, LinearSpec("actor_head", feat, action_dim, 0), LinearSpec("critic_head", feat, 1, 0),
+                   [action_dim], feat, 1, True, b.params, off, bool(popart), num_rnn_layers, None, width)
     return spec, (b.values if b.init else None)
