@@ -65,6 +65,10 @@ class OracleActorCritic:
         self.cnn_layers = cnn_layers or {}
         self.use_maxpool = use_maxpool or {}
         self.num_rnn_layers, self.rnn_type = num_rnn_layers, rnn_type
+        # PopArtValueHead's `burn_in_updates` and `__update_cnt` (popart.py:16,28-29): the head is rescaled by every update
+        # once the count exceeds the burn-in
+        self.burn_in_updates = _ignored.get("burn_in_updates", float("inf"))
+        self.popart_updates = 0
         assert rnn_type in ("gru", "lstm") or num_rnn_layers == 0, "oracle restates the GRU and LSTM variants"
         self.params: "OrderedDict[str, torch.Tensor]" = OrderedDict()
 
@@ -218,7 +222,8 @@ class OracleActorCritic:
         return logits, value, new_state
 
     # ------------------------------------------------------------------ PopArt (popart.py:8-59, modules/utils.py:70-151)
-    POPART_BETA, POPART_EPS = 0.99999, 1e-5  # PopArtValueHead defaults; burn_in_updates = inf: never rescales
+    POPART_BETA, POPART_EPS = 0.99999, 1e-5  # PopArtValueHead defaults; `burn_in_updates` (default inf: never rescales) is
+    # an instance setting, see __init__
 
     VALUE_HEAD = "critic_head"
 
@@ -244,6 +249,11 @@ class OracleActorCritic:
 
     @torch.no_grad()
     def update_popart(self, x, mask):
+        """popart.py:44-51 in float64: the statistics move, the count goes up, and past the burn-in the head's weight and bias
+        are rewritten so that its de-normalised output is what it was.  The rewrite goes through ``.data`` as in the
+        reference (:50-51): a forward pass that already ran keeps its values, while its backward pass, which reads the same
+        storage, propagates through the rescaled weight."""
+        old_mean, old_std = self.popart_mean_std()
         x, mask = x.double(), mask.double()
         x = x * mask
         factor = mask.sum()
@@ -253,6 +263,13 @@ class OracleActorCritic:
         self._rms("mean")[:] = b * self._rms("mean") + bm * (1.0 - b)
         self._rms("mean_sq")[:] = b * self._rms("mean_sq") + bsq * (1.0 - b)
         self._rms("debiasing_term")[:] = b * self._rms("debiasing_term") + 1.0 - b
+        new_mean, new_std = self.popart_mean_std()
+        self.popart_updates += 1
+        if self.popart_updates > self.burn_in_updates:
+            head = f"{self.VALUE_HEAD}._PopArtValueHead__"
+            w, bias = self.params[head + "weight"], self.params[head + "bias"]
+            w.data[:] = (w.double() * (old_std / new_std).unsqueeze(-1)).to(w.dtype)
+            bias.data[:] = ((old_std * bias.double() + old_mean - new_mean) / new_std).to(bias.dtype)
 
     def _heads(self, logits):
         out, start = [], 0
@@ -345,7 +362,8 @@ class OracleSMACNet(OracleActorCritic):
     def __init__(self, obs_dim, state_dim, act_dim, hidden_dim, chunk_len, num_rnn_layers=1, agent_shared=True, **_ignored):
         super().__init__(obs_dim={"local_obs": obs_dim}, action_dim=act_dim, hidden_dim=hidden_dim,
                          state_dim={"state": state_dim}, chunk_len=chunk_len, num_rnn_layers=num_rnn_layers,
-                         rnn_type="lstm", popart=True, shared_backbone=False, dtype=_ignored.get("dtype", torch.float32))
+                         rnn_type="lstm", popart=True, shared_backbone=False, dtype=_ignored.get("dtype", torch.float32),
+                         burn_in_updates=_ignored.get("burn_in_updates", float("inf")))
         self.agent_shared = agent_shared
 
     def _rnn_key(self, prefix, n, layer):

@@ -238,14 +238,30 @@ class ActorCriticPolicy(policy_api.Policy):
             dist.all_reduce(stats)
         self.update_popart_from_stats(stats)
 
-    def update_popart_from_stats(self, stats, count=True):
-        """stats float64 [value_dim, 3] = (sum mask, sum x*mask, sum (x*mask)^2), already all-reduced."""
+    def popart_rescales(self, ahead=1):
+        """Whether the ``ahead``-th PopArt update from now rewrites the head: the reference counts every update and
+        rescales once the count exceeds the burn-in (popart.py:47-49; inf: never)."""
+        return self._popart_updates + ahead > self._popart_burn_in
+
+    def popart_head_params(self):
+        """The PopArt head's weight and bias as views of the flat parameter buffer (what a rescale rewrites)."""
+        head = self.spec.critic_head
+        infos = [self.spec.params[f"{head.prefix}.weight"], self.spec.params[f"{head.prefix}.bias"]]
+        return [self._net.flat[i.offset:i.offset + i.numel] for i in infos]
+
+    def update_popart_from_stats(self, stats, count=True, ahead=0):
+        """stats float64 [value_dim, 3] = (sum mask, sum x*mask, sum (x*mask)^2), already all-reduced.  ``count=False``: the
+        caller counts the updates of a whole trainer step afterwards, and this is update number ``ahead + 1`` of that step.
+        Returns whether the head was rescaled."""
         if count:
             self._popart_updates += 1
-        rescale = self._popart_updates + (0 if count else 1) > self._popart_burn_in  # popart.py:49 (inf: never)
+        rescale = self.popart_rescales(0 if count else ahead + 1)
         net, head = self._net, self.spec.critic_head
         hip.popart_update(stats, net.popart_state, self.spec.value_dim, self._popart_beta, ns.POPART_EPS,
                           net._p(f"{head.prefix}.weight"), net._p(f"{head.prefix}.bias"), head.in_features, rescale)
+        if rescale:  # part of ``flat`` was rewritten: what executors derived from the parameters is stale
+            net.params_changed()
+        return rescale
 
     def parameters(self):
         return [self._net.flat]

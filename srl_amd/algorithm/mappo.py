@@ -570,7 +570,10 @@ class MultiAgentPPO(PytorchTrainer):
         captured, later ones replay."""
         dev = self.policy.device
         keys = sorted(L)
-        key = (have_adv,) + tuple((k, tuple(L[k].shape), str(L[k].dtype).replace("torch.", "")) for k in keys)
+        # which epochs rescale the PopArt head is decided on the host and baked into the captured launches: a graph serves the
+        # steps with ITS pattern only (all-False until the burn-in is crossed, mixed in the step that crosses it, all-True after)
+        pattern = tuple(self.policy.popart_rescales(e + 1) for e in range(self.ppo_epochs)) if self.popart else ()
+        key = (have_adv, pattern) + tuple((k, tuple(L[k].shape), str(L[k].dtype).replace("torch.", "")) for k in keys)
         if key not in self._graphs:
             self._graphs[key] = None
             return self._device_part({k: to_device_leaf(v, dev, "as-is") for k, v in L.items()}, have_adv, None)
@@ -691,6 +694,7 @@ class MultiAgentPPO(PytorchTrainer):
             flat = lambda t: t[lo:hi].reshape(n_valid, *t.shape[2:])
             # ---- PopArt: statistics of the value targets, then the loss sees normalised targets (:263-264, :173-176) ----
             loss_ret, pstats_local = ret_d, None
+            head_old = head_new = None
             if self.popart:
                 pstats_local = block[epoch, stride - 3 * Nc:].view(Nc, 3)  # zeroed by srl_masked_stats_cols itself
                 hip.masked_stats_cols(flat(ret_d), on_reset[1 + lo:1 + hi], pstats_local, Nc, mask_invert=True)
@@ -706,7 +710,22 @@ class MultiAgentPPO(PytorchTrainer):
                         stats_work.wait()
                         stats_work = None
                     dist.all_reduce(pstats)
-                self.policy.update_popart_from_stats(pstats, count=False)
+                # The reference analyses the sample BEFORE this update (mappo.py:244 against :264) and rescales the head's storage
+                # in place (popart.py:50-51): the loss sees the values of the head as it was, while the backward pass, which reads
+                # the same storage, propagates through the rescaled weight, and the optimiser steps from the rescaled head.  Here
+                # the update comes first, so in an epoch that rescales the old head is kept, put back for every chunk's forward
+                # pass and replaced by the rescaled one before that chunk's backward pass.
+                head = self.policy.popart_head_params()
+                if self.policy.popart_rescales(epoch + 1):  # the reference counts per update, i.e. per epoch (popart.py:47-49)
+                    head_old = [net.ws.get(f"mappo.head_old{i}", p.numel())[:p.numel()] for i, p in enumerate(head)]
+                    head_new = [net.ws.get(f"mappo.head_new{i}", p.numel())[:p.numel()] for i, p in enumerate(head)]
+                    for dst, p in zip(head_old, head):
+                        dst.copy_(p)
+                self.policy.update_popart_from_stats(pstats, count=False, ahead=epoch)
+                if head_old is not None:
+                    for keep, back, p in zip(head_new, head_old, head):
+                        keep.copy_(p)
+                        p.copy_(back)
                 loss_ret = torch.empty_like(ret_d)
                 hip.popart_map(ret_d, net.popart_state, Nc, loss_ret, True, ns.POPART_EPS)
             loss_oldv = self.policy.normalize_value(old_value) if self.normalize_old_value else old_value  # :151-152
@@ -728,7 +747,9 @@ class MultiAgentPPO(PytorchTrainer):
             # Two pipelines: even chunks on the compute stream with the policy's executor, odd chunks on a second stream
             # with its twin (same parameters, own workspace / tape / gradient buffer).  Not for recurrent nets (one chunk),
             # not inside a graph capture.
-            two = (self.pipelines >= 2 and nchunks >= 2 and rnn is None and dscal is None and not net.force_explicit_conv)
+            # (nor in an epoch that rescales the PopArt head: the pipelines share the parameters the chunks swap)
+            two = (self.pipelines >= 2 and nchunks >= 2 and rnn is None and dscal is None and not net.force_explicit_conv
+                   and head_old is None)
             nets, streams = [net], [torch.cuda.current_stream()]
             if two:
                 npipe = min(self.pipelines, nchunks)
@@ -768,7 +789,15 @@ class MultiAgentPPO(PytorchTrainer):
                 with torch.cuda.stream(streams[e]):
                     c_obs = {k: v[r0:r1] for k, v in f_obs.items()}
                     c_avail = None if f_avail is None else f_avail[r0:r1]
+                    if head_old is not None and ci > 0:
+                        for p, back in zip(head, head_old):
+                            p.copy_(back)
+                        net.params_changed()
                     logits, value = cnet.forward(c_obs, n, keep_tape=True, rnn=rnn)
+                    if head_old is not None:
+                        for p, new in zip(head, head_new):
+                            p.copy_(new)
+                        net.params_changed()
                     logp = cnet.ws.get("new_logp", n)[:n]
                     ent = cnet.ws.get("entropy", n)[:n]
                     self.policy.dist_fwd(logits, f_action[r0:r1], c_avail, logp, ent, net=cnet)

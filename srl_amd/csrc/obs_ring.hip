@@ -31,7 +31,10 @@ __global__ __launch_bounds__(256) void gather_rows4_kernel(const uint32_t* __res
 // ring sequence numbers -> storage slots
 __global__ __launch_bounds__(256) void ring_slots_kernel(const int64_t* __restrict__ refs, long n, long capacity, long base,
                                                          int32_t* __restrict__ slots) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) slots[i] = (int32_t)((refs[i] - base) % capacity);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = (refs[i] - base) % capacity;  // C's remainder takes the dividend's sign; a slot is the non-negative one,
+    slots[i] = (int32_t)(r < 0 ? r + capacity : r);  // as the host path's numpy `%` gives for a stamp below the base
+  }
 }
 
 // A frame-stacked observation (atari_wrappers.py:211-242: the k latest frames, the newest last; reset() fills the stack with k

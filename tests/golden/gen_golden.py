@@ -56,6 +56,9 @@ from oracle.trainer import OracleMappo
 from srl_amd.algorithm.netspec import build_netspec
 from srl_amd.runtime import synthetic
 
+sys.path.insert(0, os.path.dirname(HERE))
+from popart_rescale_cases import CASES as RESCALE_CASES, SMACU, scale_rewards
+
 TORCH_VERSION = torch.__version__
 
 
@@ -273,7 +276,27 @@ def check_init(policy_args, ref_sd):
     return spec
 
 
-def run_steps(tag, policy_args, trainer_args, sample_kw, n_steps, store_state="full", out=None, analyze_check=True):
+PARAM_TOL = 2e-5  # what the GPU parity tests allow on a parameter after a step (tests/test_gpu_trainer.py, test_gpu_smac.py)
+
+
+def set_popart_burn_in(head, burn_in, update_cnt):
+    """PopArtValueHead's private burn-in and update count (popart.py:28-29), set from outside: the reference's files stay
+    untouched.  Only `smac_rnn(unbiased_popart=True)` reaches a finite burn-in through a constructor."""
+    assert hasattr(head, "_PopArtValueHead__burn_in_updates") and hasattr(head, "_PopArtValueHead__update_cnt")
+    setattr(head, "_PopArtValueHead__burn_in_updates", burn_in)
+    setattr(head, "_PopArtValueHead__update_cnt", update_cnt)
+
+
+def assert_rescale_matters(tag, oracle_net, plain_net):
+    """The fixture proves something only if a run that never rescales ends far away from it."""
+    key = f"{oracle_net.VALUE_HEAD}._PopArtValueHead__weight"
+    gap = float((oracle_net.params[key] - plain_net.params[key]).detach().abs().max())
+    assert gap > 100 * PARAM_TOL, (tag, "head weight with and without rescale differ by only", gap)
+    print(f"{tag}: head weight with / without rescale differ by {gap:.3g} (> {100 * PARAM_TOL:g})")
+
+
+def run_steps(tag, policy_args, trainer_args, sample_kw, n_steps, store_state="full", out=None, analyze_check=True,
+              popart_burn_in=None, popart_update_cnt=0, reward_scale=None):
     out = {} if out is None else out
     trainer = make_ref_trainer(policy_args, trainer_args)
     net = trainer.policy.net
@@ -283,9 +306,18 @@ def run_steps(tag, policy_args, trainer_args, sample_kw, n_steps, store_state="f
     oracle_net = OracleActorCritic(**policy_args)
     oracle_net.load_state_dict(sd0)
     oracle = OracleMappo(oracle_net, **trainer_args)
+    plain = None
+    if popart_burn_in is not None:  # the head is rescaled once the count exceeds the burn-in (popart.py:47-51)
+        set_popart_burn_in(net.critic_head, popart_burn_in, popart_update_cnt)
+        oracle_net.burn_in_updates, oracle_net.popart_updates = popart_burn_in, popart_update_cnt
+        plain_net = OracleActorCritic(**policy_args)  # the same run without any rescale
+        plain_net.load_state_dict(sd0)
+        plain = OracleMappo(plain_net, **trainer_args)
     stat_keys = None
     for step in range(n_steps):
         arrays = synthetic.make_sample_arrays(seed=100 + step, **sample_kw)
+        if reward_scale is not None:
+            arrays = scale_rewards(arrays, reward_scale[step])
         sample = ref_sample({k: v.copy() for k, v in arrays.items()})
         if step == 0 and analyze_check:
             # G6: analysis outputs on the initial weights
@@ -308,6 +340,8 @@ def run_steps(tag, policy_args, trainer_args, sample_kw, n_steps, store_state="f
             out[f"{tag}_analyze_entropy"] = ar.entropy.numpy()
         res = trainer.step(sample)
         o_stats, o_out = oracle.step(arrays)
+        if plain is not None:
+            plain.step(arrays)
         stats = {k: float(v) for k, v in res.stats.items()}
         for k in ("policy_loss", "value_loss", "entropy", "grad_norm", "clip_ratio", "importance_weight", "advantage",
                   "value_targets", "done", "truncated"):
@@ -332,6 +366,8 @@ def run_steps(tag, policy_args, trainer_args, sample_kw, n_steps, store_state="f
                     out[f"{tag}_step{step}_param:{k}"] = v
                 else:  # large tensors: a strided subsample (stride recorded in the key)
                     out[f"{tag}_step{step}_param_s97:{k}"] = v.reshape(-1)[::97].copy()
+    if plain is not None:
+        assert_rescale_matters(tag, oracle_net, plain.net)
     out[f"{tag}_stat_names"] = np.array(stat_keys)
     out[f"{tag}_version"] = np.array(trainer.policy.version)
     if store_state == "full":
@@ -591,49 +627,63 @@ def gen_rnn():
 SMAC_3M = ((30,), (48,), 9, 3)  # (obs, state, #actions, #agents): the standard 3m feature sizes
 
 
-def gen_smac():
-    """``smac_rnn`` (game_policies/smac_rnn.py), shared agents: full trainer steps on ``[Tb, B, agents, ...]`` samples,
-    and a rollout.
+SMAC_H, SMAC_A, SMAC_CL = 32, 3, 5
+SMAC_POLICY = dict(map_name="3m", hidden_dim=SMAC_H, chunk_len=SMAC_CL, seed=31, shared=True)
+SMAC_TRAINER = dict(popart=True, ppo_epochs=2, optimizer_config=dict(lr=5e-4, eps=1e-5), max_grad_norm=10.0,
+                    value_loss="huber", value_loss_config=dict(delta=10.0), clip_value=True, dual_clip=False)
 
-    Harness-side shims (the reference file itself is untouched): (1) ``legacy.environment.smac.smac_env`` needs a
-    StarCraft installation; a stand-in module supplies ``SMACAction`` and ``get_smac_shapes`` returning the 3m sizes.
-    (2) The module is imported explicitly (``legacy/algorithm/ppo/game_policies/__init__.py`` has the import commented
-    out).  (3) For the rollout only: ``SMACNet`` gets ``AutoResetRNN``'s default LSTM, whose state is 2H wide, while
-    ``SMACPolicy``'s default state is H wide, so the stock rollout raises inside ``nn.LSTM``; the private default is
-    replaced by a 2H-wide zero array before calling it.  The training side needs no such patch."""
+
+def smac_shims():
+    """Harness-side shims for ``smac_rnn`` (the reference file itself is untouched): (1) ``legacy.environment.smac.smac_env``
+    needs a StarCraft installation; a stand-in module supplies ``SMACAction`` and ``get_smac_shapes`` returning the 3m
+    sizes.  (2) The module is imported explicitly (``legacy/algorithm/ppo/game_policies/__init__.py`` has the import
+    commented out)."""
     import types
-    from oracle.net import OracleSMACNet
-    from srl_amd.algorithm.netspec import build_smac_netspec
-    fake = types.ModuleType("legacy.environment.smac.smac_env")
+    if "legacy.environment.smac.smac_env" not in sys.modules:
+        fake = types.ModuleType("legacy.environment.smac.smac_env")
 
-    class SMACAction(DiscreteAction):
-        pass
+        class SMACAction(DiscreteAction):
+            pass
 
-    fake.SMACAction = SMACAction
-    fake.get_smac_shapes = lambda map_name, **kw: SMAC_3M
-    sys.modules["legacy.environment.smac.smac_env"] = fake
+        fake.SMACAction = SMACAction
+        fake.get_smac_shapes = lambda map_name, **kw: SMAC_3M
+        sys.modules["legacy.environment.smac.smac_env"] = fake
     import legacy.algorithm.ppo.game_policies.smac_rnn  # noqa: F401  (registers "smac_rnn")
 
-    out = {}
-    H, A, CL = 32, 3, 5
-    policy_args = dict(map_name="3m", hidden_dim=H, chunk_len=CL, seed=31, shared=True)
-    trainer_args = dict(popart=True, ppo_epochs=2, optimizer_config=dict(lr=5e-4, eps=1e-5), max_grad_norm=10.0,
-                        value_loss="huber", value_loss_config=dict(delta=10.0), clip_value=True, dual_clip=False)
+
+def run_smac_steps(tag, policy_args, trainer_args, n_steps, out, popart_update_cnt=None, reward_scale=None):
+    """``n_steps`` trainer steps of ``smac_rnn`` (shared agents) on ``[Tb, B, agents, ...]`` samples, reference against
+    oracle, recorded under ``tag``; returns the reference trainer.  ``popart_update_cnt``: preset of the head's update
+    count (with ``unbiased_popart=True`` the burn-in is 1000 updates)."""
+    from oracle.net import OracleSMACNet
+    from srl_amd.algorithm.netspec import build_smac_netspec
+    smac_shims()
+    H, A, CL = policy_args["hidden_dim"], SMAC_A, policy_args["chunk_len"]
     trainer = make_ref_trainer(policy_args, trainer_args, "smac_rnn")
     net = trainer.policy.net
     sd0 = sd_to_np(net.state_dict())
-    spec, vals = build_smac_netspec(30, 48, 9, H, seed=31)
+    spec, vals = build_smac_netspec(30, 48, 9, H, seed=policy_args["seed"])
     assert list(vals.keys()) == list(sd0.keys()), "state_dict key order differs"
     for k in vals:
         assert torch.equal(vals[k], net.state_dict()[k]), f"init mismatch at {k}"
     oracle_net = OracleSMACNet(30, 48, 9, H, CL)
     oracle_net.load_state_dict(sd0)
     oracle = OracleMappo(oracle_net, **trainer_args)
+    plain = None
+    if popart_update_cnt is not None:
+        burn_in = getattr(net.value_head, "_PopArtValueHead__burn_in_updates")
+        assert burn_in == SMACU["burn_in"], "unbiased_popart=True is the public route to a finite burn-in (smac_rnn.py:132)"
+        set_popart_burn_in(net.value_head, burn_in, popart_update_cnt)
+        oracle_net.burn_in_updates, oracle_net.popart_updates = burn_in, popart_update_cnt
+        plain_net = OracleSMACNet(30, 48, 9, H, CL)
+        plain_net.load_state_dict(sd0)
+        plain = OracleMappo(plain_net, **trainer_args)
     sample_kw = dict(T=20, B=4, agents=A, obs_spec={"local_obs": ((30,), "f32"), "state": ((48,), "f32")}, action_dim=9,
                      p_done=0.08, policy_state={"actor_hx": (1, 2 * H), "critic_hx": (1, 2 * H)})
-    n_steps = 2
     for step in range(n_steps):
         arrays = synthetic.make_multiagent_arrays(seed=300 + step, **sample_kw)
+        if reward_scale is not None:
+            arrays = scale_rewards(arrays, reward_scale[step])
         sample = ref_sample({k: v.copy() for k, v in arrays.items()})
         if step == 0:
             ts = recursive_apply(sample, lambda x: torch.from_numpy(x).float())
@@ -651,32 +701,49 @@ def gen_smac():
             assert torch.allclose(lp[fin], ar.new_action_log_probs[fin], rtol=1e-5, atol=1e-6)
             assert torch.allclose(v, ar.state_values, rtol=1e-5, atol=1e-6)
             assert torch.allclose(ent, ar.entropy, rtol=1e-5, atol=1e-6)
-            out["smac_analyze_new_lp"] = ar.new_action_log_probs.numpy()
-            out["smac_analyze_value"] = ar.state_values.numpy()
-            out["smac_analyze_entropy"] = ar.entropy.numpy()
+            out[f"{tag}_analyze_new_lp"] = ar.new_action_log_probs.numpy()
+            out[f"{tag}_analyze_value"] = ar.state_values.numpy()
+            out[f"{tag}_analyze_entropy"] = ar.entropy.numpy()
         res = trainer.step(sample)
         o_stats, o_out = oracle.step(arrays)
+        if plain is not None:
+            plain.step(arrays)
         stats = {k: float(v) for k, v in res.stats.items()}
         for k in ("policy_loss", "value_loss", "entropy", "grad_norm", "clip_ratio", "importance_weight", "advantage",
                   "value_targets", "done", "truncated", "denorm_value"):
-            assert abs(o_stats[k] - stats[k]) <= 2e-5 * max(1.0, abs(stats[k])), ("smac", step, k, o_stats[k], stats[k])
+            assert abs(o_stats[k] - stats[k]) <= 2e-5 * max(1.0, abs(stats[k])), (tag, step, k, o_stats[k], stats[k])
         assert np.array_equal(o_out["adv"], sample.analyzed_result.adv)
         assert np.array_equal(o_out["ret"], sample.analyzed_result.ret)
         stat_keys = sorted(stats)
-        out[f"smac_step{step}_stats"] = np.array([stats[k] for k in stat_keys], dtype=np.float64)
+        out[f"{tag}_step{step}_stats"] = np.array([stats[k] for k in stat_keys], dtype=np.float64)
         if step == 0:
-            out["smac_step0_adv"], out["smac_step0_ret"] = sample.analyzed_result.adv, sample.analyzed_result.ret
+            out[f"{tag}_step0_adv"], out[f"{tag}_step0_ret"] = sample.analyzed_result.adv, sample.analyzed_result.ret
         sd = sd_to_np(net.state_dict())
         osd = oracle_net.state_dict()
         for k in sd:
-            assert np.allclose(osd[k].numpy(), sd[k], rtol=1e-4, atol=1e-6), ("smac", step, k)
+            assert np.allclose(osd[k].numpy(), sd[k], rtol=1e-4, atol=1e-6), (tag, step, k)
         for k, v in sd.items():
-            out[f"smac_step{step}_param:{k}"] = v
-    out["smac_stat_names"] = np.array(stat_keys)
-    out["smac_version"] = np.array(trainer.policy.version)
-    out["smac_init_sha"] = np.array(state_sha(OrderedDictNP(sd0)))
+            out[f"{tag}_step{step}_param:{k}"] = v
+    if plain is not None:
+        assert_rescale_matters(tag, oracle_net, plain.net)
+    out[f"{tag}_stat_names"] = np.array(stat_keys)
+    out[f"{tag}_version"] = np.array(trainer.policy.version)
+    out[f"{tag}_init_sha"] = np.array(state_sha(OrderedDictNP(sd0)))
     for k, v in sd0.items():
-        out[f"smac_init_param:{k}"] = v
+        out[f"{tag}_init_param:{k}"] = v
+    return trainer
+
+
+def gen_smac():
+    """``smac_rnn`` (game_policies/smac_rnn.py), shared agents: full trainer steps on ``[Tb, B, agents, ...]`` samples,
+    and a rollout.
+
+    Harness-side shims: (1), (2) see ``smac_shims``.  (3) For the rollout only: ``SMACNet`` gets ``AutoResetRNN``'s default
+    LSTM, whose state is 2H wide, while ``SMACPolicy``'s default state is H wide, so the stock rollout raises inside ``nn.LSTM``; the private default is
+    replaced by a 2H-wide zero array before calling it.  The training side needs no such patch."""
+    out = {}
+    H, A = SMAC_H, SMAC_A
+    trainer = run_smac_steps("smac", SMAC_POLICY, SMAC_TRAINER, 2, out)
 
     # deterministic rollout of [N, agents, ...] requests on the trained weights, carried states on some rows reset
     policy = trainer.policy
@@ -702,6 +769,23 @@ def gen_smac():
     out["smac_roll_value"] = res.analyzed_result.value
     out["smac_roll_new_actor_hx"], out["smac_roll_new_critic_hx"] = res.policy_state.actor_hx, res.policy_state.critic_hx
     save("steps_smac.npz", **out)
+
+
+def gen_popart_rescale():
+    """PopArt's head rescale (popart.py:47-51): once the head's update count exceeds its burn-in, every update rewrites the
+    head's weight and bias so that its de-normalised output is preserved.  The burn-in and the count are private attributes
+    of the reference's head module, set here from outside (`set_popart_burn_in`).  This early the debiasing term is tiny
+    and mean / std move by large factors between updates, so a missing or misplaced rescale leaves the parameters far
+    outside any tolerance (`assert_rescale_matters`)."""
+    out = {}
+    for tag, c in RESCALE_CASES.items():  # par0: every update rescales; parx: the onset falls between the epochs of step 1
+        run_steps(tag, c["policy"], c["trainer"], c["sample"], c["n_steps"], out=out, popart_burn_in=c["burn_in"],
+                  popart_update_cnt=c["updates"], reward_scale=c["reward_scale"])
+    # smac_rnn(unbiased_popart=True): burn-in 1000, count preset to 998 -> updates 999, 1000 plain, 1001, 1002 rescale
+    assert SMACU["policy"] == dict(SMAC_POLICY, unbiased_popart=True) and SMACU["trainer"] == SMAC_TRAINER
+    run_smac_steps("smacu", SMACU["policy"], SMACU["trainer"], SMACU["n_steps"], out,
+                   popart_update_cnt=SMACU["updates"], reward_scale=SMACU["reward_scale"])
+    save("steps_popart_rescale.npz", **out)
 
 
 def gen_presets():

@@ -26,43 +26,92 @@ def close(a, b, rtol, scale=1.0):
 
 
 def test_smac_steps_match_reference_golden(golden):
-    g = golden("steps_smac.npz")
-    trainer = trainer_api.make(config.Trainer("mappo", args=TRAINER), config.Policy("smac_rnn", args=POLICY))
+    check_smac_steps(golden("steps_smac.npz"), "smac", POLICY)
+
+
+def test_smacu_steps_match_reference_golden(golden):
+    """`unbiased_popart=True`: the head is rescaled by every PopArt update past the 1000th (popart.py:47-51).  The count starts at
+    998 -- set from outside, as gen_golden.py gen_popart_rescale set it on the reference's head -- so the burn-in is crossed
+    between the two steps: updates 999 and 1000 leave the head alone, 1001 and 1002 rescale it."""
+    from popart_rescale_cases import SMACU
+    assert SMACU["trainer"] == TRAINER and SMACU["sample"] == SAMPLE and SMACU["policy"] == dict(POLICY, unbiased_popart=True)
+    check_smac_steps(golden("steps_popart_rescale.npz"), "smacu", SMACU["policy"], SMACU)
+
+
+def test_smacu_onset_between_epochs_vs_oracle():
+    """The fixture's count (998, two epochs a step) puts the onset of the rescale between two steps.  From 997 it falls between the
+    epochs of the second step -- update 1000 leaves the head alone, update 1001 rescales it -- which only a trainer that counts per
+    epoch gets right.  Against the CPU oracle, which the fixture pins to the reference (tests/test_oracle.py); bounds of
+    test_football_smm_preset_downsized_vs_oracle."""
+    from oracle.net import OracleSMACNet
+    from oracle.trainer import OracleMappo
+    from popart_rescale_cases import SMACU, scale_rewards
+    trainer = trainer_api.make(config.Trainer("mappo", args=TRAINER), config.Policy("smac_rnn", args=SMACU["policy"]))
+    trainer.policy._popart_updates = 997
+    onet = OracleSMACNet(30, 48, 9, H, CL, burn_in_updates=1000)
+    onet.load_state_dict({k: v.numpy() for k, v in trainer.policy.get_checkpoint()["state_dict"].items()})
+    onet.popart_updates = 997
+    oracle = OracleMappo(onet, **TRAINER)
+    head = "value_head._PopArtValueHead__weight"
+    for step in range(2):
+        arrays = scale_rewards(synthetic.make_multiagent_arrays(seed=300 + step, **SAMPLE), SMACU["reward_scale"][step])
+        w_before = onet.params[head].detach().clone()
+        res = trainer.step(synthetic.to_sample_batch(arrays))
+        ostats, _ = oracle.step(arrays)
+        for k in ("policy_loss", "value_loss", "entropy", "grad_norm", "denorm_value"):
+            assert abs(res.stats[k] - ostats[k]) <= 2e-5 * max(abs(ostats[k]), 1e-2), (step, k, res.stats[k], ostats[k])
+        sd, osd = trainer.policy.get_checkpoint()["state_dict"], onet.state_dict()
+        for k in sd:
+            d = np.abs(sd[k].numpy() - osd[k].numpy())
+            assert d.max() <= 5e-4 and np.mean(d > 1e-6) < 1e-3, (step, k, d.max(), np.mean(d > 1e-6))
+    assert trainer.policy._popart_updates == onet.popart_updates == 1001
+    # the one rescale moved the head by far more than those bounds (Adam alone moves a weight by ~lr = 5e-4 per epoch)
+    assert float((onet.params[head].detach() - w_before).abs().max()) > 0.01
+
+
+def check_smac_steps(g, tag, policy_args, rescale=None):
+    from popart_rescale_cases import scale_rewards
+    trainer = trainer_api.make(config.Trainer("mappo", args=TRAINER), config.Policy("smac_rnn", args=policy_args))
+    if rescale is not None:
+        assert trainer.policy._popart_burn_in == rescale["burn_in"]  # what unbiased_popart=True sets (smac_rnn.py:132)
+        trainer.policy._popart_updates = rescale["updates"]
     for k, v in trainer.policy.get_checkpoint()["state_dict"].items():  # same seed -> the reference's initial weights
-        assert np.allclose(v.numpy(), g[f"smac_init_param:{k}"], rtol=1e-4, atol=1e-4), k
-    names = list(g["smac_stat_names"])
+        assert np.allclose(v.numpy(), g[f"{tag}_init_param:{k}"], rtol=1e-4, atol=1e-4), k
+    names = list(g[f"{tag}_stat_names"])
     for step in range(2):
         arrays = synthetic.make_multiagent_arrays(seed=300 + step, **SAMPLE)
+        if rescale is not None:
+            arrays = scale_rewards(arrays, rescale["reward_scale"][step])
         sample = synthetic.to_sample_batch(arrays)
         if step == 0:
             Tb = arrays["on_reset"].shape[0]
             ar = trainer.policy.analyze(sample[:Tb - 1], target="ppo")
-            lp, ref_lp = ar.new_action_log_probs.cpu().numpy(), g["smac_analyze_new_lp"]
+            lp, ref_lp = ar.new_action_log_probs.cpu().numpy(), g[f"{tag}_analyze_new_lp"]
             assert lp.shape == ref_lp.shape == (Tb - 1, 4, A, 1)
             dead = arrays["obs.is_alive"][:Tb - 1] == 0
             assert np.array_equal(np.isneginf(lp), dead) and np.array_equal(np.isneginf(ref_lp), dead)
             assert close(lp[~dead], ref_lp[~dead], 1e-5), "analyze log-probs"
-            assert close(ar.state_values.cpu().numpy(), g["smac_analyze_value"], 1e-5), "analyze values"
-            assert close(ar.entropy.cpu().numpy(), g["smac_analyze_entropy"], 1e-5), "analyze entropy"
+            assert close(ar.state_values.cpu().numpy(), g[f"{tag}_analyze_value"], 1e-5), "analyze values"
+            assert close(ar.entropy.cpu().numpy(), g[f"{tag}_analyze_entropy"], 1e-5), "analyze entropy"
         res = trainer.step(sample)
-        ref = dict(zip(names, g[f"smac_step{step}_stats"]))
+        ref = dict(zip(names, g[f"{tag}_step{step}_stats"]))
         for k in ("policy_loss", "value_loss", "entropy", "advantage", "value_targets", "importance_weight", "clip_ratio",
                   "done", "truncated", "grad_norm", "frames", "denorm_value"):
             tol = 1e-5 if k in ("policy_loss", "value_loss", "entropy", "value_targets", "denorm_value") else 1e-4
             assert abs(res.stats[k] - ref[k]) <= tol * max(abs(ref[k]), 1e-2), (step, k, res.stats[k], ref[k])
         if step == 0:
-            assert sample.analyzed_result.adv.shape == g["smac_step0_adv"].shape  # [Tb, B, agents, 1]
-            assert close(sample.analyzed_result.adv, g["smac_step0_adv"], 1e-5)
-            assert close(sample.analyzed_result.ret, g["smac_step0_ret"], 1e-5)
+            assert sample.analyzed_result.adv.shape == g[f"{tag}_step0_adv"].shape  # [Tb, B, agents, 1]
+            assert close(sample.analyzed_result.adv, g[f"{tag}_step0_adv"], 1e-5)
+            assert close(sample.analyzed_result.ret, g[f"{tag}_step0_ret"], 1e-5)
         sd = trainer.policy.get_checkpoint()["state_dict"]
-        pre = f"smac_step{step}_param:"
+        pre = f"{tag}_step{step}_param:"
         for key in g.files:
             if key.startswith(pre):
                 got = sd[key[len(pre):]].numpy()
                 assert np.abs(got - g[key]).max() <= 2e-5, (step, key, np.abs(got - g[key]).max())
                 if "_RunningMeanStd__" in key:
                     assert got.dtype == np.float64 and np.allclose(got, g[key], rtol=1e-6, atol=1e-13), (step, key)
-    assert trainer.policy.version == int(g["smac_version"]) and res.step == trainer.policy.version
+    assert trainer.policy.version == int(g[f"{tag}_version"]) and res.step == trainer.policy.version
 
 
 def test_smac_rollout_golden(golden):

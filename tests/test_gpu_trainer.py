@@ -12,6 +12,7 @@ from oracle.trainer import OracleMappo
 from srl_amd.api import config, policy as policy_api, trainer as trainer_api
 from srl_amd.namedarray import NamedArray
 from srl_amd.runtime import synthetic
+from popart_rescale_cases import CASES as RESCALE_CASES, scale_rewards
 
 srl_amd.register_all()
 pytestmark = pytest.mark.gpu
@@ -172,6 +173,8 @@ CASES["padm"] = (dict(obs_dim={"img": (4, 12, 10), "seq": (2, 21)}, action_dim=3
                  dict(popart=False, ppo_epochs=2, optimizer_config=dict(lr=1e-3), max_grad_norm=10.0),
                  dict(T=5, B=4, obs_spec={"img": ((4, 12, 10), "u8"), "seq": ((2, 21), "f32")}, action_dims=3, p_done=0.1), 2,
                  "steps_cnn_padmode.npz")
+# PopArt's head rescale (gen_golden.py gen_popart_rescale): every update rescales / the onset falls between the epochs of a step
+CASES.update({tag: (c["policy"], c["trainer"], c["sample"], c["n_steps"], "steps_popart_rescale.npz") for tag, c in RESCALE_CASES.items()})
 
 
 def make_trainer(policy_args, trainer_args):
@@ -188,9 +191,14 @@ def test_step_matches_reference_golden(tag, golden):
     pargs, targs, skw, n_steps, fname = CASES[tag]
     g = golden(fname)
     trainer = make_trainer(pargs, targs)
+    rescale = RESCALE_CASES.get(tag)
+    if rescale is not None:  # burn-in and count of the head, set from outside as the generator set them on the reference's head
+        trainer.policy._popart_burn_in, trainer.policy._popart_updates = rescale["burn_in"], rescale["updates"]
     names = list(g[f"{tag}_stat_names"])
     for step in range(n_steps):
         arrays = synthetic.make_sample_arrays(seed=100 + step, **skw)
+        if rescale is not None:
+            arrays = scale_rewards(arrays, rescale["reward_scale"][step])
         sample = synthetic.to_sample_batch(arrays)
         if step == 0 and f"{tag}_analyze_new_lp" in g.files:
             Tb = arrays["on_reset"].shape[0]
@@ -225,6 +233,74 @@ def test_step_matches_reference_golden(tag, golden):
                     assert got.dtype == np.float64 and np.allclose(got, g[key], rtol=1e-6, atol=1e-13), (tag, step, key)
     assert trainer.policy.version == int(g[f"{tag}_version"])
     assert res.step == trainer.policy.version
+
+
+def test_rescaled_head_is_served_fresh():
+    """`policy.update_popart` with the rescale active rewrites the head inside the flat parameter buffer.  What the policy serves
+    afterwards -- `analyze` and `rollout`, both of which ran before on the same observations, so whatever they derive from the
+    parameters exists -- must come from the rewritten head: the de-normalised values are what they were (PopArt's invariant,
+    popart.py:50-51), the normalised ones are the oracle's."""
+    pargs = RESCALE_CASES["par0"]["policy"]
+    pol = policy_api.make(config.Policy("actor-critic", args=pargs))
+    pol._popart_burn_in = 0
+    onet = OracleActorCritic(**pargs, burn_in_updates=0)
+    onet.load_state_dict({k: v.numpy() for k, v in pol.get_checkpoint()["state_dict"].items()})
+    skw = RESCALE_CASES["par0"]["sample"]
+    arrays = synthetic.make_sample_arrays(seed=100, **skw)
+    sample = synthetic.to_sample_batch(arrays)
+    T, N = skw["T"], 64
+    robs = arrays["obs.obs"][:T].reshape(-1, 4)[:N]
+    req = policy_api.RolloutRequest(obs=NamedArray(obs=robs), is_evaluation=np.ones((N, 1), np.uint8),
+                                    on_reset=np.zeros((N, 1), np.uint8))
+    f32 = lambda a: torch.from_numpy(np.asarray(a)).float()
+    o_analyze = lambda: onet.analyze({"obs": f32(arrays["obs.obs"][:T])}, f32(arrays["action.x"][:T]), f32(arrays["on_reset"][:T]))[1]
+    rng = np.random.default_rng(3)
+    mask = (rng.random((T, 8, 1)) < 0.9).astype(np.uint8)
+    # Both updates rescale: from the all-zero statistics (mean 0, std 0.1) to the first targets' own, and on from there.  The
+    # de-normalised values stay what the untrained head gives at the start, a few 0.01; they come out of v * std + mean, so the
+    # targets are centred near zero: around a mean fifty times larger, float32 values of v could not hold them to 1e-5.
+    for mean, std in ((0.02, 0.3), (-0.03, 0.6)):
+        x = (mean + std * rng.standard_normal((T, 8, 1))).astype(np.float32)
+        before_a = pol.denormalize_value(pol.analyze(sample[:T], target="ppo").state_values).cpu().numpy()
+        before_r = pol.denormalize_value(pol.rollout(req).analyzed_result.value).cpu().numpy()
+        w_before = pol.get_checkpoint()["state_dict"]["critic_head._PopArtValueHead__weight"].clone()
+        pol.update_popart(x, mask)
+        onet.update_popart(torch.from_numpy(x), torch.from_numpy(mask))
+        assert not torch.equal(w_before, pol.get_checkpoint()["state_dict"]["critic_head._PopArtValueHead__weight"])
+        after_a = pol.analyze(sample[:T], target="ppo").state_values
+        after_r = pol.rollout(req).analyzed_result.value
+        assert close(pol.denormalize_value(after_a).cpu().numpy(), before_a, 1e-5, scale=1e-2), "analyze: de-normalised values moved"
+        assert close(pol.denormalize_value(after_r).cpu().numpy(), before_r, 1e-5, scale=1e-2), "rollout: de-normalised values moved"
+        with torch.no_grad():
+            o_value = o_analyze().numpy()
+        assert close(after_a.cpu().numpy(), o_value, 1e-5), "analyze values"
+        assert close(after_r, o_value.reshape(-1, 1)[:N], 1e-5, scale=1e-2), "rollout values"
+    assert pol._popart_updates == 2 and onet.popart_updates == 2
+
+
+def test_captured_step_crosses_the_burn_in():
+    """Whether a PopArt update rescales the head is decided on the host, per epoch, so a captured step carries the pattern of the
+    step it was captured in.  `parx` from the same initial state with and without `use_graph`: the first two steps are the
+    fixture's (no rescale, then the onset between the epochs of step 1); four more on the same two samples follow, so that a
+    graph is captured and replayed on each side of the burn-in.  Tolerances of tests/test_gpu_graph.py."""
+    c = RESCALE_CASES["parx"]
+    mk = lambda graph: make_trainer(c["policy"], dict(c["trainer"], use_graph=graph))
+    eager, graphed = mk(False), mk(True)
+    for tr in (eager, graphed):
+        tr.policy._popart_burn_in, tr.policy._popart_updates = c["burn_in"], c["updates"]
+    for step in range(6):
+        arrays = scale_rewards(synthetic.make_sample_arrays(seed=100 + step % 2, **c["sample"]), c["reward_scale"][step % 2])
+        ra = eager.step(synthetic.to_sample_batch(dict(arrays)))
+        rb = graphed.step(synthetic.to_sample_batch(dict(arrays)))
+        assert ra.step == rb.step
+        for k, v in ra.stats.items():
+            assert abs(v - rb.stats[k]) <= 2e-5 * max(1.0, abs(v)), (step, k, v, rb.stats[k])
+        pa, pb = eager.get_checkpoint()["state_dict"], graphed.get_checkpoint()["state_dict"]
+        for k in pa:  # parameters and PopArt statistics
+            assert torch.allclose(pa[k], pb[k], rtol=0, atol=1e-5), (step, k, float((pa[k] - pb[k]).abs().max()))
+    assert eager.policy._popart_updates == graphed.policy._popart_updates == 18
+    # one graph per rescale pattern: none / onset inside the step / every epoch; the last one was captured and replayed
+    assert len(graphed._graphs) == 3 and list(graphed._graphs.values())[-1] is not None
 
 
 def test_init_matches_reference_init(golden):
@@ -268,6 +344,33 @@ def test_step_vs_oracle_larger(T, B, chunk):
         ostats, oout = oracle.step(arrays)
         assert close(sample.analyzed_result.ret, oout["ret"], 1e-5)
         for k in ("policy_loss", "value_loss", "entropy", "grad_norm"):
+            assert abs(res.stats[k] - ostats[k]) <= 2e-5 * max(abs(ostats[k]), 1e-2), (step, k, res.stats[k], ostats[k])
+    sd = trainer.policy.get_checkpoint()["state_dict"]
+    osd = onet.state_dict()
+    for k in sd:
+        assert np.abs(sd[k].numpy() - osd[k].numpy()).max() <= 3e-5, k
+
+
+def test_rescale_over_several_row_chunks_vs_oracle():
+    """An epoch that rescales the PopArt head, with the batch cut into row chunks (three, the last one ragged): every chunk's
+    forward pass must see the head as it was before the update and every chunk's backward pass the rescaled one (the
+    reference analyses the whole sample, then rescales, then differentiates), on one pipeline.  Bounds of
+    test_step_vs_oracle_larger; the second step's rewards are four times the first's so that its rescales are no near-identity."""
+    pargs = dict(C1_POLICY, popart=True, layernorm=True, seed=7)
+    targs = dict(ATARI_TRAINER, popart=True, ppo_epochs=2, chunk_rows=100)
+    trainer = make_trainer(pargs, targs)
+    trainer.policy._popart_burn_in = 0
+    onet = OracleActorCritic(**pargs, burn_in_updates=0)
+    onet.load_state_dict({k: v.numpy() for k, v in trainer.policy.get_checkpoint()["state_dict"].items()})
+    oracle = OracleMappo(onet, **{k: v for k, v in targs.items() if k != "chunk_rows"})
+    for step in range(2):
+        arrays = scale_rewards(synthetic.make_sample_arrays(seed=step, T=32, B=8, obs_spec=synthetic.CARTPOLE_OBS, action_dims=2,
+                                                            p_done=0.02), (1.0, 4.0)[step])
+        sample = synthetic.to_sample_batch(arrays)
+        res = trainer.step(sample)
+        ostats, oout = oracle.step(arrays)
+        assert close(sample.analyzed_result.ret, oout["ret"], 1e-5)
+        for k in ("policy_loss", "value_loss", "entropy", "grad_norm", "denorm_value"):
             assert abs(res.stats[k] - ostats[k]) <= 2e-5 * max(abs(ostats[k]), 1e-2), (step, k, res.stats[k], ostats[k])
     sd = trainer.policy.get_checkpoint()["state_dict"]
     osd = onet.state_dict()

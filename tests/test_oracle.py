@@ -180,6 +180,41 @@ def test_full_step_golden_popart_vtrace(golden, tag, pargs, targs, n_steps, p_tr
         assert np.allclose(sd[k].numpy(), g[f"{tag}_step{n_steps - 1}_param:{k}"], rtol=1e-4, atol=1e-6), k
 
 
+@pytest.mark.parametrize("tag", ["par0", "parx", "smacu"])
+def test_full_step_golden_popart_rescale(golden, tag):
+    """PopArt's head rescale (popart.py:47-51; fixtures: gen_golden.py gen_popart_rescale): every update rescales (par0), the
+    onset falls between the epochs of a step (parx), and `smac_rnn(unbiased_popart=True)` crossing its 1000 updates (smacu).
+    Assertions and tolerances of test_full_step_golden_popart_vtrace."""
+    from oracle.net import OracleSMACNet
+    from popart_rescale_cases import CASES, SMACU, scale_rewards
+    g = golden("steps_popart_rescale.npz")
+    if tag == "smacu":
+        c = SMACU
+        net = OracleSMACNet(30, 48, 9, c["policy"]["hidden_dim"], c["policy"]["chunk_len"])
+        make = lambda step: synthetic.make_multiagent_arrays(seed=300 + step, **c["sample"])
+    else:
+        c = CASES[tag]
+        net = OracleActorCritic(**c["policy"])
+        make = lambda step: synthetic.make_sample_arrays(seed=100 + step, **c["sample"])
+    pre = f"{tag}_init_param:"
+    net.load_state_dict({k[len(pre):]: g[k] for k in g.files if k.startswith(pre)})
+    net.burn_in_updates, net.popart_updates = c["burn_in"], c["updates"]
+    tr = OracleMappo(net, **c["trainer"])
+    names = list(g[f"{tag}_stat_names"])
+    n_steps = c["n_steps"]
+    for step in range(n_steps):
+        stats, out = tr.step(scale_rewards(make(step), c["reward_scale"][step]))
+        ref = dict(zip(names, g[f"{tag}_step{step}_stats"]))
+        for k in ["policy_loss", "value_loss", "entropy", "grad_norm", "clip_ratio", "value_targets", "denorm_value"]:
+            assert abs(stats[k] - ref[k]) <= 2e-5 * max(1.0, abs(ref[k])), (tag, step, k)
+        if step == 0:
+            assert np.allclose(out["ret"], g[f"{tag}_step0_ret"], rtol=1e-5, atol=1e-6)
+    assert net.popart_updates == c["updates"] + n_steps * c["trainer"].get("ppo_epochs", 1)
+    sd = net.state_dict()
+    for k in sd:
+        assert np.allclose(sd[k].numpy(), g[f"{tag}_step{n_steps - 1}_param:{k}"], rtol=1e-4, atol=1e-6), k
+
+
 def test_full_step_golden_recurrent(golden):
     """GRU backbone with auto reset and chunked analysis: OracleMappo against the reference (gen_golden.py gen_rnn)."""
     g = golden("steps_rnn.npz")
