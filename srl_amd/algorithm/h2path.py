@@ -152,8 +152,8 @@ class H2Cnn:
     # with three / four: what the smaller fill gains the slabs' traffic takes back.  Off by default.
     FC_TRAIN_SPLITK = int(os.environ.get("SRL_FC_TRAIN_SPLITK", "1"))
 
-    def forward(self, tag, staged, obs, n, is_u8, src, mean, rstd, row_index, split_fc=None):
-        """The four layers on `n` rows.  src / mean / rstd / row_index: the first layer's staged frames and statistics as
+    def forward(self, tag, n, first, split_fc=None):
+        """The four layers on `n` rows.  ``first`` (hipnet.FirstConv): the first layer's staged frames and statistics as
         `_encoder_fwd` resolved them.  Returns (y Buf float32 [n, H], saved).  ``split_fc`` ("infer" | "train": the consumer
         finishes the product -- `srl_ln_heads_fwd`'s x_slabs): the Linear writes raw partial sums, `saved["fc_slabs"]` = (pointer,
         slabs, stride in floats, bias pointer, activation) tells the consumer where; y is then only valid BEHIND the consumer's
@@ -174,9 +174,10 @@ class H2Cnn:
         desc1 = hip.conv_desc(n, 21, 21, 64, 2, 2, 1, 32, hip.ACT_RELU)
         fws = self._folded()[1]
         reuse = net._derived_fresh(f"{self.c1.prefix}.folded:h2", fws)
-        hip.conv2d_obs_fwd_h2(desc1, src.data_ptr(), mean.data_ptr(), rstd.data_ptr(), net._p(f"{self.ln.prefix}.weight"),
-                              net._p(f"{self.ln.prefix}.bias"), net._p(f"{self.c1.prefix}.weight"), net._p(f"{self.c1.prefix}.bias"),
-                              a1, P(S_A1), fws, row_index, P(M_A1), m1, reuse_folded=reuse, ent_order=2,
+        hip.conv2d_obs_fwd_h2(desc1, first.src.data_ptr(), first.mean.data_ptr(), first.rstd.data_ptr(),
+                              net._p(f"{self.ln.prefix}.weight"), net._p(f"{self.ln.prefix}.bias"),
+                              net._p(f"{self.c1.prefix}.weight"), net._p(f"{self.c1.prefix}.bias"),
+                              a1, P(S_A1), fws, first.row_index, P(M_A1), m1, reuse_folded=reuse, ent_order=2,
                               records=self._bytes(f"{t}records", 16 * (n + 32)))   # (the folded weights are shared: `wws`)
         if not reuse:
             net._derived_done(fws)
@@ -188,7 +189,7 @@ class H2Cnn:
                     bias=net._p(f"{self.c3.prefix}.bias"), act=1, out_scale=P(S_A3), bound_in=P(M_A2),
                     bound_w=W(R_W3), bound_b=W(B_W3), mask_out=m3)
         # Linear: float32 out (the layers behind it take the ReLU derivative from these floats, as after `_linear_fwd`)
-        saved = dict(n=n, a1=a1, a2=a2, a3=a3, m1=m1, m2=m2, m3=m3, first=(src, is_u8, mean, rstd, row_index), tag=tag)
+        saved = dict(n=n, a1=a1, a2=a2, a3=a3, m1=m1, m2=m2, m3=m3, first=first, tag=tag)
         y = net._buf(f"{tag}{self.fc.prefix}.y", n, self.H)
         ks, wide = 1, False
         if split_fc == "infer":
@@ -262,13 +263,13 @@ class H2Cnn:
 
     def first_layer_bwd(self, n, first, dz_ptr, dz_absmax_ptr):
         """The first layer's weight / bias / LayerNorm-affine gradients from dz (float32 NHWC [n, 20, 20, 32]) with its measured
-        range.  Inside the trainer's chunk loop the position sums (Q, R, C) of an executor's chunks add up in this block's
+        range; ``first``: the first-convolution record of the forward pass (hipnet.FirstConv).
+        Inside the trainer's chunk loop the position sums (Q, R, C) of an executor's chunks add up in this block's
         workspace and the four gradients are formed ONCE, behind the executor's last chunk (srl_conv2d_obs_bwd's `phase`).
         Whether a call continues an accumulation is decided from the block's STATE, never from `n`: a ragged last chunk --
-        including one below H2_MIN_ROWS, which `HipNet._chain_bwd` sends here from the layer-by-layer path -- must add to and
+        including one below H2_MIN_ROWS, which `HipNet._conv_first_bwd` sends here from the layer-by-layer path -- must add to and
         close what the chunks before it opened.  Only OPENING one asks for a full-sized chunk."""
         net = self.net
-        src, is_u8, mean, rstd, row_index = first
         desc1 = hip.conv_desc(n, 21, 21, 64, 2, 2, 1, 32, hip.ACT_RELU)
         wsz = hip.conv2d_obs_bwd_workspace(desc1)
         phase = 3
@@ -283,10 +284,11 @@ class H2Cnn:
             self.open = not net.last_chunk
             self._open_ws = wst if self.open else None
         g = net._g
-        hip.conv2d_obs_bwd(desc1, src.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), net._p(f"{self.ln.prefix}.weight"),
-                           net._p(f"{self.ln.prefix}.bias"), net._p(f"{self.c1.prefix}.weight"), dz_ptr, g(f"{self.c1.prefix}.weight"),
-                           g(f"{self.c1.prefix}.bias"), g(f"{self.ln.prefix}.weight"), g(f"{self.ln.prefix}.bias"),
-                           wst.data_ptr(), channels_last=True, row_index=row_index, phase=phase,
+        hip.conv2d_obs_bwd(desc1, first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(),
+                           net._p(f"{self.ln.prefix}.weight"), net._p(f"{self.ln.prefix}.bias"),
+                           net._p(f"{self.c1.prefix}.weight"), dz_ptr, g(f"{self.c1.prefix}.weight"), g(f"{self.c1.prefix}.bias"),
+                           g(f"{self.ln.prefix}.weight"), g(f"{self.ln.prefix}.bias"),
+                           wst.data_ptr(), channels_last=True, row_index=first.row_index, phase=phase,
                            dz_absmax_ptr=dz_absmax_ptr)
 
     # The Linear's weight gradient on the pre-split operands both products of the data-gradient chain read anyway (dyh, a3) through

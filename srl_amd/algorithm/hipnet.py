@@ -56,6 +56,130 @@ class RnnCtx(NamedTuple):
     reset: Optional[torch.Tensor]
 
 
+# ---------------------------------------------------------------------------------------------------
+# the backward tape: what a forward pass with keep_tape=True leaves for backward()
+class Rec(NamedTuple):
+    """One record of a chain's tape, appended by the layer's forward handler and read by the backward handler of its `kind`."""
+    kind: str
+    layer: object    # the layer's spec; the block that ran it ("h2cnn": an H2Cnn, "fusedenc" / "fusedtail": a FusedChain)
+    x: object        # the layer's input (a Buf; the observation tensor, the token ids or the leaves where a layer reads those)
+    saved: object    # per kind: LayerNorm statistics, a Linear's input range, one of the payloads below, the rows of a pool
+    in_act: int      # the activation that produced x: its derivative is applied by this record's data gradient
+    out_cols: int    # columns of the layer's output (a Flatten between two records shows as g.cols != below.out_cols)
+
+
+class FirstConv(NamedTuple):
+    """The first convolution's view of the observation (the observation LayerNorm `lnspec` is fused into it)."""
+    src: object           # tensor the frames are read from (the sample's rows, their space-to-depth copy, or the ring)
+    is_u8: bool
+    mean: torch.Tensor
+    rstd: torch.Tensor
+    lnspec: object
+    channels_last: bool
+    row_index: object     # the sample's slot index when the frames are read in place from the ring, else None
+
+
+class ConvSaved(NamedTuple):
+    P: Optional[Buf]              # the patch matrix of the explicit path; None: implicit GEMM
+    first: Optional[FirstConv]    # set for the layer that reads the observation
+    n: int
+    desc: object
+    x_range: Optional[int]        # device float bounding max |x| (the producer tracked it), or None
+
+
+LnHeadsSaved = NamedTuple("LnHeadsSaved", [("mean", torch.Tensor), ("rstd", torch.Tensor), ("heads", list)])
+ObsLnSaved = NamedTuple("ObsLnSaved", [("is_u8", bool), ("mean", torch.Tensor), ("rstd", torch.Tensor), ("n", int)])
+ConvNdSaved = NamedTuple("ConvNdSaved", [("P", Buf), ("n", int), ("sp", tuple)])   # sp: the (padded) input volume
+LstmSaved = NamedTuple("LstmSaved", [("inp", Buf), ("pre", Buf), ("hin", Buf), ("cin", Buf), ("cnew", Buf)])   # one per layer
+GruSaved = NamedTuple("GruSaved", [("inp", Buf), ("gi", Buf), ("gh", Buf), ("hin", Buf)])                      # one per layer
+RnnSaved = NamedTuple("RnnSaved", [("layers", list), ("ctx", RnnCtx)])
+
+
+class FusedChain(NamedTuple):
+    """A LayerNorm / Linear chain that ran as one launch (`_fused_layers_fwd`): a whole trunk's tape, or the `layer` of a
+    `fusedenc` / `fusedtail` record."""
+    arr: object
+    x: object
+    xptr: int
+    xcols: int
+    tape: Optional[torch.Tensor]
+    tld: int
+    n: int
+    feat: Buf
+    act: int
+    head_in: bool     # the tower's head ran inside the launch
+    prefixes: list
+    need_dx: bool
+    tag: str
+
+
+class TrunkTape(NamedTuple):
+    enc_tapes: list   # per piece of rows, per encoder: a list of Rec
+    bb_tape: list     # the backbone's records
+    widths: list
+    pieces: list
+    # whether the tower's head ran inside the trunk's last launch: False; True (the trunk ends in a `fusedtail` that took the
+    # head in); "lnheads" (the encoder closes in `lnheads`: with a shared backbone BOTH heads ran there)
+    head_in: object
+
+
+class PassTape(NamedTuple):
+    """`HipNet._tape`: one forward pass.  c_tape is None when the backbone is shared."""
+    n: int
+    a_feat: Optional[Buf]
+    a_act: int
+    a_tape: object    # TrunkTape | FusedChain
+    c_feat: Optional[Buf]
+    c_act: int
+    c_tape: object
+    cm: bool          # the pass ran on chunk-major rows
+    rnn: Optional[RnnCtx]
+
+
+class _Walk:
+    """Running state of one walk over a list of layers: an encoder (`_encoder_fwd`) or a backbone (`_trunk_fwd`)."""
+    __slots__ = ("obs", "n", "tag", "tape", "enc", "lnheads", "into", "track", "h2", "staged", "cur", "cur_act", "cur_range",
+                 "pending_obs_ln", "skip", "done")
+
+    def __init__(self, obs, n, tag, tape, enc=None, lnheads=None, into=None, cur=None, track=True):
+        self.obs, self.n, self.tag, self.tape, self.enc, self.lnheads, self.into, self.track = obs, n, tag, tape, enc, lnheads, into, track
+        self.h2 = self.staged = self.pending_obs_ln = None
+        self.cur, self.cur_act = cur, 0
+        self.cur_range = None  # device float bounding max |cur| (convolution outputs), or None: range unknown
+        self.skip, self.done = 0, False
+
+    def advance(self, y, act=0, y_range=None):
+        # (track=False, the backbone: its Linears have never been told their input's range)
+        self.cur, self.cur_act, self.cur_range = y, act, (y_range if self.track else None)
+
+    def finish(self, out):
+        """`out` is the walk's output: the layers that remain ran inside the last launch."""
+        self.cur, self.done = out, True
+
+
+_FWD, _FWD_KINDS, _BWD, _BWD_OWN_RELEASE = {}, set(), {}, set()
+
+
+def _fwd(*spec_classes, emits=()):
+    """Forward handler of these spec classes (`HipNet.FWD_HANDLERS`); ``emits``: the record kinds it may append."""
+    def register(fn):
+        _FWD.update((c, fn) for c in spec_classes)
+        _FWD_KINDS.update(emits)
+        return fn
+    return register
+
+
+def _bwd(kind, own_release=False):
+    """Backward handler of the records of `kind` (`HipNet.BWD_HANDLERS`).  ``own_release``: it releases its parameters'
+    gradient buckets itself (`HipNet.BWD_OWN_RELEASE`)."""
+    def register(fn):
+        _BWD[kind] = fn
+        if own_release:
+            _BWD_OWN_RELEASE.add(kind)
+        return fn
+    return register
+
+
 class Workspace:
     """Named device buffers that only ever grow (steady-state steps allocate nothing)."""
 
@@ -133,7 +257,6 @@ class HipNet:
         # recurrent layers in one launch per direction (csrc/mlp_small.hip).  tests/test_gpu_smac_attn.py clears it for
         # its layer-by-layer reference
         self._enc_fused = True
-        self._lnheads_dv = None
         self._infer = False
         self._cm = False
         self._mlp_cache = {}
@@ -510,7 +633,7 @@ class HipNet:
         step = max(256, ((0xfff00000 // (4 * width)) // 256) * 256)
         return [(r0, min(n, r0 + step)) for r0 in range(0, n, step)]
 
-    def _linear_fwd_h2d(self, L, x: Buf, tag: str, x_range) -> Buf:
+    def _linear_fwd_h2d(self, L, x: Buf, tag: str, x_range):
         n, K, N = x.rows, L.in_features, L.out_features
         sl = self.ws.get(f"{tag}{L.prefix}.h2d.slots", self.H2D_NP)
         sl.zero_()
@@ -527,11 +650,10 @@ class HipNet:
             hip.h2_gemm(xh + 4 * r0 * K, wh, sp + 4 * self.H2D_SX, wsp + 4 * self.H2D_SW, r1 - r0, N, K, y.ptr + 4 * r0 * N,
                         bias=self._p(f"{L.prefix}.bias"), act=1 if L.act == hip.ACT_RELU else 0,
                         mask_out=(mask + 4 * (r0 * N // 32)) if mask else None, out_absmax=sp + 4 * self.H2D_MY)
-        self._y_range = sp + 4 * self.H2D_MY
         # what the backward pass reads again, found by the tape record's input (the backward pass of an encoder cut into pieces
         # walks every piece under ONE tag: names would find another piece's buffers)
         self._h2d_saved[(L.prefix, x.ptr)] = (xh, sp)
-        return y._replace(mask=mask) if mask else y
+        return (y._replace(mask=mask) if mask else y), sp + 4 * self.H2D_MY
 
     def _linear_bwd_h2d(self, L, x: Buf, dz: Buf, in_act: int, need_dx: bool, tag: str, dz_range, dx_range) -> Optional[Buf]:
         n, K, N = x.rows, L.in_features, L.out_features
@@ -572,10 +694,10 @@ class HipNet:
         return (self.on_gpu and not L.first and not L.pad and L.stride == 1 and L.k in (3, 5)
                 and hip.conv2d_small_supported(desc))
 
-    def _linear_fwd(self, L: ns.LinearSpec, x: Buf, tag: str, x_range: Optional[int] = None) -> Buf:
+    def _linear_fwd(self, L: ns.LinearSpec, x: Buf, tag: str, x_range: Optional[int] = None):
         """``x_range``: device float bounding max |x| when the producer tracked it (a convolution's output): with the
-        weight's range the product runs on two f16 pieces per operand (srl_gemm_desc::a_absmax)."""
-        self._y_range = None
+        weight's range the product runs on two f16 pieces per operand (srl_gemm_desc::a_absmax).  Returns (y, device float
+        bounding max |y| or None: only the wide-layer path measures it)."""
         if self._h2d_ok(L, x):
             return self._linear_fwd_h2d(L, x, tag, x_range)
         y = self._buf(f"{tag}{L.prefix}.y", x.rows, L.out_features)
@@ -586,7 +708,7 @@ class HipNet:
         hip.gemm(x.rows, L.out_features, L.in_features, x.ptr, x.ld, 0, pre or w, L.in_features, 0,
                  y.ptr, y.ld, bias=self._p(f"{L.prefix}.bias"), act=L.act, a_absmax=x_range, b_absmax=w_range,
                  b_presplit=pre is not None)
-        return y
+        return y, None
 
     def _wgrad(self, out_f, in_f, rows, dz: Buf, x_ptr, x_ld, gw_ptr, gb_ptr=None, dz_range=None, x_range=None):
         """gw += dz^T x; gb += column sums of dz -- from the same kernel when the operands allow it.  ``dz_range`` /
@@ -696,7 +818,7 @@ class HipNet:
                                   hin.ptr + o1n if nxt else None, cin.ptr + o1n if nxt else None)
             hip.copy2d(y.ptr + 4 * (C - 1) * N * H, H, last[l].data_ptr(), SW, N, H)
             hip.copy2d(cnew.ptr + 4 * (C - 1) * N * H, H, last[l].data_ptr() + 4 * H, SW, N, H)
-            saved.append((inp, pre, hin, cin, cnew))
+            saved.append(LstmSaved(inp, pre, hin, cin, cnew))
             inp = y
         for l in range(G.layers if G.kind == "gru" else 0):
             w_ih, w_hh = self._p(f"{G.prefix}.weight_ih_l{l}"), self._p(f"{G.prefix}.weight_hh_l{l}")
@@ -717,17 +839,17 @@ class HipNet:
                 hip.gru_cell_fwd(gi.ptr + o3, gh.ptr + o3, hin.ptr + o1, rptr(c + 1) if nxt else None, N, H, y.ptr + o1,
                                  hin.ptr + 4 * (c + 1) * N * H if nxt else None)
             hip.copy2d(y.ptr + 4 * (C - 1) * N * H, H, last[l].data_ptr(), H, N, H)
-            saved.append((inp, gi, gh, hin))
+            saved.append(GruSaved(inp, gi, gh, hin))
             inp = y
         if K > 1 and not self._cm:
             ytm = self._buf(f"{tag}{G.prefix}.ytm", n, H)
             hip.chunk_rows(inp.ptr, ytm.ptr, T, B, C, H, inverse=True)
         else:
             ytm = inp
-        return ytm, (saved, ctx), last
+        return ytm, RnnSaved(saved, ctx), last
 
-    def _gru_bwd(self, G: ns.GruSpec, saved_all, dy: Buf, in_act: int, need_dx: bool, tag: str) -> Optional[Buf]:
-        saved, ctx = saved_all
+    def _gru_bwd(self, G: ns.GruSpec, saved_all: RnnSaved, dy: Buf, in_act: int, need_dx: bool, tag: str) -> Optional[Buf]:
+        saved, ctx = saved_all.layers, saved_all.ctx
         T, B, C, H = ctx.T, ctx.B, ctx.C, G.hidden
         n, K = T * B, T // C
         N = K * B
@@ -803,461 +925,610 @@ class HipNet:
             return dxt
         return dout
 
-    # ------------------------------------------------------------------ encoders
+    # ------------------------------------------------------------------ encoders: one forward handler per layer spec
+    # A handler `(self, st, L)` runs layer L on `st.cur`, appends its record to `st.tape` (with the record's `out_cols`: only
+    # the handler knows it) and moves `st` on.  FWD_HANDLERS picks it by spec class; a new layer kind adds one handler here, one
+    # backward handler below and, if it saves a tuple, one record type above.
+    FWD_HANDLERS, FWD_KINDS = _FWD, _FWD_KINDS
+
     def _encoder_fwd(self, enc: ns.EncoderSpec, obs: torch.Tensor, n: int, tag: str, tape: list, lnheads=None, into=None) -> Buf:
         """obs: device tensor [n, *shape] (float32 vectors; uint8 or float32 images).  ``lnheads``: ``(heads, outs)`` when the
         encoder's closing LayerNorm and the heads behind it are to run as one launch (`_lnheads_ok`): the record `lnheads` then
         closes the tape and the heads' outputs are in ``outs``."""
-        cur: Optional[Buf] = None
-        cur_act = 0
-        cur_range = None  # device float bounding max |cur| (convolution outputs), or None: range unknown
-        pending_obs_ln = None
-        staged = None
+        st = _Walk(obs, n, tag, tape, enc, lnheads, into)
         if isinstance(obs, RingObs):  # rows kept in the HBM observation ring since their rollout
             if obs.rows != n:
                 raise hip.HipError(f"observation `{enc.key}`: {obs.rows} ring rows for {n} network rows")
             if obs.layout[0] == "s2d":
-                staged = obs  # already in the first convolution's layout, statistics beside them
+                st.staged = obs  # already in the first convolution's layout, statistics beside them
             else:
-                obs = obs.gather_raw(self.ws, f"{tag}{enc.key}.ring")
+                st.obs = obs.gather_raw(self.ws, f"{tag}{enc.key}.ring")
+        if self._fwd_fused_enc(st):
+            return st.cur
+        st.h2 = self._h2_for(enc)
+        closing = enc.layers[-1] if lnheads is not None else None
+        handlers = self.FWD_HANDLERS
+        for L in enc.layers:
+            if st.skip:  # layers the pre-split block below has already run
+                st.skip -= 1
+                continue
+            if L is closing and st.cur is not None and st.cur.ld == st.cur.cols == L.dim and st.cur.rows == n:
+                self._fwd_lnheads(st, L)
+            else:
+                handlers[type(L)](self, st, L)
+            if st.done:
+                break
+        return st.cur
+
+    @_fwd(emits=("fusedenc",))
+    def _fwd_fused_enc(self, st) -> bool:
         # a vector encoder in front of a recurrent backbone (the multi-agent nets: LayerNorm -> Linear -> LayerNorm -> Linear ->
         # LayerNorm, 64 wide) as ONE launch per direction: the whole-trunk fusion above stops at the recurrent cell, and layer by
         # layer these 307 200-row products and LayerNorms were ~2 ms of the SMAC-sized step
-        if (self._enc_fused and staged is None and isinstance(obs, torch.Tensor) and obs.dim() == 2
+        enc, obs, n, tag = st.enc, st.obs, st.n, st.tag
+        if not (self._enc_fused and st.staged is None and isinstance(obs, torch.Tensor) and obs.dim() == 2
                 and obs.dtype == torch.float32 and enc.layers and all(isinstance(L, (ns.LayerNormSpec, ns.LinearSpec)) for L in enc.layers)
                 and (isinstance(enc.layers[-1], ns.LayerNormSpec) or enc.layers[-1].act == 0) and n >= 512):
-            rec = self._fused_layers_fwd((tag, "enc", enc.key), f"{tag}enc.{enc.key}.", list(enc.layers), obs, n)
-            if rec is not None:
-                tape.append(("fusedenc", rec, None, None, 0))
-                return rec["feat"]
-        h2 = self._h2_for(enc)
-        skip = 0
-        for L in enc.layers:
-            if skip:  # layers the pre-split block below has already run
-                skip -= 1
-                continue
-            if lnheads is not None and L is enc.layers[-1] and cur is not None and cur.ld == cur.cols == L.dim and cur.rows == n:
-                heads, outs = lnheads
-                mean = self.ws.get(f"{tag}{L.prefix}.mean", n)
-                rstd = self.ws.get(f"{tag}{L.prefix}.rstd", n)
-                slabs = tape[-1][3].get("fc_slabs") if (tape and tape[-1][0] == "h2cnn") else None
-                xptr, ks, stride, xb, xact, keep = slabs if slabs else (cur.ptr, 1, 0, None, 0, False)
-                # (a split product: this launch adds the slabs, the bias and the ReLU while it reads them -- and, when a backward
-                # pass follows, writes the finished rows to `cur`)
-                hip.ln_heads_fwd(xptr, cur.ld, n, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
-                                 [self._p(f"{h.prefix}.weight") for h in heads], [self._p(f"{h.prefix}.bias") for h in heads],
-                                 [h.out_features for h in heads], [o.data_ptr() for o in outs], [h.out_features for h in heads],
-                                 mean.data_ptr(), rstd.data_ptr(), x_slabs=ks, x_slab_stride=stride, x_bias=xb, x_act=xact,
-                                 x_out=cur.ptr if (slabs and not self._infer) else None, ldxo=cur.ld)
-                tape.append(("lnheads", L, cur, (mean, rstd, heads), cur_act))
-                return None
-            if isinstance(L, ns.InstrLstmSpec):
-                tok = self._instr_tokens(L, obs, n, enc.key)
-                # `into`: (pointer, pitch) of this encoder's columns in the trunk's concatenation buffer -- no copy follows
-                y = Buf(into[0], into[1], n, L.units) if into is not None else self._buf(f"{tag}{L.prefix}.y", n, L.units)
-                hip.instr_lstm_fwd(self._instr_desc(L), tok.data_ptr(), L.length, tok.dtype == torch.int32, n, y.ptr, y.ld)
-                # no tape: the backward launch walks forward again from the tokens (kept alive by the record)
-                tape.append(("instr", L, tok, None, 0))
-                cur, cur_act, cur_range = y, 0, None
-            elif isinstance(L, ns.ObsScaleSpec):
-                c, h, w = L.shape
-                if not isinstance(obs, torch.Tensor) or obs.dim() < 2 or obs.shape[0] != n or math.prod(obs.shape[1:]) != c * h * w:
-                    raise hip.HipError(f"image observation `{enc.key}`: sample rows of shape {tuple(getattr(obs, 'shape', ()))[1:]} "
-                                       f"for a network built for {tuple(L.shape)} ({n} rows expected)")
-                is_u8 = obs.dtype == torch.uint8
-                if not is_u8 and obs.dtype != torch.float32:
-                    raise hip.HipError(f"image observation `{enc.key}` must be uint8 or float32, got {obs.dtype}")
-                zero, scale, one = self._scale_consts(L, n)
-                y = self._buf(f"{tag}{L.prefix}.y", n * h * w, c)
-                # (x - 0) * scale * 1 + 0, channels-last: the observation LayerNorm's writer with constant tables.  Not on the tape:
-                # nothing is learnt here and the frames take no gradient
-                hip.obs_ln_nhwc(obs.data_ptr(), is_u8, zero, scale, one, zero, n, c, h, w, y.ptr)
-                cur, cur_act, cur_range = y, 0, None
-            elif isinstance(L, ns.EntityAttnSpec):
-                leaves = self._eattn_leaves(L, obs, n, enc.key)
-                y = self._buf(f"{tag}{L.prefix}.eattn.y", n, 2 * L.dim)
-                hip.entity_attn_fwd(self._eattn_desc(L), *leaves, n, y.ptr, y.ld)
-                # no tape: the backward launch walks forward again from the leaves (kept alive by the record)
-                tape.append(("eattn", L, leaves, obs, 0))
-                cur, cur_act, cur_range = y, 0, None
-                # the dense tail behind the block (LayerNorm -> Linear -> LayerNorm) as one launch per direction, like the flat
-                # encoders above; its backward also forms d loss / d (self_emb | pooled) for the block (chains that keep no tape)
-                rest = list(enc.layers[1:])
-                if (self._enc_fused and n >= 512 and rest and lnheads is None
-                        and all(isinstance(M, (ns.LayerNormSpec, ns.LinearSpec)) for M in rest)
-                        and (isinstance(rest[-1], ns.LayerNormSpec) or rest[-1].act == 0)):
-                    rec = self._fused_layers_fwd((tag, "enc", enc.key), f"{tag}enc.{enc.key}.", rest, y, n, need_dx=True)
-                    if rec is not None:
-                        tape.append(("fusedtail", rec, None, None, 0))
-                        return rec["feat"]
-            elif isinstance(L, ns.LayerNormSpec):
-                if cur is None:
-                    if obs.dtype != torch.float32:
-                        raise hip.HipError(f"vector observation `{enc.key}` must be float32, got {obs.dtype}")
-                    if obs.shape[0] != n or math.prod(obs.shape[1:]) != L.dim:
-                        raise hip.HipError(f"vector observation `{enc.key}`: sample rows of shape {tuple(obs.shape[1:])} for a "
-                                           f"network built for ({L.dim},) ({n} rows expected, {obs.shape[0]} given)")
-                    cur = Buf(obs.data_ptr(), L.dim, n, L.dim)
-                y, saved = self._ln_fwd(L, cur, tag)
-                tape.append(("ln", L, cur, saved, cur_act))
-                cur, cur_act, cur_range = y, 0, None
-            elif isinstance(L, ns.LinearSpec):
-                if cur.cols != L.in_features:  # Flatten after the convolution stack: [n*OH*OW, C] -> [n, OH*OW*C]
-                    assert cur.rows * cur.cols == n * L.in_features and cur.ld == cur.cols
-                    cur = Buf(cur.ptr, L.in_features, n, L.in_features, cur.mask)
-                y = self._linear_fwd(L, cur, tag, cur_range)
-                tape.append(("linear", L, cur, cur_range, cur_act))
-                cur, cur_act, cur_range = y, L.act, self._y_range   # (the wide-layer path measures its output's range)
-            elif isinstance(L, ns.ObsLayerNormSpec):
-                pending_obs_ln = L
-                if isinstance(obs, torch.Tensor) and (obs.dim() < 2 or obs.shape[0] != n or
-                                                      math.prod(obs.shape[1:]) != math.prod(L.shape)):
-                    # the kernels take sizes from the network's spec: a sample of another shape must not reach them
-                    raise hip.HipError(f"image observation `{enc.key}`: sample rows of shape {tuple(obs.shape[1:])} "
-                                       f"for a network built for {tuple(L.shape)} ({n} rows expected, {obs.shape[0]} given)")
-                if L.explicit:  # written out once, channels-last float32; the convolutions then see a plain activation
-                    c, h, w = L.shape
-                    is_u8 = obs.dtype == torch.uint8
-                    if not is_u8 and obs.dtype != torch.float32:
-                        raise hip.HipError(f"image observation `{enc.key}` must be uint8 or float32, got {obs.dtype}")
-                    mean = self.ws.get(f"{tag}{L.prefix}.mean", n)
-                    rstd = self.ws.get(f"{tag}{L.prefix}.rstd", n)
-                    hip.obs_ln_stats(obs.data_ptr(), is_u8, n, c * h * w, mean.data_ptr(), rstd.data_ptr())
-                    y = self._buf(f"{tag}{L.prefix}.y", n * h * w, c)
-                    hip.obs_ln_nhwc(obs.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), self._p(f"{L.prefix}.weight"),
-                                    self._p(f"{L.prefix}.bias"), n, c, h, w, y.ptr)
-                    tape.append(("obsln", L, obs, (is_u8, mean, rstd, n), 0))
-                    cur, cur_act, cur_range = y, 0, None
-            elif isinstance(L, ns.PoolSpec):
-                (h, w), (ph, pw) = L.in_hw, L.out_hw
-                assert cur.ld == L.c and cur.rows == n * h * w
-                y = self._buf(f"{tag}{L.prefix}.y", n * ph * pw, L.c)
-                hip.maxpool2_nhwc_fwd(cur.ptr, n, h, w, L.c, y.ptr)
-                tape.append(("pool", L, cur, n, cur_act))
-                cur, cur_act, cur_range = y, 0, None  # the activation's derivative is applied by the pooling backward at the winner
-            elif isinstance(L, ns.PoolNdSpec):
-                assert cur.ld == L.c and cur.rows == n * math.prod(L.in_sp)
-                y = self._buf(f"{tag}{L.prefix}.y", n * math.prod(L.out_sp), L.c)
-                hip.maxpool_ndhwc_fwd(cur.ptr, n, (*L.in_sp, L.c), L.win, y.ptr)
-                tape.append(("poolnd", L, cur, n, cur_act))
-                cur, cur_act, cur_range = y, 0, None
-            elif isinstance(L, ns.ConvNdSpec):
-                sp = L.in_sp
-                assert cur.ld == L.cin and cur.rows == n * math.prod(sp)
-                if any(L.pads):
-                    sp = tuple(d + 2 * p for d, p in zip(sp, L.pads))
-                    xp = self._buf(f"{tag}{L.prefix}.xp", n * math.prod(sp), L.cin)
-                    hip.pad_ndhwc(cur.ptr, n, (*L.in_sp, L.cin), L.pads, xp.ptr, L.pad_mode)
-                    cur = xp
-                m, kdim = n * math.prod(L.out_sp), L.cin * math.prod(L.kern)
-                P = self._buf(f"{tag}{L.prefix}.P", m, kdim)
-                hip.im2col_ndhwc(cur.ptr, n, (*sp, L.cin), L.kern, L.stride, P.ptr)
-                y = self._buf(f"{tag}{L.prefix}.y", m, L.cout)
-                hip.gemm(m, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
-                         bias=self._p(f"{L.prefix}.bias"), act=L.act)
-                tape.append(("convnd", L, cur, (P, n, sp), cur_act))
-                cur, cur_act, cur_range = y, L.act, None
-            elif isinstance(L, ns.ConvSpec):
-                oh, ow = L.out_hw
-                m = n * oh * ow
-                kdim = L.cin * L.k * L.k
-                h, w = L.in_hw
-                if L.pad:  # zero-padded copy: the implicit-GEMM gather needs no bounds logic
-                    assert not L.first and cur.ld == L.cin and cur.rows == n * h * w
-                    h, w = h + 2 * L.pad, w + 2 * L.pad
-                    xp = self._buf(f"{tag}{L.prefix}.xp", n * h * w, L.cin)
-                    if L.pad_mode:  # reflect / replicate / circular borders: the general kernel (D = 1)
-                        hip.pad_ndhwc(cur.ptr, n, (1, L.in_hw[0], L.in_hw[1], L.cin), (0, L.pad, L.pad), xp.ptr, L.pad_mode)
-                    else:
-                        hip.pad_nhwc(cur.ptr, n, L.in_hw[0], L.in_hw[1], L.cin, L.pad, xp.ptr)
-                    cur = xp
-                desc = hip.conv_desc(n, h, w, L.cin, L.k, L.k, L.stride, L.cout, L.act)
-                # implicit GEMM (no patch matrix) whenever the geometry allows; explicit im2col otherwise
-                implicit = not self.force_explicit_conv and hip.conv2d_supported(desc, L.first)
-                if L.first and L.s2d:  # strided first layer on the space-to-depth'd observation (channels-last)
-                    b = L.s2d
-                    desc = hip.conv_desc(n, h // b, w // b, L.cin * b * b, L.k // b, L.k // b, 1, L.cout, L.act)
-                    implicit = True
-                    if self.force_explicit_conv or not hip.conv2d_supported(desc, 2):
-                        raise hip.HipError("space-to-depth parameter layout needs the implicit convolution path "
-                                           "(build the policy with SRL_EXPLICIT_CONV=1 to use the fallback)")
-                y = self._buf(f"{tag}{L.prefix}.y", m, L.cout)
-                if implicit and L.act == hip.ACT_RELU and L.cout % 32 == 0:
-                    y = y._replace(mask=self.ws.get(f"{tag}{L.prefix}.mask", m * L.cout // 32, torch.int32).data_ptr())
-                P = None if implicit else self._buf(f"{tag}{L.prefix}.P", m, kdim)
-                saved = None
-                if L.first:
-                    c = pending_obs_ln.shape[0]
-                    is_u8 = obs.dtype == torch.uint8
-                    if not is_u8 and obs.dtype != torch.float32:
-                        raise hip.HipError(f"image observation `{enc.key}` must be uint8 or float32, got {obs.dtype}")
-                    gam, bet = self._p(f"{pending_obs_ln.prefix}.weight"), self._p(f"{pending_obs_ln.prefix}.bias")
-                    if staged is not None and not (implicit and L.s2d and staged.layout == ("s2d", int(L.s2d))):
-                        raise hip.HipError(f"observation `{enc.key}`: ring layout {staged.layout} does not fit this network")
-                    row_index = None
-                    if staged is not None and staged.span is None and hip.conv2d_obs_row_index_supported(desc, is_u8, True):
-                        # the byte kernels read the ring's rows in place, through the sample's slot index: no pass over
-                        # the frames besides the convolution's own
-                        src, mean, rstd, row_index = staged.in_place()
-                    elif staged is not None:
-                        # no re-tiling pass and no statistics pass: both were done once, when the rollout uploaded the row
-                        src, mean, rstd = staged.resolve(self.ws, f"{tag}{L.prefix}")
-                    else:
-                        mean = self.ws.get(f"{tag}{pending_obs_ln.prefix}.mean", n)
-                        rstd = self.ws.get(f"{tag}{pending_obs_ln.prefix}.rstd", n)
-                        src = obs
-                        if L.s2d:
-                            src = self.ws.get(f"{tag}{L.prefix}.s2d", n * c * h * w, dtype=obs.dtype)
-                            hip.obs_space_to_depth(obs.data_ptr(), is_u8, n, c, h, w, L.s2d, src.data_ptr(), mean.data_ptr(),
-                                                   rstd.data_ptr())
-                        else:
-                            hip.obs_ln_stats(obs.data_ptr(), is_u8, n, c * h * w, mean.data_ptr(), rstd.data_ptr())
-                    if (h2 is not None and implicit and is_u8 and L.s2d and n >= self.H2_MIN_ROWS
-                            and hip.conv2d_obs_row_index_supported(desc, is_u8, True)):
-                        # the whole convolution stack and the Linear behind it on pre-split activations (h2path.py)
-                        # (inference with the closing LayerNorm + heads as the consumer: the Linear's reduction may be split
-                        # over workgroups, the consumer adds the slabs)
-                        split = None
-                        if lnheads is not None and len(enc.layers) == 6 and enc.layers[4] is h2.fc:
-                            split = "infer" if self._infer else "train"
-                        y2, saved2 = h2.forward(tag, staged, obs, n, is_u8, src, mean, rstd, row_index, split_fc=split)
-                        tape.append(("h2cnn", h2, None, saved2, 0))
-                        cur, cur_act, cur_range = y2, h2.fc.act, None
-                        skip = 3
-                        continue
-                    y_range = self._act_range() if implicit else None
-                    if implicit:
-                        fws = self.ws.get(f"{L.prefix}.folded", hip.conv2d_obs_fwd_workspace(desc)).data_ptr()
-                        hip.conv2d_obs_fwd(desc, src.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), gam, bet,
-                                           self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"), y.ptr,
-                                           channels_last=bool(L.s2d), row_index=row_index, y_absmax=y_range, y_mask=y.mask,
-                                           ws_ptr=fws, reuse_folded=self._derived_fresh(f"{L.prefix}.folded:{desc.n >= 64}:{desc.n >= 32}", fws))
-                    else:
-                        hip.im2col_obs_ln(obs.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), gam, bet, n, c, h, w,
-                                          L.k, L.k, L.stride, P.ptr)
-                    saved = (src, is_u8, mean, rstd, pending_obs_ln, bool(L.s2d), row_index)
-                else:
-                    assert cur.ld == L.cin and cur.rows == n * h * w
-                    small = implicit and self._conv_small(L, desc)
-                    y_range = self._act_range() if implicit and not small else None
-                    if small:
-                        # 4 / 8 channels on both sides: a direct vector-unit kernel (csrc/conv_small.hip), not a matrix-core tile
-                        hip.conv2d_small_fwd(desc, cur.ptr, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"), y.ptr)
-                    elif implicit:
-                        w_range = self._weight_range(L.prefix, L.cout * kdim) if cur_range is not None and not L.pad else None
-                        xr = cur_range if w_range is not None else None
-                        w, pre = self._p(f"{L.prefix}.weight"), None
-                        if hip.conv2d_fwd_two_piece(desc, xr, w_range):
-                            pre = self._presplit(f"{L.prefix}.w2h", w, L.cout * kdim, w_range)
-                        hip.conv2d_nhwc_fwd(desc, cur.ptr, pre or w, self._p(f"{L.prefix}.bias"),
-                                            y.ptr, x_absmax=xr, w_absmax=w_range, y_absmax=y_range, y_mask=y.mask,
-                                            presplit=pre is not None)
-                    else:
-                        hip.im2col_nhwc(cur.ptr, n, h, w, L.cin, L.k, L.k, L.stride, P.ptr)
-                if not implicit:
-                    hip.gemm(m, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
-                             bias=self._p(f"{L.prefix}.bias"), act=L.act)
-                tape.append(("conv", L, cur, (P, saved, n, desc, cur_range), cur_act))
-                cur, cur_act, cur_range = y, L.act, y_range
-            else:  # pragma: no cover
-                raise TypeError(L)
-        return cur
+            return False
+        rec = self._fused_layers_fwd((tag, "enc", enc.key), f"{tag}enc.{enc.key}.", list(enc.layers), obs, n)
+        if rec is None:
+            return False
+        st.tape.append(Rec("fusedenc", rec, None, None, 0, rec.feat.cols))
+        st.finish(rec.feat)
+        return True
 
-    def _chain_bwd(self, records: list, dy: Buf, tag: str, need_input_grad=False) -> Optional[Buf]:
+    @_fwd(emits=("lnheads",))
+    def _fwd_lnheads(self, st, L):
+        n, tag, cur = st.n, st.tag, st.cur
+        heads, outs = st.lnheads
+        mean = self.ws.get(f"{tag}{L.prefix}.mean", n)
+        rstd = self.ws.get(f"{tag}{L.prefix}.rstd", n)
+        slabs = st.tape[-1].saved.get("fc_slabs") if (st.tape and st.tape[-1].kind == "h2cnn") else None
+        xptr, ks, stride, xb, xact, keep = slabs if slabs else (cur.ptr, 1, 0, None, 0, False)
+        # (a split product: this launch adds the slabs, the bias and the ReLU while it reads them -- and, when a backward
+        # pass follows, writes the finished rows to `cur`)
+        hip.ln_heads_fwd(xptr, cur.ld, n, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
+                         [self._p(f"{h.prefix}.weight") for h in heads], [self._p(f"{h.prefix}.bias") for h in heads],
+                         [h.out_features for h in heads], [o.data_ptr() for o in outs], [h.out_features for h in heads],
+                         mean.data_ptr(), rstd.data_ptr(), x_slabs=ks, x_slab_stride=stride, x_bias=xb, x_act=xact,
+                         x_out=cur.ptr if (slabs and not self._infer) else None, ldxo=cur.ld)
+        st.tape.append(Rec("lnheads", L, cur, LnHeadsSaved(mean, rstd, heads), st.cur_act, L.dim))
+        st.finish(None)
+
+    @_fwd(ns.InstrLstmSpec, emits=("instr",))
+    def _fwd_instr(self, st, L):
+        n, into = st.n, st.into
+        tok = self._instr_tokens(L, st.obs, n, st.enc.key)
+        # `into`: (pointer, pitch) of this encoder's columns in the trunk's concatenation buffer -- no copy follows
+        y = Buf(into[0], into[1], n, L.units) if into is not None else self._buf(f"{st.tag}{L.prefix}.y", n, L.units)
+        hip.instr_lstm_fwd(self._instr_desc(L), tok.data_ptr(), L.length, tok.dtype == torch.int32, n, y.ptr, y.ld)
+        # no tape: the backward launch walks forward again from the tokens (kept alive by the record)
+        st.tape.append(Rec("instr", L, tok, None, 0, L.units))
+        st.advance(y)
+
+    def _image_is_u8(self, st) -> bool:
+        is_u8 = st.obs.dtype == torch.uint8
+        if not is_u8 and st.obs.dtype != torch.float32:
+            raise hip.HipError(f"image observation `{st.enc.key}` must be uint8 or float32, got {st.obs.dtype}")
+        return is_u8
+
+    @_fwd(ns.ObsScaleSpec)
+    def _fwd_obs_scale(self, st, L):
+        obs, n = st.obs, st.n
+        c, h, w = L.shape
+        if not isinstance(obs, torch.Tensor) or obs.dim() < 2 or obs.shape[0] != n or math.prod(obs.shape[1:]) != c * h * w:
+            raise hip.HipError(f"image observation `{st.enc.key}`: sample rows of shape {tuple(getattr(obs, 'shape', ()))[1:]} "
+                               f"for a network built for {tuple(L.shape)} ({n} rows expected)")
+        is_u8 = self._image_is_u8(st)
+        zero, scale, one = self._scale_consts(L, n)
+        y = self._buf(f"{st.tag}{L.prefix}.y", n * h * w, c)
+        # (x - 0) * scale * 1 + 0, channels-last: the observation LayerNorm's writer with constant tables.  Not on the tape:
+        # nothing is learnt here and the frames take no gradient
+        hip.obs_ln_nhwc(obs.data_ptr(), is_u8, zero, scale, one, zero, n, c, h, w, y.ptr)
+        st.advance(y)
+
+    @_fwd(ns.EntityAttnSpec, emits=("eattn", "fusedtail"))
+    def _fwd_eattn(self, st, L):
+        enc, n, tag = st.enc, st.n, st.tag
+        leaves = self._eattn_leaves(L, st.obs, n, enc.key)
+        y = self._buf(f"{tag}{L.prefix}.eattn.y", n, 2 * L.dim)
+        hip.entity_attn_fwd(self._eattn_desc(L), *leaves, n, y.ptr, y.ld)
+        # no tape: the backward launch walks forward again from the leaves (kept alive by the record)
+        st.tape.append(Rec("eattn", L, leaves, st.obs, 0, 2 * L.dim))
+        st.advance(y)
+        # the dense tail behind the block (LayerNorm -> Linear -> LayerNorm) as one launch per direction, like the flat
+        # encoders above; its backward also forms d loss / d (self_emb | pooled) for the block (chains that keep no tape)
+        rest = list(enc.layers[1:])
+        if (self._enc_fused and n >= 512 and rest and st.lnheads is None
+                and all(isinstance(M, (ns.LayerNormSpec, ns.LinearSpec)) for M in rest)
+                and (isinstance(rest[-1], ns.LayerNormSpec) or rest[-1].act == 0)):
+            rec = self._fused_layers_fwd((tag, "enc", enc.key), f"{tag}enc.{enc.key}.", rest, y, n, need_dx=True)
+            if rec is not None:
+                st.tape.append(Rec("fusedtail", rec, None, None, 0, rec.feat.cols))
+                st.finish(rec.feat)
+
+    @_fwd(ns.LayerNormSpec, emits=("ln",))
+    def _fwd_ln(self, st, L):
+        if st.cur is None:
+            obs, n = st.obs, st.n
+            if obs.dtype != torch.float32:
+                raise hip.HipError(f"vector observation `{st.enc.key}` must be float32, got {obs.dtype}")
+            if obs.shape[0] != n or math.prod(obs.shape[1:]) != L.dim:
+                raise hip.HipError(f"vector observation `{st.enc.key}`: sample rows of shape {tuple(obs.shape[1:])} for a "
+                                   f"network built for ({L.dim},) ({n} rows expected, {obs.shape[0]} given)")
+            st.cur = Buf(obs.data_ptr(), L.dim, n, L.dim)
+        y, saved = self._ln_fwd(L, st.cur, st.tag)
+        st.tape.append(Rec("ln", L, st.cur, saved, st.cur_act, L.dim))
+        st.advance(y)
+
+    @_fwd(ns.LinearSpec, emits=("linear",))
+    def _fwd_linear(self, st, L):
+        cur = st.cur
+        if cur.cols != L.in_features:  # Flatten after the convolution stack: [n*OH*OW, C] -> [n, OH*OW*C]
+            assert cur.rows * cur.cols == st.n * L.in_features and cur.ld == cur.cols
+            cur = Buf(cur.ptr, L.in_features, st.n, L.in_features, cur.mask)
+        y, y_range = self._linear_fwd(L, cur, st.tag, st.cur_range)
+        st.tape.append(Rec("linear", L, cur, st.cur_range, st.cur_act, L.out_features))
+        st.advance(y, L.act, y_range)   # (the wide-layer path measures its output's range)
+
+    @_fwd(ns.GruSpec, emits=("gru",))
+    def _fwd_gru(self, st, L):
+        y, saved, last = self._gru_fwd(L, st.cur, st.tag)
+        st.tape.append(Rec("gru", L, st.cur, saved, st.cur_act, L.hidden))
+        self.last_state[st.tag] = last
+        st.advance(y)
+
+    @_fwd(ns.ObsLayerNormSpec, emits=("obsln",))
+    def _fwd_obs_ln(self, st, L):
+        obs, n, tag = st.obs, st.n, st.tag
+        st.pending_obs_ln = L
+        if isinstance(obs, torch.Tensor) and (obs.dim() < 2 or obs.shape[0] != n or
+                                              math.prod(obs.shape[1:]) != math.prod(L.shape)):
+            # the kernels take sizes from the network's spec: a sample of another shape must not reach them
+            raise hip.HipError(f"image observation `{st.enc.key}`: sample rows of shape {tuple(obs.shape[1:])} "
+                               f"for a network built for {tuple(L.shape)} ({n} rows expected, {obs.shape[0]} given)")
+        if L.explicit:  # written out once, channels-last float32; the convolutions then see a plain activation
+            c, h, w = L.shape
+            is_u8 = self._image_is_u8(st)
+            mean = self.ws.get(f"{tag}{L.prefix}.mean", n)
+            rstd = self.ws.get(f"{tag}{L.prefix}.rstd", n)
+            hip.obs_ln_stats(obs.data_ptr(), is_u8, n, c * h * w, mean.data_ptr(), rstd.data_ptr())
+            y = self._buf(f"{tag}{L.prefix}.y", n * h * w, c)
+            hip.obs_ln_nhwc(obs.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), self._p(f"{L.prefix}.weight"),
+                            self._p(f"{L.prefix}.bias"), n, c, h, w, y.ptr)
+            st.tape.append(Rec("obsln", L, obs, ObsLnSaved(is_u8, mean, rstd, n), 0, c))
+            st.advance(y)
+
+    @_fwd(ns.PoolSpec, emits=("pool",))
+    def _fwd_pool(self, st, L):
+        cur, n = st.cur, st.n
+        (h, w), (ph, pw) = L.in_hw, L.out_hw
+        assert cur.ld == L.c and cur.rows == n * h * w
+        y = self._buf(f"{st.tag}{L.prefix}.y", n * ph * pw, L.c)
+        hip.maxpool2_nhwc_fwd(cur.ptr, n, h, w, L.c, y.ptr)
+        st.tape.append(Rec("pool", L, cur, n, st.cur_act, L.c))
+        st.advance(y)  # the activation's derivative is applied by the pooling backward at the winner
+
+    @_fwd(ns.PoolNdSpec, emits=("poolnd",))
+    def _fwd_poolnd(self, st, L):
+        cur, n = st.cur, st.n
+        assert cur.ld == L.c and cur.rows == n * math.prod(L.in_sp)
+        y = self._buf(f"{st.tag}{L.prefix}.y", n * math.prod(L.out_sp), L.c)
+        hip.maxpool_ndhwc_fwd(cur.ptr, n, (*L.in_sp, L.c), L.win, y.ptr)
+        st.tape.append(Rec("poolnd", L, cur, n, st.cur_act, L.c))
+        st.advance(y)
+
+    @_fwd(ns.ConvNdSpec, emits=("convnd",))
+    def _fwd_convnd(self, st, L):
+        cur, n, tag = st.cur, st.n, st.tag
+        sp = L.in_sp
+        assert cur.ld == L.cin and cur.rows == n * math.prod(sp)
+        if any(L.pads):
+            sp = tuple(d + 2 * p for d, p in zip(sp, L.pads))
+            xp = self._buf(f"{tag}{L.prefix}.xp", n * math.prod(sp), L.cin)
+            hip.pad_ndhwc(cur.ptr, n, (*L.in_sp, L.cin), L.pads, xp.ptr, L.pad_mode)
+            cur = xp
+        m, kdim = n * math.prod(L.out_sp), L.cin * math.prod(L.kern)
+        P = self._buf(f"{tag}{L.prefix}.P", m, kdim)
+        hip.im2col_ndhwc(cur.ptr, n, (*sp, L.cin), L.kern, L.stride, P.ptr)
+        y = self._buf(f"{tag}{L.prefix}.y", m, L.cout)
+        hip.gemm(m, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
+                 bias=self._p(f"{L.prefix}.bias"), act=L.act)
+        st.tape.append(Rec("convnd", L, cur, ConvNdSaved(P, n, sp), st.cur_act, L.cout))
+        st.advance(y, L.act)
+
+    @_fwd(ns.ConvSpec, emits=("conv", "h2cnn"))
+    def _fwd_conv(self, st, L):
+        n, tag = st.n, st.tag
+        m, kdim = n * L.out_hw[0] * L.out_hw[1], L.cin * L.k * L.k
+        h, w = L.in_hw
+        x = st.cur
+        if L.pad:  # zero-padded copy: the implicit-GEMM gather needs no bounds logic
+            x, h, w = self._conv_pad_fwd(st, L)
+        desc = hip.conv_desc(n, h, w, L.cin, L.k, L.k, L.stride, L.cout, L.act)
+        # implicit GEMM (no patch matrix) whenever the geometry allows; explicit im2col otherwise
+        implicit = not self.force_explicit_conv and hip.conv2d_supported(desc, L.first)
+        if L.first and L.s2d:  # strided first layer on the space-to-depth'd observation (channels-last)
+            b = L.s2d
+            desc = hip.conv_desc(n, h // b, w // b, L.cin * b * b, L.k // b, L.k // b, 1, L.cout, L.act)
+            implicit = True
+            if self.force_explicit_conv or not hip.conv2d_supported(desc, 2):
+                raise hip.HipError("space-to-depth parameter layout needs the implicit convolution path "
+                                   "(build the policy with SRL_EXPLICIT_CONV=1 to use the fallback)")
+        y = self._buf(f"{tag}{L.prefix}.y", m, L.cout)
+        if implicit and L.act == hip.ACT_RELU and L.cout % 32 == 0:
+            y = y._replace(mask=self.ws.get(f"{tag}{L.prefix}.mask", m * L.cout // 32, torch.int32).data_ptr())
+        P = None if implicit else self._buf(f"{tag}{L.prefix}.P", m, kdim)
+        first, y_range = None, None
+        if L.first:
+            first = self._conv_first_source(st, L, desc, implicit, h, w)
+            if self._conv_h2_fwd(st, L, desc, implicit, first):
+                return
+            if implicit:
+                y_range = self._conv_first_fwd(L, desc, first, y)
+        else:
+            assert x.ld == L.cin and x.rows == n * h * w
+            if implicit:
+                y_range = self._conv_later_fwd(st, L, desc, x, y, kdim)
+        if not implicit:
+            self._conv_explicit_fwd(L, first, x, y, P, n, h, w, kdim)
+        st.tape.append(Rec("conv", L, x, ConvSaved(P, first, n, desc, st.cur_range), st.cur_act, L.cout))
+        st.advance(y, L.act, y_range)
+
+    def _conv_pad_fwd(self, st, L):
+        """The padded copy of `st.cur` and its extent."""
+        cur, n = st.cur, st.n
+        h, w = L.in_hw
+        assert not L.first and cur.ld == L.cin and cur.rows == n * h * w
+        h, w = h + 2 * L.pad, w + 2 * L.pad
+        xp = self._buf(f"{st.tag}{L.prefix}.xp", n * h * w, L.cin)
+        if L.pad_mode:  # reflect / replicate / circular borders: the general kernel (D = 1)
+            hip.pad_ndhwc(cur.ptr, n, (1, L.in_hw[0], L.in_hw[1], L.cin), (0, L.pad, L.pad), xp.ptr, L.pad_mode)
+        else:
+            hip.pad_nhwc(cur.ptr, n, L.in_hw[0], L.in_hw[1], L.cin, L.pad, xp.ptr)
+        return xp, h, w
+
+    def _conv_first_source(self, st, L, desc, implicit, h, w) -> "FirstConv":
+        """Where the first convolution reads the observation and its whole-image LayerNorm statistics: the ring's rows in place,
+        the ring's rows resolved into the workspace, or the sample's rows (re-tiled / measured here)."""
+        obs, n, tag, staged, ln = st.obs, st.n, st.tag, st.staged, st.pending_obs_ln
+        c = ln.shape[0]
+        is_u8 = self._image_is_u8(st)
+        if staged is not None and not (implicit and L.s2d and staged.layout == ("s2d", int(L.s2d))):
+            raise hip.HipError(f"observation `{st.enc.key}`: ring layout {staged.layout} does not fit this network")
+        row_index = None
+        if staged is not None and staged.span is None and hip.conv2d_obs_row_index_supported(desc, is_u8, True):
+            # the byte kernels read the ring's rows in place, through the sample's slot index: no pass over
+            # the frames besides the convolution's own
+            src, mean, rstd, row_index = staged.in_place()
+        elif staged is not None:
+            # no re-tiling pass and no statistics pass: both were done once, when the rollout uploaded the row
+            src, mean, rstd = staged.resolve(self.ws, f"{tag}{L.prefix}")
+        else:
+            mean = self.ws.get(f"{tag}{ln.prefix}.mean", n)
+            rstd = self.ws.get(f"{tag}{ln.prefix}.rstd", n)
+            src = obs
+            if L.s2d:
+                src = self.ws.get(f"{tag}{L.prefix}.s2d", n * c * h * w, dtype=obs.dtype)
+                hip.obs_space_to_depth(obs.data_ptr(), is_u8, n, c, h, w, L.s2d, src.data_ptr(), mean.data_ptr(),
+                                       rstd.data_ptr())
+            else:
+                hip.obs_ln_stats(obs.data_ptr(), is_u8, n, c * h * w, mean.data_ptr(), rstd.data_ptr())
+        return FirstConv(src, is_u8, mean, rstd, ln, bool(L.s2d), row_index)
+
+    def _conv_h2_fwd(self, st, L, desc, implicit, first) -> bool:
+        """The whole convolution stack and the Linear behind it on pre-split activations (h2path.py), when this encoder has
+        such a block and the pass is large enough."""
+        h2, n, enc = st.h2, st.n, st.enc
+        if not (h2 is not None and implicit and first.is_u8 and L.s2d and n >= self.H2_MIN_ROWS
+                and hip.conv2d_obs_row_index_supported(desc, first.is_u8, True)):
+            return False
+        # (inference with the closing LayerNorm + heads as the consumer: the Linear's reduction may be split
+        # over workgroups, the consumer adds the slabs)
+        split = None
+        if st.lnheads is not None and len(enc.layers) == 6 and enc.layers[4] is h2.fc:
+            split = "infer" if self._infer else "train"
+        y2, saved2 = h2.forward(st.tag, n, first, split_fc=split)
+        st.tape.append(Rec("h2cnn", h2, None, saved2, 0, h2.H))
+        st.advance(y2, h2.fc.act)
+        st.skip = 3
+        return True
+
+    def _conv_first_fwd(self, L, desc, first, y: Buf):
+        """Observation LayerNorm + first convolution as one implicit-GEMM launch; returns the output's range slot."""
+        ln = first.lnspec
+        y_range = self._act_range()
+        fws = self.ws.get(f"{L.prefix}.folded", hip.conv2d_obs_fwd_workspace(desc)).data_ptr()
+        hip.conv2d_obs_fwd(desc, first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(),
+                           self._p(f"{ln.prefix}.weight"), self._p(f"{ln.prefix}.bias"),
+                           self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"), y.ptr,
+                           channels_last=first.channels_last, row_index=first.row_index, y_absmax=y_range, y_mask=y.mask,
+                           ws_ptr=fws, reuse_folded=self._derived_fresh(f"{L.prefix}.folded:{desc.n >= 64}:{desc.n >= 32}", fws))
+        return y_range
+
+    def _conv_later_fwd(self, st, L, desc, x: Buf, y: Buf, kdim: int):
+        """A convolution on an NHWC activation without a patch matrix; returns the output's range slot (None: not tracked)."""
+        if self._conv_small(L, desc):
+            # 4 / 8 channels on both sides: a direct vector-unit kernel (csrc/conv_small.hip), not a matrix-core tile
+            hip.conv2d_small_fwd(desc, x.ptr, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"), y.ptr)
+            return None
+        y_range = self._act_range()
+        w_range = self._weight_range(L.prefix, L.cout * kdim) if st.cur_range is not None and not L.pad else None
+        xr = st.cur_range if w_range is not None else None
+        w, pre = self._p(f"{L.prefix}.weight"), None
+        if hip.conv2d_fwd_two_piece(desc, xr, w_range):
+            pre = self._presplit(f"{L.prefix}.w2h", w, L.cout * kdim, w_range)
+        hip.conv2d_nhwc_fwd(desc, x.ptr, pre or w, self._p(f"{L.prefix}.bias"),
+                            y.ptr, x_absmax=xr, w_absmax=w_range, y_absmax=y_range, y_mask=y.mask,
+                            presplit=pre is not None)
+        return y_range
+
+    def _conv_explicit_fwd(self, L, first, x: Buf, y: Buf, P: Buf, n, h, w, kdim):
+        """The fallback: patch matrix (of the layer-normed observation for the first layer) + dense GEMM."""
+        if first is not None:
+            ln = first.lnspec
+            hip.im2col_obs_ln(first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(),
+                              self._p(f"{ln.prefix}.weight"), self._p(f"{ln.prefix}.bias"), n, ln.shape[0], h, w,
+                              L.k, L.k, L.stride, P.ptr)
+        else:
+            hip.im2col_nhwc(x.ptr, n, h, w, L.cin, L.k, L.k, L.stride, P.ptr)
+        hip.gemm(P.rows, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
+                 bias=self._p(f"{L.prefix}.bias"), act=L.act)
+
+    # ------------------------------------------------------------------ one backward handler per record kind
+    # A handler `(self, rec, g, g_range, need_dx, tag, below, dv)` takes the gradient `g` w.r.t. the record's pre-activation output
+    # (`g_range`: device float bounding max |g| when its producer tracked it) and returns the gradient for the record below and
+    # its range.  `below` is that record (None at the chain's start), `dv` the second head's gradient for `lnheads`.
+    # `own_release=True`: the handler releases its parameters' buckets itself, and `_chain_bwd`'s tail is skipped.
+    BWD_HANDLERS, BWD_OWN_RELEASE = _BWD, _BWD_OWN_RELEASE
+
+    def _chain_bwd(self, records: list, dy: Buf, tag: str, need_input_grad=False, dv: Optional[Buf] = None) -> Optional[Buf]:
         """Walk tape records of one sequential chain backwards; dy is w.r.t. the chain's (pre-activation) output."""
-        g = dy
-        g_range = None  # device float bounding max |g| when its producer tracked it
+        g, g_range = dy, None
+        handlers, own_release = self.BWD_HANDLERS, self.BWD_OWN_RELEASE
         for idx in range(len(records) - 1, -1, -1):
-            kind, L, x, saved, in_act = records[idx]
-            need_dx = idx > 0 or need_input_grad
-            if kind == "ln":
-                # the layer below wants its gradient's range (a Linear whose input's range the forward pass tracked): the
-                # LayerNorm's backward folds it in while it writes dx, instead of one more pass over dx
-                below = records[idx - 1] if idx > 0 else None
-                want = need_dx and below is not None and below[0] == "linear" and below[3] is not None
-                dxr = self._grad_range() if want else None
-                g = self._ln_bwd(L, x, saved, g, in_act, need_dx, tag, dx_range=dxr)
-                g_range = dxr
-            elif kind == "linear":
-                x_range = saved  # the forward pass's range of this layer's input (a convolution's output), or None
-                if x_range is not None and g_range is None and g.ld == g.cols:
-                    g_range = self._grad_range(g)  # one pass over dz: its producer (a LayerNorm) does not track it
-                dx_range = self._grad_range() if (x_range is not None and g_range is not None and need_dx) else None
-                g = self._linear_bwd(L, x, g, in_act, need_dx, tag, x_range=x_range,
-                                     dz_range=g_range if x_range is not None else None, dx_range=dx_range)
-                g_range = dx_range
-            elif kind == "eattn":   # one launch: every parameter of the block is final behind it
-                hip.entity_attn_bwd(self._eattn_desc(L), *x, g.rows, g.ptr, g.ld)
-                self._release(L.prefixes)
-                g, g_range = None, None
+            rec = records[idx]
+            below = records[idx - 1] if idx > 0 else None
+            g, g_range = handlers[rec.kind](self, rec, g, g_range, idx > 0 or need_input_grad, tag, below, dv)
+            if rec.kind in own_release:
                 continue
-            elif kind == "instr":   # one launch: every parameter of the block is final behind it
-                d = self._instr_desc(L)
-                nbytes = hip.instr_lstm_bwd_workspace(d, g.rows)
-                wsp = self.ws.get(f"{tag}{L.prefix}.states", nbytes // 4)
-                hip.instr_lstm_bwd(d, x.data_ptr(), L.length, x.dtype == torch.int32, g.rows, g.ptr, g.ld, wsp.data_ptr(), nbytes)
-                self._release(L.prefixes)
-                g, g_range = None, None
-                continue
-            elif kind == "fusedenc":
-                self._fused_bwd(L, g.ptr, g.ld)   # (releases its layers' buckets itself)
-                g, g_range = None, None
-                continue
-            elif kind == "lnheads":   # closing LayerNorm + heads: g is d loss / d first head's output, the second head's gradient
-                # was left in self._lnheads_dv by backward()
-                mean, rstd, heads = saved
-                dys = [g] + ([self._lnheads_dv] if len(heads) > 1 else [])
-                dx = self._buf(f"{tag}{L.prefix}.dx", x.rows, L.dim)
-                # a pre-split block below wants max |dx|: tracked here while dx is written, instead of one more pass over it
-                below = records[idx - 1] if idx > 0 else None
-                amax = below[1].open_backward(below[3]) if (below is not None and below[0] == "h2cnn") else None
-                hip.ln_heads_bwd(x.ptr, x.ld, x.rows, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
-                                 mean.data_ptr(), rstd.data_ptr(), [self._p(f"{h.prefix}.weight") for h in heads],
-                                 [h.out_features for h in heads], [d.ptr for d in dys], [d.ld for d in dys], in_act, dx.ptr, dx.ld,
-                                 self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"),
-                                 [self._g(f"{h.prefix}.weight") for h in heads], [self._g(f"{h.prefix}.bias") for h in heads],
-                                 dx_absmax=amax)
-                self._release([h.prefix for h in heads] + [L.prefix])
-                g, g_range = dx, ("tracked" if amax is not None else None)
-                continue
-            elif kind == "fusedtail":   # what follows the recurrent layers, head included: g is d loss / d head output
-                g, g_range = self._fused_bwd(L, g.ptr, g.ld), None
-                continue
-            elif kind == "h2cnn":
-                L.backward(saved, g, dy_ranged=(g_range == "tracked"))
-                g, g_range = None, None
-                continue   # (the block released its layers one by one)
-            elif kind == "gru":
-                g = self._gru_bwd(L, saved, g, in_act, need_dx, tag)
-                g_range = None
-            elif kind == "obsln":
-                is_u8, mean, rstd, n = saved
-                c, h, w = L.shape
-                assert g.ld == c and g.rows == n * h * w
-                hip.obs_ln_nhwc_bwd(g.ptr, x.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), n, c, h, w,
-                                    self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"))
-                g, g_range = None, None
-            elif kind == "poolnd":
-                n = saved
-                dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(L.in_sp), L.c)
-                hip.maxpool_ndhwc_bwd(g.ptr, x.ptr, n, (*L.in_sp, L.c), L.win, in_act, dx.ptr)
-                g, g_range = dx, None
-            elif kind == "convnd":
-                P, n, sp = saved
-                m, kdim = g.rows, L.cin * math.prod(L.kern)
-                assert g.ld == L.cout and m == n * math.prod(L.out_sp)
-                self._wgrad(L.cout, kdim, m, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
-                hip.colsum(g.ptr, g.ld, m, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
-                hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)  # dP over P
-                dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(sp), L.cin)
-                hip.col2im_ndhwc(P.ptr, n, (*sp, L.cin), L.kern, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
-                if any(L.pads):
-                    dxc = self._buf(f"{tag}{L.prefix}.dxc", n * math.prod(L.in_sp), L.cin)
-                    hip.crop_ndhwc(dx.ptr, n, (*L.in_sp, L.cin), L.pads, dxc.ptr, L.pad_mode)
-                    dx = dxc
-                g, g_range = dx, None
-            elif kind == "pool":
-                n = saved
-                (h, w), (ph, pw) = L.in_hw, L.out_hw
-                assert g.ld == L.c and g.rows == n * ph * pw
-                dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.c)
-                hip.maxpool2_nhwc_bwd(g.ptr, x.ptr, n, h, w, L.c, in_act, dx.ptr)
-                g, g_range = dx, None
-            elif kind == "conv":
-                P, first_saved, n, desc, x_range = saved
-                kdim = L.cin * L.k * L.k
-                m = g.rows
-                if P is None:  # implicit-GEMM path
-                    assert g.ld == L.cout
-                    gw, gb, wp = self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"), self._p(f"{L.prefix}.weight")
-                    if L.first:
-                        obs, is_u8, mean, rstd, lnspec, chlast, row_index = first_saved
-                        blk = self._h2_blocks.get(lnspec.prefix)
-                        wsz = hip.conv2d_obs_bwd_workspace(desc)
-                        if blk is not None and blk.open:
-                            # a ragged last chunk below H2_MIN_ROWS: the executor's earlier chunks left their position sums open
-                            # in the pre-split block's workspace -- this chunk adds to them and closes (h2path.first_layer_bwd)
-                            blk.first_layer_bwd(n, (obs, is_u8, mean, rstd, row_index), g.ptr, self._grad_range(g))
-                        else:
-                            hip.conv2d_obs_bwd(desc, obs.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(),
-                                               self._p(f"{lnspec.prefix}.weight"), self._p(f"{lnspec.prefix}.bias"), wp, g.ptr,
-                                               gw, gb, self._g(f"{lnspec.prefix}.weight"), self._g(f"{lnspec.prefix}.bias"),
-                                               self.ws.get("conv_obs_bwd", wsz).data_ptr(), channels_last=chlast, row_index=row_index)
-                        g = None
-                    elif self._conv_small(L, desc):
-                        wws = self.ws.get("conv_small_wgrad", hip.conv2d_small_wgrad_workspace(desc)).data_ptr()
-                        self._on_side(lambda d=desc, xp=x.ptr, gp=g.ptr: hip.conv2d_small_wgrad(d, xp, gp, wws, gw, gb))
-                        if not need_dx:   # the chain's first record on a written-out observation (ObsScaleSpec): nobody takes dx
-                            g = None
-                            self._notify_ready(kind, L, saved)
-                            continue
-                        h, w = L.in_hw
-                        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
-                        hip.conv2d_small_dgrad(desc, g.ptr, wp, x.ptr if in_act else None, in_act, dx.ptr)
-                        g, g_range = dx, None
-                    else:
-                        wsz = hip.conv2d_wgrad_workspace(desc)
-                        if g_range is None and not L.pad and g.ld == g.cols:
-                            g_range = self._grad_range(g)
-                        two = g_range is not None and not L.pad
-                        wgrad_ws = self.ws.get("conv_wgrad", wsz).data_ptr()
-                        self._on_side(lambda d=desc, xp=x.ptr, gp=g.ptr, xr=x_range if two else None,
-                                      gr=g_range if two and x_range is not None else None: hip.conv2d_nhwc_wgrad(
-                                          d, xp, gp, gw, wgrad_ws, gb, x_absmax=xr, dz_absmax=gr))
-                        if not need_dx:   # (as above)
-                            g = None
-                            self._notify_ready(kind, L, saved)
-                            continue
-                        wt = self.ws.get(f"{L.prefix}.wt", hip.conv2d_dgrad_weight_elems(desc))
-                        if not self._derived_fresh(f"{L.prefix}.wt", wt.data_ptr()):  # once per update, not per chunk
-                            hip.conv2d_dgrad_repack(desc, wp, wt.data_ptr())
-                        h, w = L.in_hw[0] + 2 * L.pad, L.in_hw[1] + 2 * L.pad
-                        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
-                        dx_range = self._grad_range() if two else None
-                        x_mask = x.mask if in_act == hip.ACT_RELU else None  # the derivative from sign bits, not floats
-                        wr = self._weight_range(L.prefix, L.cout * kdim) if two else None
-                        wtp, pre = wt.data_ptr(), None
-                        if hip.conv2d_dgrad_two_piece(desc, g_range if two else None, wr):
-                            pre = self._presplit(f"{L.prefix}.wt2h", wtp, hip.conv2d_dgrad_weight_elems(desc), wr)
-                        hip.conv2d_nhwc_dgrad(desc, g.ptr, pre or wtp, x.ptr if in_act and x_mask is None else None, in_act,
-                                              dx.ptr, dz_absmax=g_range if two else None, w_absmax=wr,
-                                              dx_absmax=dx_range, x_mask=x_mask, presplit=pre is not None)
-                        g = self._crop(L, dx, n, tag)
-                        g_range = dx_range
-                    if g is not None and idx > 0:
-                        prev_out_cols = self._out_cols(records[idx - 1])
-                        if g.cols != prev_out_cols:
-                            g = Buf(g.ptr, prev_out_cols, g.rows * g.cols // prev_out_cols, prev_out_cols)
-                    self._notify_ready(kind, L, saved)
-                    continue
-                self._wgrad(L.cout, kdim, m, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
-                hip.colsum(g.ptr, g.ld, m, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
-                if not L.first and not need_dx:   # (as above; the patch-matrix path)
-                    g = None
-                    self._notify_ready(kind, L, saved)
-                    continue
-                # dP = dZ W, written over the patch matrix (its last reader was the weight gradient above)
-                hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)
-                if L.first:
-                    obs, is_u8, mean, rstd, lnspec, _, _ = first_saved
-                    c, h, w = lnspec.shape
-                    hip.obs_ln_affine_bwd(P.ptr, obs.data_ptr(), is_u8, mean.data_ptr(), rstd.data_ptr(), n, c, h, w, L.k,
-                                          L.k, L.stride, self._g(f"{lnspec.prefix}.weight"),
-                                          self._g(f"{lnspec.prefix}.bias"))
-                    g = None
-                else:
-                    h, w = L.in_hw[0] + 2 * L.pad, L.in_hw[1] + 2 * L.pad
-                    dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
-                    hip.col2im_nhwc(P.ptr, n, h, w, L.cin, L.k, L.k, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
-                    g, g_range = self._crop(L, dx, n, tag), None
-            self._notify_ready(kind, L, saved)
-            if g is not None and idx > 0:
+            self._notify_ready(rec)
+            if g is not None and below is not None and g.cols != below.out_cols:
                 # a Flatten between this record's input and the previous record's output: reshape the gradient
-                prev_out_cols = self._out_cols(records[idx - 1])
-                if g.cols != prev_out_cols:
-                    assert g.ld == g.cols and (g.rows * g.cols) % prev_out_cols == 0
-                    g = Buf(g.ptr, prev_out_cols, g.rows * g.cols // prev_out_cols, prev_out_cols)
+                assert g.ld == g.cols and (g.rows * g.cols) % below.out_cols == 0
+                g = Buf(g.ptr, below.out_cols, g.rows * g.cols // below.out_cols, below.out_cols)
         return g
+
+    def _notify_ready(self, rec):
+        if self.grad_ready_hook is None or rec.kind in ("pool", "poolnd"):
+            return
+        done = [rec.layer.prefix]
+        if rec.kind == "conv" and rec.saved.first is not None:
+            done.append(rec.saved.first.lnspec.prefix)  # the observation LayerNorm fused into the first convolution
+        self._release(done)
+
+    @_bwd("ln")
+    def _bwd_ln(self, rec, g, g_range, need_dx, tag, below, dv):
+        # the layer below wants its gradient's range (a Linear whose input's range the forward pass tracked): the
+        # LayerNorm's backward folds it in while it writes dx, instead of one more pass over dx
+        want = need_dx and below is not None and below.kind == "linear" and below.saved is not None
+        dxr = self._grad_range() if want else None
+        return self._ln_bwd(rec.layer, rec.x, rec.saved, g, rec.in_act, need_dx, tag, dx_range=dxr), dxr
+
+    @_bwd("linear")
+    def _bwd_linear(self, rec, g, g_range, need_dx, tag, below, dv):
+        x_range = rec.saved  # the forward pass's range of this layer's input (a convolution's output), or None
+        if x_range is not None and g_range is None and g.ld == g.cols:
+            g_range = self._grad_range(g)  # one pass over dz: its producer (a LayerNorm) does not track it
+        dx_range = self._grad_range() if (x_range is not None and g_range is not None and need_dx) else None
+        g = self._linear_bwd(rec.layer, rec.x, g, rec.in_act, need_dx, tag, x_range=x_range,
+                             dz_range=g_range if x_range is not None else None, dx_range=dx_range)
+        return g, dx_range
+
+    @_bwd("eattn", own_release=True)
+    def _bwd_eattn(self, rec, g, g_range, need_dx, tag, below, dv):   # one launch: every parameter of the block is final behind it
+        hip.entity_attn_bwd(self._eattn_desc(rec.layer), *rec.x, g.rows, g.ptr, g.ld)
+        self._release(rec.layer.prefixes)
+        return None, None
+
+    @_bwd("instr", own_release=True)
+    def _bwd_instr(self, rec, g, g_range, need_dx, tag, below, dv):   # one launch: every parameter of the block is final behind it
+        L, tok = rec.layer, rec.x
+        d = self._instr_desc(L)
+        nbytes = hip.instr_lstm_bwd_workspace(d, g.rows)
+        wsp = self.ws.get(f"{tag}{L.prefix}.states", nbytes // 4)
+        hip.instr_lstm_bwd(d, tok.data_ptr(), L.length, tok.dtype == torch.int32, g.rows, g.ptr, g.ld, wsp.data_ptr(), nbytes)
+        self._release(L.prefixes)
+        return None, None
+
+    @_bwd("fusedenc", own_release=True)
+    def _bwd_fusedenc(self, rec, g, g_range, need_dx, tag, below, dv):
+        self._fused_bwd(rec.layer, g.ptr, g.ld)   # (releases its layers' buckets itself)
+        return None, None
+
+    @_bwd("fusedtail", own_release=True)
+    def _bwd_fusedtail(self, rec, g, g_range, need_dx, tag, below, dv):
+        # what follows the recurrent layers, head included: g is d loss / d head output
+        return self._fused_bwd(rec.layer, g.ptr, g.ld), None
+
+    @_bwd("lnheads", own_release=True)
+    def _bwd_lnheads(self, rec, g, g_range, need_dx, tag, below, dv):
+        # closing LayerNorm + heads: g is d loss / d first head's output, `dv` the second head's gradient
+        L, x = rec.layer, rec.x
+        mean, rstd, heads = rec.saved
+        dys = [g] + ([dv] if len(heads) > 1 else [])
+        dx = self._buf(f"{tag}{L.prefix}.dx", x.rows, L.dim)
+        # a pre-split block below wants max |dx|: tracked here while dx is written, instead of one more pass over it
+        amax = below.layer.open_backward(below.saved) if (below is not None and below.kind == "h2cnn") else None
+        hip.ln_heads_bwd(x.ptr, x.ld, x.rows, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
+                         mean.data_ptr(), rstd.data_ptr(), [self._p(f"{h.prefix}.weight") for h in heads],
+                         [h.out_features for h in heads], [d.ptr for d in dys], [d.ld for d in dys], rec.in_act, dx.ptr, dx.ld,
+                         self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"),
+                         [self._g(f"{h.prefix}.weight") for h in heads], [self._g(f"{h.prefix}.bias") for h in heads],
+                         dx_absmax=amax)
+        self._release([h.prefix for h in heads] + [L.prefix])
+        return dx, ("tracked" if amax is not None else None)
+
+    @_bwd("h2cnn", own_release=True)
+    def _bwd_h2cnn(self, rec, g, g_range, need_dx, tag, below, dv):
+        rec.layer.backward(rec.saved, g, dy_ranged=(g_range == "tracked"))
+        return None, None   # (the block released its layers one by one)
+
+    @_bwd("gru")
+    def _bwd_gru(self, rec, g, g_range, need_dx, tag, below, dv):
+        return self._gru_bwd(rec.layer, rec.saved, g, rec.in_act, need_dx, tag), None
+
+    @_bwd("obsln")
+    def _bwd_obsln(self, rec, g, g_range, need_dx, tag, below, dv):
+        L, s = rec.layer, rec.saved
+        c, h, w = L.shape
+        assert g.ld == c and g.rows == s.n * h * w
+        hip.obs_ln_nhwc_bwd(g.ptr, rec.x.data_ptr(), s.is_u8, s.mean.data_ptr(), s.rstd.data_ptr(), s.n, c, h, w,
+                            self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"))
+        return None, None
+
+    @_bwd("poolnd")
+    def _bwd_poolnd(self, rec, g, g_range, need_dx, tag, below, dv):
+        L, n = rec.layer, rec.saved
+        dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(L.in_sp), L.c)
+        hip.maxpool_ndhwc_bwd(g.ptr, rec.x.ptr, n, (*L.in_sp, L.c), L.win, rec.in_act, dx.ptr)
+        return dx, None
+
+    @_bwd("pool")
+    def _bwd_pool(self, rec, g, g_range, need_dx, tag, below, dv):
+        L, n = rec.layer, rec.saved
+        (h, w), (ph, pw) = L.in_hw, L.out_hw
+        assert g.ld == L.c and g.rows == n * ph * pw
+        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.c)
+        hip.maxpool2_nhwc_bwd(g.ptr, rec.x.ptr, n, h, w, L.c, rec.in_act, dx.ptr)
+        return dx, None
+
+    @_bwd("convnd")
+    def _bwd_convnd(self, rec, g, g_range, need_dx, tag, below, dv):
+        L, x, in_act = rec.layer, rec.x, rec.in_act
+        P, n, sp = rec.saved
+        m, kdim = g.rows, L.cin * math.prod(L.kern)
+        assert g.ld == L.cout and m == n * math.prod(L.out_sp)
+        self._wgrad(L.cout, kdim, m, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
+        hip.colsum(g.ptr, g.ld, m, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
+        hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)  # dP over P
+        dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(sp), L.cin)
+        hip.col2im_ndhwc(P.ptr, n, (*sp, L.cin), L.kern, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
+        if any(L.pads):
+            dxc = self._buf(f"{tag}{L.prefix}.dxc", n * math.prod(L.in_sp), L.cin)
+            hip.crop_ndhwc(dx.ptr, n, (*L.in_sp, L.cin), L.pads, dxc.ptr, L.pad_mode)
+            dx = dxc
+        return dx, None
+
+    @_bwd("conv")
+    def _bwd_conv(self, rec, g, g_range, need_dx, tag, below, dv):
+        """Four variants, as the forward pass chose: first layer on the observation (one launch), small direct kernels, implicit
+        matrix-core kernels, explicit patch matrix.  The last three are a weight-gradient half and a data-gradient half."""
+        L, s = rec.layer, rec.saved
+        assert s.P is not None or g.ld == L.cout
+        if s.P is not None:
+            wgrad, dgrad = self._conv_explicit_wgrad, self._conv_explicit_dgrad
+        elif L.first:
+            return self._conv_first_bwd(rec, g)
+        elif self._conv_small(L, s.desc):
+            wgrad, dgrad = self._conv_small_wgrad, self._conv_small_dgrad
+        else:
+            wgrad, dgrad = self._conv_implicit_wgrad, self._conv_implicit_dgrad
+        g_range = wgrad(rec, g, g_range)
+        if not (need_dx or L.first):   # the chain's first record on a written-out observation (ObsScaleSpec): nobody takes dx
+            return None, None
+        return dgrad(rec, g, g_range, tag)
+
+    def _conv_first_bwd(self, rec, g):
+        L, desc = rec.layer, rec.saved.desc
+        first, n = rec.saved.first, rec.saved.n
+        ln = first.lnspec
+        blk = self._h2_blocks.get(ln.prefix)
+        wsz = hip.conv2d_obs_bwd_workspace(desc)
+        if blk is not None and blk.open:
+            # a ragged last chunk below H2_MIN_ROWS: the executor's earlier chunks left their position sums open
+            # in the pre-split block's workspace -- this chunk adds to them and closes (h2path.first_layer_bwd)
+            blk.first_layer_bwd(n, first, g.ptr, self._grad_range(g))
+        else:
+            hip.conv2d_obs_bwd(desc, first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(),
+                               self._p(f"{ln.prefix}.weight"), self._p(f"{ln.prefix}.bias"), self._p(f"{L.prefix}.weight"), g.ptr,
+                               self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"),
+                               self._g(f"{ln.prefix}.weight"), self._g(f"{ln.prefix}.bias"),
+                               self.ws.get("conv_obs_bwd", wsz).data_ptr(), channels_last=first.channels_last,
+                               row_index=first.row_index)
+        return None, None
+
+    def _conv_small_wgrad(self, rec, g, g_range):
+        L, desc = rec.layer, rec.saved.desc
+        gw, gb = self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias")
+        wws = self.ws.get("conv_small_wgrad", hip.conv2d_small_wgrad_workspace(desc)).data_ptr()
+        self._on_side(lambda d=desc, xp=rec.x.ptr, gp=g.ptr: hip.conv2d_small_wgrad(d, xp, gp, wws, gw, gb))
+        return g_range
+
+    def _conv_small_dgrad(self, rec, g, g_range, tag):
+        L, x, in_act = rec.layer, rec.x, rec.in_act
+        h, w = L.in_hw
+        dx = self._buf(f"{tag}{L.prefix}.dx", rec.saved.n * h * w, L.cin)
+        hip.conv2d_small_dgrad(rec.saved.desc, g.ptr, self._p(f"{L.prefix}.weight"), x.ptr if in_act else None, in_act, dx.ptr)
+        return dx, None
+
+    def _conv_implicit_wgrad(self, rec, g, g_range):
+        """Returns g's range: measured here (one pass) when its producer did not track it and the two-piece products can use it."""
+        L, desc, x_range = rec.layer, rec.saved.desc, rec.saved.x_range
+        gw, gb = self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias")
+        wsz = hip.conv2d_wgrad_workspace(desc)
+        if g_range is None and not L.pad and g.ld == g.cols:
+            g_range = self._grad_range(g)
+        two = g_range is not None and not L.pad
+        wgrad_ws = self.ws.get("conv_wgrad", wsz).data_ptr()
+        self._on_side(lambda d=desc, xp=rec.x.ptr, gp=g.ptr, xr=x_range if two else None,
+                      gr=g_range if two and x_range is not None else None: hip.conv2d_nhwc_wgrad(
+                          d, xp, gp, gw, wgrad_ws, gb, x_absmax=xr, dz_absmax=gr))
+        return g_range
+
+    def _conv_implicit_dgrad(self, rec, g, g_range, tag):
+        L, x, in_act, desc, n = rec.layer, rec.x, rec.in_act, rec.saved.desc, rec.saved.n
+        kdim = L.cin * L.k * L.k
+        two = g_range is not None and not L.pad
+        wt = self.ws.get(f"{L.prefix}.wt", hip.conv2d_dgrad_weight_elems(desc))
+        if not self._derived_fresh(f"{L.prefix}.wt", wt.data_ptr()):  # once per update, not per chunk
+            hip.conv2d_dgrad_repack(desc, self._p(f"{L.prefix}.weight"), wt.data_ptr())
+        h, w = L.in_hw[0] + 2 * L.pad, L.in_hw[1] + 2 * L.pad
+        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
+        dx_range = self._grad_range() if two else None
+        x_mask = x.mask if in_act == hip.ACT_RELU else None  # the derivative from sign bits, not floats
+        wr = self._weight_range(L.prefix, L.cout * kdim) if two else None
+        wtp, pre = wt.data_ptr(), None
+        if hip.conv2d_dgrad_two_piece(desc, g_range if two else None, wr):
+            pre = self._presplit(f"{L.prefix}.wt2h", wtp, hip.conv2d_dgrad_weight_elems(desc), wr)
+        hip.conv2d_nhwc_dgrad(desc, g.ptr, pre or wtp, x.ptr if in_act and x_mask is None else None, in_act,
+                              dx.ptr, dz_absmax=g_range if two else None, w_absmax=wr,
+                              dx_absmax=dx_range, x_mask=x_mask, presplit=pre is not None)
+        return self._crop(L, dx, n, tag), dx_range
+
+    def _conv_explicit_wgrad(self, rec, g, g_range):
+        L, P = rec.layer, rec.saved.P
+        kdim = L.cin * L.k * L.k
+        self._wgrad(L.cout, kdim, g.rows, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
+        hip.colsum(g.ptr, g.ld, g.rows, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
+        return g_range
+
+    def _conv_explicit_dgrad(self, rec, g, g_range, tag):
+        L, x, in_act = rec.layer, rec.x, rec.in_act
+        P, first, n = rec.saved.P, rec.saved.first, rec.saved.n
+        m, kdim = g.rows, L.cin * L.k * L.k
+        # dP = dZ W, written over the patch matrix (its last reader was the weight gradient above)
+        hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)
+        if L.first:
+            ln = first.lnspec
+            c, h, w = ln.shape
+            hip.obs_ln_affine_bwd(P.ptr, first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(), n, c, h, w,
+                                  L.k, L.k, L.stride, self._g(f"{ln.prefix}.weight"), self._g(f"{ln.prefix}.bias"))
+            return None, None
+        h, w = L.in_hw[0] + 2 * L.pad, L.in_hw[1] + 2 * L.pad
+        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
+        hip.col2im_nhwc(P.ptr, n, h, w, L.cin, L.k, L.k, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
+        return self._crop(L, dx, n, tag), None
 
     def _crop(self, L, dx: Buf, n: int, tag: str) -> Buf:
         """Gradient of a zero-padded input: drop the border."""
@@ -1271,39 +1542,6 @@ class HipNet:
             hip.crop_nhwc(dx.ptr, n, h, w, L.cin, L.pad, out.ptr)
         return out
 
-    def _notify_ready(self, kind, L, saved):
-        if self.grad_ready_hook is None or kind in ("pool", "poolnd"):
-            return
-        done = [L.prefix]
-        if kind == "conv" and L.first and saved[1] is not None:
-            done.append(saved[1][4].prefix)  # the observation LayerNorm fused into the first convolution
-        self._release(done)
-
-    @staticmethod
-    def _out_cols(record):
-        kind, L = record[0], record[1]
-        if kind == "ln":
-            return L.dim
-        if kind == "h2cnn":
-            return L.H
-        if kind in ("fusedenc", "fusedtail"):
-            return L["feat"].cols
-        if kind == "lnheads":
-            return L.dim
-        if kind == "eattn":
-            return 2 * L.dim
-        if kind == "instr":
-            return L.units
-        if kind == "linear":
-            return L.out_features
-        if kind == "gru":
-            return L.hidden
-        if kind in ("pool", "poolnd"):
-            return L.c
-        if kind == "obsln":
-            return L.shape[0]
-        return L.cout
-
     def _lnheads_ok(self, encoders, backbone, heads, n) -> bool:
         """The encoder's closing LayerNorm and the heads right behind it (no backbone layers between) as one launch."""
         if backbone or len(encoders) != 1 or n > self.encoder_rows or not heads or n < 64:
@@ -1316,7 +1554,7 @@ class HipNet:
     def _trunk_fwd(self, tag, encoders, backbone, obs: Dict[str, torch.Tensor], n: int, head=None, head_out=None, lnheads=None):
         """``head`` / ``head_out``: the head behind this trunk and the tensor its output goes to -- when the layers that follow the
         last recurrent layer are LayerNorm / Linear no wider than 64, they and the head run as ONE launch per direction
-        (`fusedtail`; the tape's last field says whether the head went in)."""
+        (`fusedtail`; the tape's `head_in` says whether the head went in)."""
         for enc in encoders:
             for key in self._enc_keys(enc):
                 if key not in obs:
@@ -1345,8 +1583,8 @@ class HipNet:
                 tapes.append(tape)
                 col += enc.out_dim
             enc_tapes.append(tapes)
-            if lnheads is not None and tapes[0] and tapes[0][-1][0] == "lnheads":   # (one piece, one encoder: _lnheads_ok)
-                return None, 0, (enc_tapes, [], widths, pieces, "lnheads")
+            if lnheads is not None and tapes[0] and tapes[0][-1].kind == "lnheads":   # (one piece, one encoder: _lnheads_ok)
+                return None, 0, TrunkTape(enc_tapes, [], widths, pieces, "lnheads")
             if len(pieces) == 1 and len(outs) == 1:
                 feat = outs[0]
                 break
@@ -1358,34 +1596,24 @@ class HipNet:
                     hip.copy2d(o.ptr, o.ld, feat.ptr + 4 * (r0 * width + col), width, r1 - r0, o.cols)
                 col += o.cols
         bb_tape = []
-        cur, cur_act = feat, 0
+        st = _Walk(None, n, tag, bb_tape, cur=feat, track=False)
         last_rnn = max((i for i, L in enumerate(backbone) if isinstance(L, ns.GruSpec)), default=-1)
+        handlers = self.FWD_HANDLERS
         for li, L in enumerate(backbone):
             if (head is not None and li == last_rnn + 1 and last_rnn >= 0 and self._enc_fused and n >= 512
-                    and cur_act == 0 and all(isinstance(M, (ns.LayerNormSpec, ns.LinearSpec)) for M in backbone[li:])):
-                rec = self._fused_layers_fwd((tag, "tail"), f"{tag}tail.", list(backbone[li:]) + [head], cur, n, out=head_out, head=True,
+                    and st.cur_act == 0 and all(isinstance(M, (ns.LayerNormSpec, ns.LinearSpec)) for M in backbone[li:])):
+                rec = self._fused_layers_fwd((tag, "tail"), f"{tag}tail.", list(backbone[li:]) + [head], st.cur, n, out=head_out, head=True,
                                              need_dx=True)
                 if rec is not None:
-                    bb_tape.append(("fusedtail", rec, None, None, 0))
-                    return rec["feat"], 0, (enc_tapes, bb_tape, widths, pieces, True)
-            if isinstance(L, ns.LinearSpec):
-                y = self._linear_fwd(L, cur, tag)
-                bb_tape.append(("linear", L, cur, None, cur_act))
-                cur, cur_act = y, L.act
-            elif isinstance(L, ns.GruSpec):
-                y, saved, last = self._gru_fwd(L, cur, tag)
-                bb_tape.append(("gru", L, cur, saved, cur_act))
-                self.last_state[tag] = last
-                cur, cur_act = y, 0
-            else:
-                y, saved = self._ln_fwd(L, cur, tag)
-                bb_tape.append(("ln", L, cur, saved, cur_act))
-                cur, cur_act = y, 0
-        return cur, cur_act, (enc_tapes, bb_tape, widths, pieces, False)
+                    bb_tape.append(Rec("fusedtail", rec, None, None, 0, rec.feat.cols))
+                    return rec.feat, 0, TrunkTape(enc_tapes, bb_tape, widths, pieces, True)
+            handlers[type(L)](self, st, L)   # Linear, LayerNorm, recurrent layers
+        return st.cur, st.cur_act, TrunkTape(enc_tapes, bb_tape, widths, pieces, False)
 
-    def _trunk_bwd(self, tag, trunk_tape, dfeat: Buf):
-        enc_tapes, bb_tape, widths, pieces, _ = trunk_tape
-        g = self._chain_bwd(bb_tape, dfeat, tag, need_input_grad=True) if bb_tape else dfeat
+    def _trunk_bwd(self, tag, trunk_tape: TrunkTape, dfeat: Buf, dv: Optional[Buf] = None):
+        """``dv``: the second head's gradient for an encoder that closes in `lnheads` with both heads."""
+        enc_tapes, widths, pieces = trunk_tape.enc_tapes, trunk_tape.widths, trunk_tape.pieces
+        g = self._chain_bwd(trunk_tape.bb_tape, dfeat, tag, need_input_grad=True) if trunk_tape.bb_tape else dfeat
         hook = self.grad_ready_hook
         for pi, (r0, r1) in enumerate(pieces):
             # encoder gradients accumulate over the pieces: they are final (and may be reduced) after the last one
@@ -1393,7 +1621,7 @@ class HipNet:
             col = 0
             for tape, wdt in zip(enc_tapes[pi], widths):
                 sub = Buf(g.ptr + 4 * (r0 * g.ld + col), g.ld, r1 - r0, wdt)
-                self._chain_bwd(tape, sub, tag, need_input_grad=False)
+                self._chain_bwd(tape, sub, tag, need_input_grad=False, dv=dv)
                 col += wdt
             if len(pieces) > 1:
                 self._join_side()  # the pieces share their backward buffers: the next one must not overtake this one's
@@ -1541,27 +1769,18 @@ class HipNet:
         tape = self.ws.get(f"{tag}mlp.tape", n * tld) if taped else None
         y = out if out is not None else self.ws.get(f"{tag}mlp.y", n * width)
         hip.mlp_fwd(arr, xptr, xcols, n, tape.data_ptr() if tape is not None else 0, tld, y.data_ptr(), width)
-        return dict(arr=arr, x=x, xptr=xptr, xcols=xcols, tape=tape, tld=tld, n=n, feat=Buf(y.data_ptr(), width, n, width), act=act,
-                    head=head, prefixes=[L.prefix for L in layers], need_dx=need_dx, tag=tag)
+        return FusedChain(arr=arr, x=x, xptr=xptr, xcols=xcols, tape=tape, tld=tld, n=n, feat=Buf(y.data_ptr(), width, n, width), act=act,
+                          head_in=bool(head), prefixes=[L.prefix for L in layers], need_dx=need_dx, tag=tag)
 
-    def _fused_bwd(self, rec, dy_ptr: int, lddy: int) -> Optional[Buf]:
+    def _fused_bwd(self, rec: FusedChain, dy_ptr: int, lddy: int) -> Optional[Buf]:
         dx = None
-        if rec["need_dx"]:
-            dx = self._buf(f"{rec['tag']}mlp.dx", rec["n"], rec["xcols"])
-            hip.mlp_bwd_dx(rec["arr"], rec["xptr"], rec["xcols"], rec["n"], dy_ptr, lddy, dx.ptr, dx.ld)
+        if rec.need_dx:
+            dx = self._buf(f"{rec.tag}mlp.dx", rec.n, rec.xcols)
+            hip.mlp_bwd_dx(rec.arr, rec.xptr, rec.xcols, rec.n, dy_ptr, lddy, dx.ptr, dx.ld)
         else:
-            hip.mlp_bwd(rec["arr"], rec["xptr"], rec["xcols"], rec["n"], rec["tape"].data_ptr() if rec["tape"] is not None else 0,
-                        rec["tld"], dy_ptr, lddy)
-        self._release(rec["prefixes"])  # one launch: every layer of the chain is final behind it
+            hip.mlp_bwd(rec.arr, rec.xptr, rec.xcols, rec.n, rec.tape.data_ptr() if rec.tape is not None else 0, rec.tld, dy_ptr, lddy)
+        self._release(rec.prefixes)  # one launch: every layer of the chain is final behind it
         return dx
-
-    @staticmethod
-    def _head_in(tape):
-        """Whether the tower's head ran inside its trunk's last launch: a fused chain, a trunk ending in a `fusedtail` (True), or
-        an encoder closing in `lnheads` ("lnheads": with a shared backbone BOTH heads ran there).  Falsy otherwise."""
-        if isinstance(tape, dict):
-            return bool(tape["head"])
-        return tape[4] if (tape is not None and len(tape) > 4) else False
 
     # ------------------------------------------------------------------ public: forward / backward
     def forward(self, obs: Dict[str, torch.Tensor], n: int, keep_tape: bool = True, rnn: Optional[RnnCtx] = None):
@@ -1606,7 +1825,7 @@ class HipNet:
         fa = self._fused_fwd("a:", sp.obs_encoders, sp.actor_backbone, sp.actor_head if heads_in else None, obs, n,
                              out=logits_t if heads_in else None)
         if fa is not None:
-            a_feat, a_act, a_tape = fa["feat"], fa["act"], fa
+            a_feat, a_act, a_tape = fa.feat, fa.act, fa
         else:
             lnh = None
             if sp.std_type != "shared_learnable" and sp.aux_head is None and not sp.num_rnn_layers:
@@ -1621,17 +1840,18 @@ class HipNet:
             fc = self._fused_fwd("c:", sp.state_encoders, sp.critic_backbone, sp.critic_head if heads_in else None, obs, n,
                                  out=value_t if heads_in else None)
             if fc is not None:
-                c_feat, c_act, c_tape = fc["feat"], fc["act"], fc
+                c_feat, c_act, c_tape = fc.feat, fc.act, fc
             else:
                 lnh = None
                 if sp.aux_head is None and not sp.num_rnn_layers and self._lnheads_ok(sp.state_encoders, sp.critic_backbone, [sp.critic_head], n):
                     lnh = ([sp.critic_head], [value_t])
                 c_feat, c_act, c_tape = self._trunk_fwd("c:", sp.state_encoders, sp.critic_backbone, obs, n,
                                                         head=sp.critic_head if heads_in else None, head_out=value_t, lnheads=lnh)
-        if not self._head_in(a_tape):
+        # (`head_in` of a tower's tape: its head ran inside the trunk's last launch; a shared backbone has no critic tape)
+        if not a_tape.head_in:
             hip.gemm(n, atot, sp.hidden_dim, a_feat.ptr, a_feat.ld, 0, self._p(f"{sp.actor_head.prefix}.weight"), sp.hidden_dim, 0,
                      logits_t.data_ptr(), atot, bias=self._p(f"{sp.actor_head.prefix}.bias"))
-        if not self._head_in(c_tape) and not (sp.shared_backbone and self._head_in(a_tape) == "lnheads"):
+        if not (c_tape is not None and c_tape.head_in) and not (sp.shared_backbone and a_tape.head_in == "lnheads"):
             hip.gemm(n, sp.value_dim, sp.hidden_dim, c_feat.ptr, c_feat.ld, 0, self._p(f"{sp.critic_head.prefix}.weight"),
                      sp.hidden_dim, 0, value_t.data_ptr(), sp.value_dim, bias=self._p(f"{sp.critic_head.prefix}.bias"))
         self.log_std_rows = None
@@ -1646,7 +1866,7 @@ class HipNet:
             hip.gemm(n, sp.value_dim, sp.hidden_dim, a_feat.ptr, a_feat.ld, 0, self._p(f"{sp.aux_head.prefix}.weight"), sp.hidden_dim, 0,
                      aux_t.data_ptr(), sp.value_dim, bias=self._p(f"{sp.aux_head.prefix}.bias"))
             self.aux_value = aux_t[:n * sp.value_dim].view(n, sp.value_dim)
-        self._tape = (n, a_feat, a_act, a_tape, c_feat, c_act, c_tape, cm, rnn) if keep_tape else None
+        self._tape = PassTape(n, a_feat, a_act, a_tape, c_feat, c_act, c_tape, cm, rnn) if keep_tape else None
         if cm:  # the heads' outputs back into time-major order
             hip.chunk_rows(logits_t.data_ptr(), logits_out.data_ptr(), rnn.T, rnn.B, rnn.C, atot, inverse=True)
             hip.chunk_rows(value_t.data_ptr(), value_out.data_ptr(), rnn.T, rnn.B, rnn.C, sp.value_dim, inverse=True)
@@ -1665,7 +1885,9 @@ class HipNet:
         # (row order and time structure travel with the tape.  They do NOT make an interleaved pass safe: a forward(keep_tape=False)
         # between a taped forward and this call drops the tape -- the branch above raises -- and would have overwritten the shared
         # workspace buffers the tape points at (logits, value, a_feat, mlp.y); inference beside training uses an executor of its own)
-        n, a_feat, a_act, a_tape, c_feat, c_act, c_tape, self._cm, self._rnn = self._tape
+        t = self._tape
+        n, a_feat, a_act, a_tape, c_feat, c_act, c_tape = t.n, t.a_feat, t.a_act, t.a_tape, t.c_feat, t.c_act, t.c_tape
+        self._cm, self._rnn = t.cm, t.rnn
         atot = sum(sp.act_dims)
         dl = Buf(d_logits.data_ptr(), atot, n, atot)
         dv = Buf(d_value.data_ptr(), sp.value_dim, n, sp.value_dim)
@@ -1675,7 +1897,7 @@ class HipNet:
             hip.chunk_rows(dl.ptr, dlc.ptr, rnn.T, rnn.B, rnn.C, atot)
             hip.chunk_rows(dv.ptr, dvc.ptr, rnn.T, rnn.B, rnn.C, sp.value_dim)
             dl, dv = dlc, dvc
-        a_head_in, c_head_in = self._head_in(a_tape), self._head_in(c_tape)
+        a_head_in, c_head_in = a_tape.head_in, c_tape is not None and c_tape.head_in
         da = None if a_head_in else self._linear_bwd(sp.actor_head, a_feat, dl, a_act, True, "a:")
         if sp.std_type == "shared_learnable":
             dls = Buf(d_log_std_rows.data_ptr(), atot, n, atot)
@@ -1690,15 +1912,15 @@ class HipNet:
         if sp.shared_backbone and not a_head_in:
             self._release([sp.actor_head.prefix])
 
-        def trunk_bwd(tag, tape, dfeat, dhead):  # fused chains: one launch, all of its layers released behind it
-            if isinstance(tape, dict):
-                self._fused_bwd(tape, dhead.ptr if tape["head"] else dfeat.ptr, dhead.ld if tape["head"] else dfeat.ld)
-            else:  # (a trunk whose last record took the head in starts from the head's gradient)
-                self._trunk_bwd(tag, tape, dhead if tape[4] else dfeat)
+        def trunk_bwd(tag, tape, dfeat, dhead, dv=None):
+            g = dhead if tape.head_in else dfeat   # (a trunk whose last launch took the head in starts from the head's gradient)
+            if isinstance(tape, FusedChain):   # one launch, all of its layers released behind it
+                self._fused_bwd(tape, g.ptr, g.ld)
+            else:
+                self._trunk_bwd(tag, tape, g, dv)
 
         if sp.shared_backbone and a_head_in == "lnheads":   # both heads' gradients go into the closing launch
-            self._lnheads_dv = dv
-            trunk_bwd("a:", a_tape, da, dl)
+            trunk_bwd("a:", a_tape, da, dl, dv)
         elif sp.shared_backbone:
             self._linear_bwd(sp.critic_head, c_feat, dv, c_act, True, "a:", dx_into=da, dx_accumulate=True)
             self._release([sp.critic_head.prefix])

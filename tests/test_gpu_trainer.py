@@ -235,6 +235,43 @@ def test_step_matches_reference_golden(tag, golden):
     assert res.step == trainer.policy.version
 
 
+@pytest.mark.parametrize("tag,encoder_rows", [
+    ("c1", None),       # fused MLP chains (32 x 8 rows)
+    ("cshr", None),     # shared backbone plus `log_std`
+    ("cnn", None),      # 4 x 3 rows, below H2_MIN_ROWS: layer-by-layer implicit convolutions, first-layer fused obs-LN
+    ("cnnpool", None),  # pool plus a second vector encoder, separate towers
+    ("padm", None),     # padding modes, two encoders, explicit obs scale / LN
+    ("cnn3d", None),    # ConvNd
+    ("gru2", None),     # two recurrent layers, separate towers
+    ("cnnpad", 13),     # several encoder pieces: the hook only on the last
+])
+def test_backward_releases_every_parameter_exactly_once(tag, encoder_rows):
+    """Data parallel reduces a gradient bucket when `grad_ready_hook` names its parameters' prefixes: over one forward(keep_tape=True)
+    and one backward() (through `analyze` / `backward_ppo`, which builds the recurrent context as training does) every prefix
+    that owns a parameter is released exactly once, and nothing else is."""
+    pargs, targs, skw, _, _ = CASES[tag]
+    policy = make_trainer(pargs, targs).policy
+    net = policy.net
+    if encoder_rows is not None:
+        net.encoder_rows = encoder_rows
+    released = []
+    net.grad_ready_hook = lambda prefixes: released.append(tuple(prefixes))
+    arrays = synthetic.make_sample_arrays(seed=100, **skw)
+    sample = synthetic.to_sample_batch(arrays)
+    ar = policy.analyze(sample[:arrays["on_reset"].shape[0] - 1], target="ppo")
+    n = ar.new_action_log_probs.numel()
+    assert encoder_rows is None or n > encoder_rows   # (more than one piece)
+    rng = torch.Generator().manual_seed(0)
+    d = lambda *shape: torch.randn(*shape, generator=rng).to(policy.device)
+    policy.backward_ppo(d(n), d(n, net.spec.value_dim), d(n))
+    torch.cuda.synchronize()
+    net.grad_ready_hook = None
+    got = sorted(p for prefixes in released for p in prefixes)
+    owners = sorted({name.rsplit(".", 1)[0] for name in net.spec.params})
+    print(tag, "released:", released)
+    assert got == owners, (tag, sorted(set(owners) - set(got)), sorted(p for p in set(got) if got.count(p) > 1 or p not in owners))
+
+
 def test_rescaled_head_is_served_fresh():
     """`policy.update_popart` with the rescale active rewrites the head inside the flat parameter buffer.  What the policy serves
     afterwards -- `analyze` and `rollout`, both of which ran before on the same observations, so whatever they derive from the

@@ -326,3 +326,24 @@ def test_environment_switches_match_the_documented_table():
         documented |= set(re.findall(r"SRL_[A-Z0-9_]+", ln.split("|")[1]))
     assert read == documented, (sorted(read - documented), sorted(documented - read))
     assert read <= ENV_SWITCHES and len(read) <= len(ENV_SWITCHES), sorted(read - ENV_SWITCHES)
+
+
+def test_every_layer_kind_has_its_forward_and_backward_handler():
+    """The executor picks a forward handler by spec class and a backward handler by record kind (hipnet.HipNet.FWD_HANDLERS /
+    BWD_HANDLERS).  Every layer descriptor of netspec -- its dataclasses that carry a parameter `prefix`; the containers
+    (EncoderSpec, NetSpec, ParamInfo) carry none -- has a forward handler, every record kind a forward handler declares has a
+    backward handler, and the kinds that release their own gradient buckets are kinds that exist."""
+    import dataclasses
+    import inspect
+    from srl_amd.algorithm.hipnet import HipNet
+    layer_specs = [c for _, c in inspect.getmembers(ns, inspect.isclass)
+                   if c.__module__ == ns.__name__ and dataclasses.is_dataclass(c) and hasattr(c, "__dataclass_fields__")
+                   and ("prefix" in c.__dataclass_fields__ or hasattr(c, "prefix"))]
+    assert {ns.LinearSpec, ns.LayerNormSpec, ns.GruSpec, ns.ConvSpec, ns.InstrLstmSpec} <= set(layer_specs) and len(layer_specs) >= 11
+    assert not {ns.EncoderSpec, ns.NetSpec, ns.ParamInfo} & set(layer_specs)
+    missing = [c.__name__ for c in layer_specs if c not in HipNet.FWD_HANDLERS]
+    assert not missing, f"no forward handler for {missing}"
+    assert set(HipNet.FWD_HANDLERS) <= set(layer_specs)
+    assert HipNet.FWD_KINDS and set(HipNet.FWD_KINDS) <= set(HipNet.BWD_HANDLERS), set(HipNet.FWD_KINDS) - set(HipNet.BWD_HANDLERS)
+    assert set(HipNet.BWD_OWN_RELEASE) <= set(HipNet.BWD_HANDLERS)
+    assert all(callable(f) for f in list(HipNet.FWD_HANDLERS.values()) + list(HipNet.BWD_HANDLERS.values()))
