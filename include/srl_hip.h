@@ -266,6 +266,8 @@ int srl_categorical_bwd(void* stream, const float* logits, int ld_logits, const 
                         const float* d_logp, const float* d_entropy, float* d_logits, int ld_dlogits);
 /* Rollout: action = argmax if is_eval[row] else inverse-CDF sample with Philox4x32-10
  * (key = seed, counter = {row0 + row, head, offset}); logp [n] = sum over heads of log p(action).
+ * The counter's four 32-bit words are {low, high word of row0 + row; head; LOW word of offset} and the key's
+ * {low, high word of seed}: only the low 32 bits of offset enter, so offsets 2^32 apart repeat the stream.
  * action_out int64 [n, n_heads] (dtype of actor_critic_policy.py:515).  row0: as for srl_gaussian_sample. */
 int srl_categorical_sample(void* stream, const float* logits, int ld_logits, const uint8_t* avail,
                            const uint8_t* is_eval, long n, int n_heads, const int32_t* host_head_dims,
