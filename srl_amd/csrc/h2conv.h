@@ -775,173 +775,240 @@ __global__ __launch_bounds__(512, 2) void h2wgrad_kernel(H2WgradArgs a) {
     }
     dvoff[qd] = off;
   }
+  auto issue_one = [&](uint32_t sox, uint32_t soz, int s, int qd) {
+    const int j = wid + 8 * qd;
+    const uint32_t ldsa = __builtin_amdgcn_readfirstlane(lds0 + s * SLOT + j * 1024);
+    if (dvoff[qd] >= 0) {
+      if (j < NDX) asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(ldsa), "v"(dvoff[qd]), "s"(rx), "s"(sox) : "memory");
+      else asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(ldsa), "v"(dvoff[qd]), "s"(rz), "s"(soz) : "memory");
+    }
+  };
   auto issue = [&](long img, int s) {
     const uint32_t sox = __builtin_amdgcn_readfirstlane((uint32_t)(img * (long)XIMGB));
     const uint32_t soz = __builtin_amdgcn_readfirstlane((uint32_t)(img * (long)ZIMGB));
 #pragma unroll
-    for (int qd = 0; qd < NDW; ++qd) {
-      const int j = wid + 8 * qd;
-      const uint32_t ldsa = __builtin_amdgcn_readfirstlane(lds0 + s * SLOT + j * 1024);
-      if (dvoff[qd] >= 0) {
-        if (j < NDX) asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(ldsa), "v"(dvoff[qd]), "s"(rx), "s"(sox) : "memory");
-        else asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(ldsa), "v"(dvoff[qd]), "s"(rz), "s"(soz) : "memory");
-      }
-    }
+    for (int qd = 0; qd < NDW; ++qd) issue_one(sox, soz, s, qd);
   };
 
   // ---- operand addresses of this lane inside a slot.  A transposed read: lane 4 q + p of octet o names position 4 o + q
   // (first read; + 16: second) and the 8 bytes of channels 4 p .. 4 p + 3 of a 16-channel block c16: group 2 (p & 1) + (c16 & 1),
-  // elements 4 (p >> 1) .. of its entry.
+  // elements 4 (p >> 1) .. of its entry.  Every address is ONE lane register (+ the slot) plus an immediate: what depends on
+  // the lane is split off here, once per launch; what depends on the chunk, the tap and the channel block is a constant of
+  // the wavefront's instantiation (below).
   auto zplane = [&](int cb32, int g, int pl) { return h2w_plane_base((cb32 * 4 + g) * 2 + pl, ZPLANE); };
-  auto xplane = [&](int cb32, int g, int pl) { return h2w_plane_base((cb32 * 4 + g) * 2 + pl, XPLANE); };
   const int ent = 4 * o + q, half8 = 8 * (p >> 1);
   // cout blocks of this wavefront
   const int mc0 = GE::MC == 4 ? 0 : (wid & 1) * 2;
-  const int nn0 = GE::MC == 4 ? wid * GE::NN : (wid >> 1) * GE::NN;   // first (tap, cin block) pair
   uint32_t za[GE::MC];   // piece 0, chunk 0, read 0
 #pragma unroll
   for (int m = 0; m < GE::MC; ++m) {
     const int cbk = mc0 + m;
     za[m] = (uint32_t)(XB_AL + zplane(cbk >> 1, 2 * (p & 1) + (cbk & 1), 0) + ent * 16 + half8);
   }
-  // x: per cin block c16x of the pair (pair index nn -> tap = nn / (CIN/16), c16x = nn % (CIN/16))
   constexpr int CPB = GE::CIN / 16;
-  uint32_t swz_lo = 0, swz_hi = 0;
-  if (GE::X_ROWS) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = (ent + u) & 7;
-      const uint32_t t = (uint32_t)((((k >> 1) & 1) | (((k >> 2) & 1) << 2)) * 16);
-      if (u < 4) swz_lo |= t << (8 * u);
-      else swz_hi |= t << (8 * (u - 4));
-    }
-  }
+  // planar x (conv3): groups 2, 3 (p & 1) lie a constant distance behind groups 0, 1 in every block and piece
+  constexpr int XG2 = 4 * XPLANE + 128;
+  static_assert(h2w_plane_base(4, XPLANE) - h2w_plane_base(0, XPLANE) == XG2 && h2w_plane_base(7, XPLANE) - h2w_plane_base(3, XPLANE) == XG2 &&
+                    h2w_plane_base(12, XPLANE) - h2w_plane_base(8, XPLANE) == XG2 && h2w_plane_base(15, XPLANE) - h2w_plane_base(11, XPLANE) == XG2,
+                "x planes: lane part");
+  const uint32_t xl_planar = (uint32_t)((p & 1) * XG2 + ent * 16 + half8);
 
-  h2_f32x4 acc[GE::MC][GE::NN];
-#pragma unroll
-  for (int m = 0; m < GE::MC; ++m)
-#pragma unroll
-    for (int n2 = 0; n2 < GE::NN; ++n2) acc[m][n2] = h2_f32x4{0.f, 0.f, 0.f, 0.f};
-  // bias gradient: D[cout i][any column] of the products with ones -- lane l, register r: cout 4 (l >> 4) + r of the block.
-  // conv2, wavefronts 0..3: block wid in [0]; conv3, wavefronts 0, 1: their two blocks
-  h2_f32x4 dbacc[2] = {h2_f32x4{0.f, 0.f, 0.f, 0.f}, h2_f32x4{0.f, 0.f, 0.f, 0.f}};
   h2_f16x8 ones;
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = (_Float16)1.0f;
 
-  auto frag = [&](const uint8_t* p0, const uint8_t* p1) {
-    union { h2_s16x4 s[2]; h2_f16x8 v; } f;
-    f.s[0] = h2_tr_read(p0);
-    f.s[1] = h2_tr_read(p1);
-    return f.v;
-  };
-  auto compute = [&](int s) {
-    const uint8_t* slot = lds + s * SLOT;
-#pragma unroll
-    for (int c = 0; c < NCHUNK; ++c) {
-      h2_f16x8 af[GE::MC][2];
-#pragma unroll
-      for (int m = 0; m < GE::MC; ++m)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-          const uint8_t* b = slot + za[m] + pl * ZPLANE + c * 512;
-          af[m][pl] = frag(b, b + 256);
-        }
-      // bias gradient from the fragments a wavefront holds anyway: both pieces against a fragment of ones on the matrix cores
-      // (two MFMAs per cout block and chunk).  As 16 conversions + 16 additions per piece pair on the vector unit it made the
-      // two (conv3) / four (conv2) wavefronts that own the sums ~ 20-30 % longer than the others, which wait for them at every
-      // image's barrier -- and vector time is not hidden under matrix time here.
-      {
-        const bool mine = GE::MC == 4 ? wid < 4 : wid < 2;
-        if (mine) {
-#pragma unroll
-          for (int m = 0; m < GE::MC; ++m) {
-            if (GE::MC == 4 && m != (wid & 3)) continue;
-            h2_f32x4& d = dbacc[GE::MC == 4 ? 0 : (m & 1)];
-            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][0], ones, d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][1], ones, d, 0, 0, 0);
-          }
-        }
-      }
-#pragma unroll
-      for (int n2 = 0; n2 < GE::NN; ++n2) {
-        const int nn = nn0 + n2;   // wavefront-uniform at run time for conv3 (nn0 runtime) -> addresses computed, not immediates
-        const int tap = nn / CPB, c16x = nn - tap * CPB;
-        h2_f16x8 xf[2];
-        if (GE::X_ROWS) {
-          // tap_u needs a compile-time tap for the table index: conv2 has nn0 = 4 wid -> tap = 2 wid + (n2 >> 1): runtime.
-          // U mod 8 at run time: table byte selected with a shift
-          const int U = GE::tap_u(tap);
-          const int P0 = c * 32 + U;   // + ent (+16)
-          const uint32_t u8 = (uint32_t)(U & 7);
-          const uint32_t x = (uint32_t)(((((uint64_t)swz_hi << 32) | swz_lo) >> (8 * u8)) & 0xffu);
-          const uint32_t g0 = (uint32_t)((2 * (2 * (p & 1) + c16x)) * 16);
-#pragma unroll
-          for (int pl = 0; pl < 2; ++pl) {
-            const uint32_t a0 = (uint32_t)((P0 + ent) * 128) + ((g0 + pl * 16) ^ x) + half8;
-            const uint32_t a1 = (uint32_t)((P0 + ent + 16) * 128) + ((g0 + pl * 16) ^ x) + half8;   // + 16 pixels: same low bits
-            xf[pl] = frag(slot + a0, slot + a1);
-          }
-        } else {
-          const int U = GE::tap_u(tap);
-          const int cb32 = c16x >> 1;
-#pragma unroll
-          for (int pl = 0; pl < 2; ++pl) {
-            const uint32_t a0 = (uint32_t)(xplane(cb32, 2 * (p & 1) + (c16x & 1), pl) + (c * 32 + U + ent) * 16 + half8);
-            xf[pl] = frag(slot + a0, slot + a0 + 256);
-          }
-        }
-#pragma unroll
-        for (int m = 0; m < GE::MC; ++m) {
-          acc[m][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][1], xf[0], acc[m][n2], 0, 0, 0);
-          acc[m][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][0], xf[1], acc[m][n2], 0, 0, 0);
-          acc[m][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][0], xf[0], acc[m][n2], 0, 0, 0);
-        }
-      }
-    }
-  };
-
   long img = blockIdx.x;
+  const long gstep = gridDim.x;   // read once: behind the loop's asm statements it would be loaded again per image
 #pragma unroll
   for (int s = 0; s < NSLOT - 1; ++s)
-    if (img + (long)s * gridDim.x < a.n) issue(img + (long)s * gridDim.x, s);
-  int s_cur = 0, s_nxt = NSLOT - 1;
-  for (; img < a.n; img += gridDim.x) {
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const long in = img + (long)(NSLOT - 1) * gridDim.x;
-    if (in < a.n) issue(in, s_nxt);
-    compute(s_cur);
-    s_cur = s_cur + 1 == NSLOT ? 0 : s_cur + 1;
-    s_nxt = s_nxt + 1 == NSLOT ? 0 : s_nxt + 1;
-  }
+    if (img + (long)s * gstep < a.n) issue(img + (long)s * gstep, s);
 
-  // ---- slab of this workgroup: dW[cout][tap][cin] (cout = 16 block + 4 (lane >> 4) + r, cin = 16 c16x + (lane & 15)), then db
-  const float inv = 1.f / (*a.sx * *a.sz);
-  float* slab = a.slabs + (size_t)blockIdx.x * (64 * K + 64);
+  // ---- the image loop and the slab, once per pair group G of the wavefront (conv2: G = wid, taps 2 G, 2 G + 1; conv3:
+  // G = wid >> 1, pairs 9 G ..): a wavefront-uniform branch per LAUNCH picks the instantiation, which owns its accumulators
+  // from the first image to the stores -- no accumulator ever meets another instantiation's in a phi node.  With G a constant
+  // the tap, the channel block, the swizzle byte of a conv2 tap and whether the wavefront owns bias sums are constants too.
+  auto run = [&](auto g_c) {
+    constexpr int G = decltype(g_c)::value;
+    constexpr int nn0 = G * GE::NN;                          // first (tap, cin block) pair
+    constexpr bool MINE = GE::MC == 4 ? G < 4 : G < 1;       // bias sums: conv2 wavefronts 0..3 (block wid), conv3 wavefronts 0, 1 (their two blocks)
+    constexpr int NP = NCHUNK * GE::NN;                      // (chunk, pair) steps of an image
+    // x lane parts.  conv2 (swizzled rows): pixel P0 + ent, slot (group, piece) ^ sigma(P): sigma touches byte-address bits 4
+    // (piece) and 6 (p & 1) only and depends on (ent + U) & 7 -- one register per tap of the wavefront and piece
+    uint32_t xl[2][2];
 #pragma unroll
-  for (int m = 0; m < GE::MC; ++m)
+    for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-    for (int n2 = 0; n2 < GE::NN; ++n2) {
-      const int nn = nn0 + n2, tap = nn / CPB, c16x = nn - tap * CPB;
+      for (int pl = 0; pl < 2; ++pl) {
+        if (GE::X_ROWS) {
+          const int k = (ent + (GE::tap_u(nn0 / CPB + t2) & 7)) & 7;
+          const uint32_t sg = (uint32_t)((((k >> 1) & 1) | (((k >> 2) & 1) << 2)) * 16);
+          xl[t2][pl] = (uint32_t)(ent * 128 + half8) + (((uint32_t)(64 * (p & 1) + 16 * pl)) ^ sg);
+        } else {
+          xl[t2][pl] = xl_planar;
+        }
+      }
+
+    h2_f32x4 acc[GE::MC][GE::NN];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int cout = 16 * (mc0 + m) + 4 * (lane >> 4) + r;
-        slab[(size_t)cout * K + tap * GE::CIN + c16x * 16 + (lane & 15)] = acc[m][n2][r] * inv;
+    for (int m = 0; m < GE::MC; ++m)
+#pragma unroll
+      for (int n2 = 0; n2 < GE::NN; ++n2) acc[m][n2] = h2_f32x4{0.f, 0.f, 0.f, 0.f};
+    // bias gradient: D[cout i][any column] of the products with ones -- lane l, register r: cout 4 (l >> 4) + r of the block.
+    h2_f32x4 dbacc[2] = {h2_f32x4{0.f, 0.f, 0.f, 0.f}, h2_f32x4{0.f, 0.f, 0.f, 0.f}};
+
+    union Frag { h2_s16x4 s[2]; h2_f16x8 v; };
+    // One image.  The (chunk, pair) steps are software-pipelined by hand: while the 3 MC MFMAs of step k issue, the four
+    // transposed reads of step k + 1's x fragments go out one per MFMA gap into the other of two fragment sets, and in a
+    // chunk's last step every dz fragment is re-read for the next chunk into its own registers right behind its last use
+    // (piece 1 behind the first product of its cout block, piece 0 behind the third).  Source order is pinned
+    // (sched_barrier): the interleave below is the schedule.  Before: the dz fragments as a burst at the top of a chunk, the
+    // x fragments wherever the compiler put them, a third of the wavefront cycles waiting.  Per accumulator the MFMA
+    // sequence (operands, order) is what it was: results are bit-identical.  An image starts with a burst (nothing of it
+    // may be read before its barrier) and ends without reads.
+    // The next image's DMA instructions (NDW per wavefront, one block): wavefronts 4..7 issue theirs at the top of the image,
+    // wavefronts 0..3 behind their 48th MFMA -- the two wavefronts of a SIMD (w, w + 4) then do not both stand in the DMA
+    // path's queue while the matrix pipe idles.  Anywhere between an image's barrier and the next one's vmcnt(0) is the same to
+    // the slot protocol.  Measured (16 384 images, conv2 / conv3, with the slab sum): all at the top 269 / 184 us, 0..3 late
+    // 254 / 176, 4..7 late 260 / 185 (behind MFMA 24: 259 / 179, 72: 268 / 191, 96: 273 / 197), one instruction per 6
+    // MFMAs 264 / 180.
+    constexpr int DMA_AT = (GE::MC == 4 ? G >= 4 : G >= 2) ? -1 : 48;
+    static_assert(DMA_AT < NP * 3 * GE::MC, "the DMA block has a gap");
+    auto image = [&](int s, bool dma, long in, int sn) {
+      const uint8_t* slot = lds + s * SLOT;
+      const uint32_t sox = __builtin_amdgcn_readfirstlane((uint32_t)(in * (long)XIMGB));
+      const uint32_t soz = __builtin_amdgcn_readfirstlane((uint32_t)(in * (long)ZIMGB));
+      auto dma_block = [&]() {
+        if (dma) {
+#pragma unroll
+          for (int qd = 0; qd < NDW; ++qd) issue_one(sox, soz, sn, qd);
+        }
+      };
+      if (DMA_AT < 0) dma_block();
+      const uint8_t* zb[GE::MC];
+#pragma unroll
+      for (int m = 0; m < GE::MC; ++m) zb[m] = slot + za[m];
+      const uint8_t* xb[2][2];
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) xb[t2][pl] = slot + xl[t2][pl];
+      Frag af[GE::MC][2], xf[2][2];
+      auto rd_z = [&](int c, int m, int pl, int h) { af[m][pl].s[h] = h2_tr_read(zb[m] + pl * ZPLANE + c * 512 + h * 256); };
+      // read h of piece pl of step k's x fragment (pair index nn -> tap = nn / (CIN/16), c16x = nn % (CIN/16))
+      auto rd_x = [&](int k, int pl, int h) {
+        const int c = k / GE::NN, n2 = k - c * GE::NN;
+        const int nn = nn0 + n2, tap = nn / CPB, c16x = nn - tap * CPB;
+        const int U = GE::tap_u(tap);
+        if constexpr (GE::X_ROWS) xf[k & 1][pl].s[h] = h2_tr_read(xb[tap - nn0 / CPB][pl] + (c * 32 + U + 16 * h) * 128 + 32 * c16x);   // + 16 pixels: same low bits
+        else xf[k & 1][pl].s[h] = h2_tr_read(xb[0][0] + h2w_plane_base(((c16x >> 1) * 4 + (c16x & 1)) * 2 + pl, XPLANE) + (c * 32 + U) * 16 + h * 256);
+      };
+      // the burst, in the order of first use
+      rd_x(0, 0, 0); rd_x(0, 0, 1);
+      rd_z(0, 0, 1, 0); rd_z(0, 0, 1, 1);
+      rd_x(0, 1, 0); rd_x(0, 1, 1);
+      rd_z(0, 0, 0, 0); rd_z(0, 0, 0, 1);
+#pragma unroll
+      for (int m = 1; m < GE::MC; ++m) { rd_z(0, m, 1, 0); rd_z(0, m, 1, 1); rd_z(0, m, 0, 0); rd_z(0, m, 0, 1); }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        const int c = k / GE::NN, n2 = k - c * GE::NN, b = k & 1;
+        // bias gradient from the fragments a wavefront holds anyway: both pieces against a fragment of ones on the matrix cores
+        // (two MFMAs per cout block and chunk).  As 16 conversions + 16 additions per piece pair on the vector unit it made the
+        // two (conv3) / four (conv2) wavefronts that own the sums ~ 20-30 % longer than the others, which wait for them at every
+        // image's barrier -- and vector time is not hidden under matrix time here.
+        if (MINE && n2 == 0) {
+#pragma unroll
+          for (int m = 0; m < GE::MC; ++m) {
+            if (GE::MC == 4 && m != (G & 3)) continue;
+            h2_f32x4& d = dbacc[GE::MC == 4 ? 0 : (m & 1)];
+            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][0].v, ones, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][1].v, ones, d, 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        const bool more = k + 1 < NP;                          // step k + 1's x fragments: one read per gap
+        const bool turn = n2 == GE::NN - 1 && c + 1 < NCHUNK;  // the chunk's last step: dz fragments of chunk c + 1
+        constexpr int XGAP = GE::MC / 2;                       // gaps 0, 1, 2, 3 (conv3: 6 MFMAs a step) / 0, 2, 4, 6 (conv2: 12)
+#pragma unroll
+        for (int m = 0; m < GE::MC; ++m)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const int g = 3 * m + j;
+            if (j == 0) acc[m][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][1].v, xf[b][0].v, acc[m][n2], 0, 0, 0);
+            else if (j == 1) acc[m][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][0].v, xf[b][1].v, acc[m][n2], 0, 0, 0);
+            else acc[m][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m][0].v, xf[b][0].v, acc[m][n2], 0, 0, 0);
+            if (more && g % XGAP == 0 && g / XGAP < 4) rd_x(k + 1, (g / XGAP) >> 1, (g / XGAP) & 1);
+            if (turn) {
+              if (j == 0) rd_z(c + 1, m, 1, 0);
+              else if (j == 1) rd_z(c + 1, m, 1, 1);
+              else { rd_z(c + 1, m, 0, 0); rd_z(c + 1, m, 0, 1); }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (k * 3 * GE::MC + g == DMA_AT) {
+              dma_block();
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+      }
+    };
+
+    int s_cur = 0, s_nxt = NSLOT - 1;
+    for (; img < a.n; img += gstep) {
+      asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      const long in = img + (long)(NSLOT - 1) * gstep;
+      image(s_cur, in < a.n, in, s_nxt);
+      s_cur = s_cur + 1 == NSLOT ? 0 : s_cur + 1;
+      s_nxt = s_nxt + 1 == NSLOT ? 0 : s_nxt + 1;
+    }
+
+    // ---- slab of this workgroup: dW[cout][tap][cin] (cout = 16 block + 4 (lane >> 4) + r, cin = 16 c16x + (lane & 15)), then db
+    const float inv = 1.f / (*a.sx * *a.sz);
+    float* slab = a.slabs + (size_t)blockIdx.x * (64 * K + 64);
+#pragma unroll
+    for (int m = 0; m < GE::MC; ++m)
+#pragma unroll
+      for (int n2 = 0; n2 < GE::NN; ++n2) {
+        const int nn = nn0 + n2, tap = nn / CPB, c16x = nn - tap * CPB;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int cout = 16 * (mc0 + m) + 4 * (lane >> 4) + r;
+          slab[(size_t)cout * K + tap * GE::CIN + c16x * 16 + (lane & 15)] = acc[m][n2][r] * inv;
+        }
+      }
+    if (MINE) {
+      // db: cout i = lane (< 16) of the block sits in register i & 3 of the lanes 16 (i >> 2) .. + 15 (every column the same sum)
+#pragma unroll
+      for (int m = 0; m < (GE::MC == 4 ? 1 : 2); ++m) {
+        float t = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = __shfl(dbacc[m][r], 16 * ((lane & 15) >> 2));
+          if ((lane & 3) == r) t = v;
+        }
+        if (lane < 16) slab[64 * K + 16 * (GE::MC == 4 ? G : mc0 + m) + lane] = t / *a.sz;
       }
     }
-  {
-    // db: cout i = lane (< 16) of the block sits in register i & 3 of the lanes 16 (i >> 2) .. + 15 (every column the same sum)
-    const bool mine = GE::MC == 4 ? wid < 4 : wid < 2;
-#pragma unroll
-    for (int m = 0; m < (GE::MC == 4 ? 1 : 2); ++m) {
-      float t = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = __shfl(dbacc[m][r], 16 * ((lane & 15) >> 2));
-        if ((lane & 3) == r) t = v;
-      }
-      if (mine && lane < 16) slab[64 * K + 16 * (GE::MC == 4 ? wid : mc0 + m) + lane] = t / *a.sz;
+  };
+  const int grp = GE::MC == 4 ? wid : wid >> 1;
+  if (GE::MC == 4) {
+    switch (grp) {
+      case 0: run(std::integral_constant<int, 0>{}); break;
+      case 1: run(std::integral_constant<int, 1>{}); break;
+      case 2: run(std::integral_constant<int, 2>{}); break;
+      case 3: run(std::integral_constant<int, 3>{}); break;
+      case 4: run(std::integral_constant<int, 4>{}); break;
+      case 5: run(std::integral_constant<int, 5>{}); break;
+      case 6: run(std::integral_constant<int, 6>{}); break;
+      default: run(std::integral_constant<int, 7>{}); break;
+    }
+  } else {
+    switch (grp) {
+      case 0: run(std::integral_constant<int, 0>{}); break;
+      case 1: run(std::integral_constant<int, 1>{}); break;
+      case 2: run(std::integral_constant<int, 2>{}); break;
+      default: run(std::integral_constant<int, 3>{}); break;
     }
   }
 }
