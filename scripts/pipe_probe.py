@@ -20,7 +20,7 @@ for pipes in (1, 2, 2, 2, 2):
         ex = net  # three chunks: the last one (2) ran on the policy's own executor in both modes
         cur = {k: ex.ws._bufs[k].clone() for k in ("logits", "value", "new_logp", "entropy", "d_logp", "d_value", "d_logits", "a:obs_modules_dict.obs.1._Convolution__model.0.y", "a:obs_modules_dict.obs.1._Convolution__model.2.y", "a:obs_modules_dict.obs.1._Convolution__model.4.y", "a:obs_modules_dict.obs.1._Convolution__model.7.0.y", "a:obs_modules_dict.obs.1._Convolution__model.7.2.y")}
         cur["act_absmax"] = ex.ws._bufs["act_absmax"][:4].clone()
-        cur["wamax"] = net._wamax[:4].clone()
+        cur["wamax"] = net.shared.wamax[:4].clone()
         cur["terms"] = net.ws._bufs["mappo.out"][:44].clone()
         if "ref" not in globals():
             ref = cur

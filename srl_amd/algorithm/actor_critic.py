@@ -101,7 +101,7 @@ class PendingRollout:
             self._done.synchronize()
             h_action, h_logp, h_value = [v.numpy().copy() for v in self._views]
         finally:
-            pol._net._serving[0] -= 1
+            pol._net.end_serving()
             pol._pending_rollout = False
         refs = self._refs
         analyzed = PPORolloutAnalyzedResult(log_probs=h_logp, value=h_value, obs_ref=None if refs is None else refs.reshape(self._n, 1))
@@ -329,11 +329,11 @@ class ActorCriticPolicy(policy_api.Policy):
         hip.require_gpu()
         if self.__dict__.get("_pending_rollout"):
             raise RuntimeError("rollout_async: the previous call's result() has not been taken (one call in flight per policy)")
-        self._net._serving[0] += 1   # what the executor derives from the parameters survives from one request batch to the next
+        self._net.begin_serving()   # what the executor derives from the parameters survives from one request batch to the next
         try:
             pend = self._rollout(requests, **kwargs)
         except BaseException:
-            self._net._serving[0] -= 1
+            self._net.end_serving()
             raise
         self._pending_rollout = True
         return pend

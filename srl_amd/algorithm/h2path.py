@@ -133,7 +133,7 @@ class H2Cnn:
                                       net._p(f"{self.c1.prefix}.weight"), net._p(f"{self.c1.prefix}.bias"), fws):
                 net._derived_done(fws)
             else:
-                net._derived.pop(fws, None)
+                net._derived_forget(fws)
 
     # ------------------------------------------------------------------ forward
     # Inference batches: the Linear's 3136-long reduction split over FC_SPLITK workgroups per tile -- the rows alone leave most CUs
@@ -273,7 +273,7 @@ class H2Cnn:
         desc1 = hip.conv_desc(n, 21, 21, 64, 2, 2, 1, 32, hip.ACT_RELU)
         wsz = hip.conv2d_obs_bwd_workspace(desc1)
         phase = 3
-        defer = net._in_update[0] and net.last_chunk is not None and os.environ.get("SRL_OBS_BWD_DEFER", "1")[:1] != "0"
+        defer = net.in_update and net.last_chunk is not None and os.environ.get("SRL_OBS_BWD_DEFER", "1")[:1] != "0"
         if self.open or (defer and n >= 4096):
             assert net.last_chunk is not None, "an open first-layer accumulation outside the trainer's chunk loop"
             phase = (0 if self.open else 1) | (2 if net.last_chunk else 0)

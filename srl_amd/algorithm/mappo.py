@@ -759,21 +759,18 @@ class MultiAgentPPO(PytorchTrainer):
                 # the weight-range slots are shared: they are recomputed here, before the fork.  Before the very first
                 # forward pass the layers that want one are not known yet: the other pipelines then start after the first
                 # chunk, which discovers and fills them
-                first_sync = not net._wamax_slot
-                net.refresh_weight_ranges()
+                first_sync = not net.refresh_weight_ranges()
                 if stats_work is not None:  # the global advantage statistics: needed by every pipeline
                     stats_work.join() if stats_work is self._comm else stats_work.wait()
                     stats_work = None
                 for twin, pst in zip(self._twin, self._pipe_stream):
-                    twin.flat, twin.popart_state = net.flat, net.popart_state  # (re-bound by a checkpoint load)
                     twin.zero_grad()
                     pst.wait_stream(streams[0])
                     nets.append(twin)
                     streams.append(pst)
             if reducer is not None:
                 reducer.begin([x.grad for x in nets])
-            net.chunks_of_one_update(True)
-            net._multi[0] = len(nets) > 1
+            net.chunks_of_one_update(True, pipelines=len(nets))
             for x in nets:
                 x.reset_open_accumulations()  # (an accumulation a failed update left open is not continued)
             for ci in range(nchunks):
@@ -819,7 +816,6 @@ class MultiAgentPPO(PytorchTrainer):
                     for pst in streams[1:]:
                         pst.wait_stream(streams[0])
             net.chunks_of_one_update(False)
-            net._multi[0] = False
             for x in nets:
                 x.last_chunk = None
             if two and reducer is None:

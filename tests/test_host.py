@@ -284,6 +284,84 @@ def test_executor_host_logic_of_round_3():
     assert not net._derived_fresh("w", 2000) and not twin._derived_fresh("w", 3000)
 
 
+def _net_and_twins():
+    from srl_amd.algorithm import hipnet
+    spec, _ = ns.build_netspec(obs_dim=4, action_dim=2, hidden_dim=8, num_dense_layers=1, num_rnn_layers=0, popart=True,
+                               layernorm=False, shared_backbone=False, seed=1)
+    net = hipnet.HipNet(spec, "cpu")
+    return net, [net.twin(), net.twin()]
+
+
+def test_twins_own_their_state_and_share_one_param_state():
+    """An executor and its twins hold ONE `ParamState` (parameters, PopArt statistics, the weight-only workspace of the first
+    executor); every other container, workspace or tensor of an executor is its own object."""
+    from srl_amd.algorithm.hipnet import Workspace
+    net, twins = _net_and_twins()
+    shared_names = {"shared", "spec", "flat", "popart_state", "wws"}
+    for twin in twins + [twins[0].twin()]:   # the last one: an executor made from a twin
+        assert twin.shared is net.shared and twin.wws is net.ws and twin.ws is not net.ws
+        assert twin.flat.data_ptr() == net.flat.data_ptr() and twin.popart_state.data_ptr() == net.popart_state.data_ptr()
+        assert net.popart_state.numel() == 3 and twin.grad.data_ptr() != net.grad.data_ptr()
+        assert vars(twin).keys() == vars(net).keys()
+        for name, mine in vars(net).items():
+            if isinstance(mine, (dict, list, set, Workspace, torch.Tensor)):
+                assert (vars(twin)[name] is mine) == (name in shared_names), name
+    assert net.shared.has_twins
+
+
+def test_weight_range_slots_are_one_table_for_all_executors():
+    """The host half of `_weight_range` (no launch: the refill is the caller's callback): slots and staleness live in the shared
+    state, whichever executor allocates, invalidates or refills them."""
+    net, (twin, _) = _net_and_twins()
+    filled = []
+    assert twin._weight_slot("a", filled.append) == 0 and net._weight_slot("b", filled.append) == 1
+    assert net._weight_slot("a", filled.append) == 0 and filled == [0, 1]     # the twin's slot, already filled: no refill
+    net.params_changed()
+    assert net.shared.wamax_stale == twin.shared.wamax_stale == {"a", "b"}
+    assert twin._weight_slot("b", filled.append) == 1 and filled == [0, 1, 1]  # refilled through the twin ...
+    assert net._weight_slot("b", filled.append) == 1 and filled == [0, 1, 1]   # ... is current for the first executor
+    assert net._weight_slot("a", filled.append) == 0 and filled == [0, 1, 1, 0]
+    assert not net.shared.wamax_stale and net.refresh_weight_ranges() == 2
+    for i in range(2, 256):
+        assert twin._weight_slot(f"p{i}", filled.append) == i
+    assert net._weight_slot("p256", filled.append) is None and twin._weight_slot("p256", filled.append) is None   # the 257th
+    assert len(filled) == 258 and len(net.shared.wamax_slot) == 256 and not net.shared.wamax_stale
+
+
+def test_update_and_serving_windows_are_seen_by_every_executor():
+    net, (twin, _) = _net_and_twins()
+    net.begin_serving()
+    net.begin_serving()
+    assert not net._derived_fresh("w", 1000) and twin._derived_fresh("w", 1000)
+    net.end_serving()
+    assert net._derived_fresh("w", 1000)                  # still serving: kept
+    net.end_serving()
+    assert not net._derived_fresh("w", 1000) and net.shared.serving == 0
+    assert not net.in_update and not twin.in_update and net._presplit("k", 1024, 64, 0) is None
+    net.chunks_of_one_update(True, pipelines=2)
+    assert net.in_update and twin.in_update and twin.shared.multi
+    assert net._presplit("k", 1024 + 4, 64, 0) is None and net._presplit("k", 1024, 63, 0) is None   # unaligned
+    assert not net._derived_fresh("w", 1000) and net._derived_fresh("w", 1000)
+    net._derived_forget(1000)
+    assert not twin._derived_fresh("w", 1000)
+    net.last_chunk = True
+    net.chunks_of_one_update(False)
+    assert not twin.in_update and not net.shared.multi and net.last_chunk is None
+    net.chunks_of_one_update(True)
+    assert net.in_update and not net.shared.multi      # (one pipeline: the trainers that never fork do not say how many)
+    net.chunks_of_one_update(False)
+
+
+def test_param_state_keeps_no_executor_alive():
+    import gc
+    import weakref
+    net, twins = _net_and_twins()
+    shared, first = net.shared, weakref.ref(net)
+    del net, twins
+    gc.collect()
+    assert first() is None and shared.wws is not None
+
+
 def test_host_side_queries_of_the_fused_kernels():
     """The planning queries the Python side makes before a launch are host code (no GPU): which (chain, rows) pairs keep no
     tape (srl_mlp_tape_floats_at -- the matrix-core chains walk forward again in their backward pass) and which LayerNorm + heads
