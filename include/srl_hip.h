@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SRL_HIP_ABI_VERSION 20
+#define SRL_HIP_ABI_VERSION 21
 
 int srl_abi_version(void);
 const char* srl_last_error(void);
@@ -299,6 +299,36 @@ int srl_ppg_aux_loss_fwd_bwd(void* stream, const float* logq_old, int ld_old, co
                              const float* pred_value, const float* target, int value_dim, const uint8_t* done,
                              const double* undone_count, float beta_clone, float value_head_weight, float* d_logits,
                              int ld_dlogits, float* d_aux, float* d_pred, double* terms);
+
+/* srl_ppg_aux_loss_gaussian_fwd_bwd (ABI 21): the same joint loss and backward for Normal action heads (continuous actions:
+ * get_action_distribution returns [Normal(mean, std)], actor_critic_policy.py:303-309), one pass:
+ *   L = aux_value_loss + beta_clone * policy_distance + value_head_weight * value_head_loss
+ *   policy_distance = sum_rows (1 - done_i) sum_j KL(N(m0_ij, s0_ij) || N(m1_ij, s1_ij)) / sum_rows (1 - done)
+ *   KL per element  = 0.5 (r + t - 1) - (ls0 - ls1),  r = exp(2 (ls0 - ls1)),  t = ((m0 - m1) exp(-ls1))^2
+ *                     (torch.distributions.kl_divergence of two Normals, kl.py _kl_normal_normal)
+ *   d KL / d m1 = -(m0 - m1) exp(-2 ls1),   d KL / d ls1 = 1 - r - t
+ *   *_value_loss and their gradients: as in srl_ppg_aux_loss_fwd_bwd
+ * It stands in for phasic_policy_gradient.py:143-150 and :262-280 on Normal heads, with the reference's two defects there repaired
+ * (neither line can execute as shipped): (1) modules/utils.py:213 `distribution.scale.cpu.detach()` raises AttributeError -- the
+ * cached distribution is Normal(loc.detach(), scale.detach()); (2) `_policy_distance` multiplies the [T, B, A] KL by `undone` of
+ * shape [T, B], a shape error unless A happens to broadcast -- every action dimension of a row is weighted by the row's 1 - done,
+ * summed over rows and dimensions and divided by the number of undone rows (as log_prob(...).sum(-1), actor_critic_policy.py:322).
+ * mean_old [n, A] (row stride ld_mean_old) and log_std_old: what the cache entry keeps; mean [n, A] (row stride ld_mean) and
+ * log_std: the current policy's.  Each log sigma operand follows srl_gaussian_fwd: a pointer and a row stride, stride 0 = one
+ * [A] vector shared by all rows (`fixed`, `separate_learnable`), otherwise rows (`shared_learnable`); the old and the new
+ * operand carry their strides independently.  aux_value / pred_value / target / value_dim / done / undone_count / beta_clone /
+ * value_head_weight: as in srl_ppg_aux_loss_fwd_bwd.  available_action plays no part (the reference applies it to discrete
+ * heads only, :134-136).
+ * Outputs: d_mean [n, A] (row stride ld_dmean); d_log_std [n, A] dense, per row, or NULL (`fixed`: requires_grad=False, :90 --
+ * the caller column-sums the rows for `separate_learnable`); d_aux, d_pred [n, value_dim]; terms float64[3] (zeroed by the call)
+ * = {aux_value_loss, value_head_loss, policy_distance}.  count == 0: zero terms and zero gradients; n == 0: returns 0 after
+ * zeroing terms. */
+int srl_ppg_aux_loss_gaussian_fwd_bwd(void* stream, const float* mean_old, int ld_mean_old, const float* log_std_old,
+                                      int ld_log_std_old, const float* mean, int ld_mean, const float* log_std, int ld_log_std,
+                                      long n, int A, const float* aux_value, const float* pred_value, const float* target,
+                                      int value_dim, const uint8_t* done, const double* undone_count, float beta_clone,
+                                      float value_head_weight, float* d_mean, int ld_dmean, float* d_log_std, float* d_aux,
+                                      float* d_pred, double* terms);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense contraction on the FP32 matrix cores (v_mfma_f32_32x32x2_f32: exact f32 FMA chains).

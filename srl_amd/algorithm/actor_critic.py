@@ -21,8 +21,8 @@ import torch.distributed as dist
 from srl_amd import hip
 from srl_amd.algorithm import netspec as ns
 from srl_amd.algorithm.hipnet import HipNet, RnnCtx
-from srl_amd.algorithm.ppo_types import (CategoricalLogits, PPGPhase1AnalyzedResult, PPGPhase2AnalyzedResult, PPORolloutAnalyzedResult,
-                                         SampleAnalyzedResult)
+from srl_amd.algorithm.ppo_types import (CategoricalLogits, NormalParams, PPGPhase1AnalyzedResult, PPGPhase2AnalyzedResult,
+                                         PPORolloutAnalyzedResult, SampleAnalyzedResult)
 from srl_amd.api import policy as policy_api
 from srl_amd.api.env_utils import DiscreteAction
 from srl_amd.namedarray import NamedArray
@@ -553,11 +553,26 @@ class ActorCriticPolicy(policy_api.Policy):
         ptr, ld = self._log_std(net)
         d_ls = net.ws.get("d_log_std_rows", n * A)[:n * A].view(n, A)
         hip.gaussian_bwd(logits, ptr, ld, action, d_lp, d_ent, d_logits, d_ls)
+        return self.log_std_bwd(d_ls, net)
+
+    def log_std_bwd(self, d_ls, net=None):
+        """Where d loss / d log sigma per row ([n, A], dense) goes: `shared_learnable` hands the rows on to ``HipNet.backward``
+        (returned); `separate_learnable` adds their column sums to the vector's gradient; `fixed` takes none."""
+        net = net or self._net
+        n, A = d_ls.shape
         if self.spec.std_type == "shared_learnable":
             return d_ls
         if self.spec.std_type == "separate_learnable":  # `fixed`: requires_grad=False in the reference, no gradient
             hip.colsum(d_ls.data_ptr(), A, n, A, net._g("log_std"), accumulate=True)
         return None
+
+    def log_std_snapshot(self, net=None) -> torch.Tensor:
+        """A COPY of log sigma as the last forward pass used it: the [A] vector, or the second head's [n, A] rows."""
+        net = net or self._net
+        if self.spec.std_type == "shared_learnable":
+            return net.log_std_rows.clone()
+        p = self.spec.params["log_std"]
+        return net.flat[p.offset:p.offset + p.numel].clone()
 
     def _packed_last_state(self):
         """New hidden states as the actors store them: numpy [n, layers, H] per backbone (:505-508)."""
@@ -589,13 +604,12 @@ class ActorCriticPolicy(policy_api.Policy):
 
     def _ppg_phase2_analyze(self, sample, **kwargs):
         """actor_critic_policy.py:417-435: the current action distributions (per head, as normalised log-probabilities -- with
-        unavailable actions at -1e10 before the normalisation, :135-136), the auxiliary and the critic head's values.  ``sample``
+        unavailable actions at -1e10 before the normalisation, :135-136; continuous actions: one ``NormalParams(loc, scale)``,
+        :303-309), the auxiliary and the critic head's values.  ``sample``
         carries ``obs``, ``on_reset`` and, for a recurrent policy, ``policy_state`` (the auxiliary phase's cache entry).  The
         forward context is kept: ``backward_ppg_aux`` follows."""
         if self.spec.aux_head is None:
             raise RuntimeError("Cannot run ppg analysis without auxiliary_head. Try setting auxiliary_head=True.")
-        if self.spec.std_type:
-            raise NotImplementedError("the auxiliary phase is built for categorical action heads")
         T, B = sample.on_reset.shape[0], sample.on_reset.shape[1]
         n = T * B
         obs = {k: to_device_leaf(v, self.device, "obs").reshape(n, *v.shape[2:]) for k, v in sample.obs.items() if v is not None}
@@ -609,6 +623,13 @@ class ActorCriticPolicy(policy_api.Policy):
             rnn = self._rnn_ctx_with_burn_in({k: to_device_leaf(v, self.device, "obs") for k, v in sample.obs.items() if v is not None},
                                              None, ps, to_device_leaf(sample.on_reset, self.device, "flag"), 0, T, B)
         logits, value = self._net.forward(obs, n, keep_tape=True, rnn=rnn)
+        if self.spec.std_type:  # [Normal(mean, std)] (:303-309); `available_action` plays no part (:128-136)
+            self._analysis = (logits, None, None, n)
+            A = logits.shape[1]
+            log_std = self.log_std_snapshot()
+            scale = log_std.exp().expand(n, A)  # (:130: the vector parametrisations broadcast over the rows)
+            return PPGPhase2AnalyzedResult(action_dists=[NormalParams(logits.clone().view(T, B, A), scale.reshape(T, B, A))],
+                                           auxiliary_value=self._net.aux_value.view(T, B, -1), predicted_value=value.view(T, B, -1))
         logq = torch.empty_like(logits)
         hip.categorical_log_softmax(logits, avail, self.spec.act_dims, logq)
         self._analysis = (logits, None, avail, n)
@@ -620,11 +641,14 @@ class ActorCriticPolicy(policy_api.Policy):
         return PPGPhase2AnalyzedResult(action_dists=dists, auxiliary_value=self._net.aux_value.view(T, B, -1),
                                        predicted_value=value.view(T, B, -1))
 
-    def backward_ppg_aux(self, d_logits: torch.Tensor, d_aux: torch.Tensor, d_value: torch.Tensor):
-        """Back-propagate the auxiliary loss's gradients with respect to the raw logits, the auxiliary values and the critic head's
-        values of the last ``analyze(target="ppg_aux_phase")`` into ``net.grad``."""
+    def backward_ppg_aux(self, d_logits: torch.Tensor, d_aux: torch.Tensor, d_value: torch.Tensor,
+                         d_log_std: Optional[torch.Tensor] = None):
+        """Back-propagate the auxiliary loss's gradients with respect to the raw logits (continuous actions: the means), the
+        auxiliary values and the critic head's values of the last ``analyze(target="ppg_aux_phase")`` into ``net.grad``.
+        ``d_log_std`` (continuous actions, [.., A] per row): see ``log_std_bwd``."""
         _, _, _, n = self._analysis
-        self._net.backward(d_logits.reshape(n, -1), d_value.reshape(n, -1), None, d_aux=d_aux.reshape(n, -1))
+        d_ls = None if d_log_std is None else self.log_std_bwd(d_log_std.reshape(n, -1))
+        self._net.backward(d_logits.reshape(n, -1), d_value.reshape(n, -1), d_ls, d_aux=d_aux.reshape(n, -1))
         self._analysis = None
 
     def _ppo_analyze(self, sample, burn_in_steps=0, **kwargs):

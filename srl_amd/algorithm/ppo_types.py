@@ -5,7 +5,7 @@
 ``PPGPhase1AnalyzedResult`` / ``PPGPhase2AnalyzedResult`` / ``AuxiliaryStepResult``: ``phasic_policy_gradient.py:15-57``.
 """
 import dataclasses
-from typing import List, Optional
+from typing import List, Optional, Union
 
 import torch
 
@@ -57,10 +57,21 @@ class CategoricalLogits:
         return CategoricalLogits(self.logits.detach().cpu())
 
 
+class NormalParams:
+    """What the auxiliary phase needs of a ``torch.distributions.Normal`` (actor_critic_policy.py:303-309, continuous actions):
+    ``loc`` and ``scale`` [..., A] (``scale`` = exp(log sigma), broadcast to the rows for the vector parametrisations, :129-132)."""
+
+    def __init__(self, loc: torch.Tensor, scale: torch.Tensor):
+        self.loc, self.scale = loc, scale
+
+    def detach_cpu(self):
+        return NormalParams(self.loc.detach().cpu(), self.scale.detach().cpu())
+
+
 @dataclasses.dataclass
 class PPGPhase2AnalyzedResult:
     """``policy.analyze(target="ppg_aux_phase")`` (phasic_policy_gradient.py:32-44)."""
-    action_dists: List[CategoricalLogits]  # one per action head, [T, B, A_h]
+    action_dists: List[Union[CategoricalLogits, NormalParams]]  # discrete: one per action head, [T, B, A_h]; continuous: one Normal
     auxiliary_value: torch.Tensor  # [T, B, value_dim], from the actor's features
     predicted_value: torch.Tensor  # [T, B, value_dim], from the critic head
 
