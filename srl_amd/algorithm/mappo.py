@@ -33,6 +33,7 @@ import torch.distributed as dist
 from srl_amd import hip
 from srl_amd.algorithm import netspec as ns
 from srl_amd.algorithm.actor_critic import ActorCriticPolicy, obs_leaves, to_device_leaf, wire_leaf
+from srl_amd.algorithm.optim import FlatOptimizer
 from srl_amd.api.trainer import PytorchTrainer, TrainerStepResult, register
 from srl_amd.namedarray import recursive_apply
 from srl_amd.runtime.obs_ring import RingObs
@@ -230,40 +231,8 @@ class MultiAgentPPO(PytorchTrainer):
             # delta [Tb - 1] in gae_trace (gae.py:63-65) and the shapes clash
             raise NotImplementedError("burn-in together with V-trace: the reference's own shapes clash (mappo.py:243-246, gae.py:65)")
 
-        # optimiser (modules/utils.py:268-286: torch.optim.{Adam, AdamW, RMSprop, SGD}(**optimizer_config))
-        name = g('optimizer', 'adam')
-        if name not in ('adam', 'adamw', 'rmsprop', 'sgd'):
-            raise AssertionError(f"Optimizer name {name} does not match any implemented optimizers "
-                                 "(['adam', 'rmsprop', 'sgd', 'adamw']).")
-        cfg = dict(g('optimizer_config', {}))
-        self._opt = name
-        self._adamw = name == 'adamw'
-        self._betas, self._eps = (0.9, 0.999), 1e-8
-        if name in ('adam', 'adamw'):
-            self._lr = cfg.pop("lr", 1e-3)
-            self._betas = tuple(cfg.pop("betas", (0.9, 0.999)))
-            self._eps = cfg.pop("eps", 1e-8)
-            self._weight_decay = cfg.pop("weight_decay", 1e-2 if self._adamw else 0.0)
-        elif name == 'rmsprop':  # torch defaults: lr 1e-2, alpha 0.99, eps 1e-8, no momentum, not centred
-            self._lr = cfg.pop("lr", 1e-2)
-            self._alpha = cfg.pop("alpha", 0.99)
-            self._eps = cfg.pop("eps", 1e-8)
-            self._weight_decay = cfg.pop("weight_decay", 0.0)
-            self._momentum = cfg.pop("momentum", 0.0)
-            self._centered = bool(cfg.pop("centered", False))
-        else:  # sgd
-            self._lr = cfg.pop("lr", 1e-3)
-            self._momentum = cfg.pop("momentum", 0.0)
-            self._dampening = cfg.pop("dampening", 0.0)
-            self._weight_decay = cfg.pop("weight_decay", 0.0)
-            self._nesterov = bool(cfg.pop("nesterov", False))
-            if self._nesterov and (self._momentum <= 0 or self._dampening != 0):
-                raise ValueError("Nesterov momentum requires a momentum and zero dampening")  # torch/optim/sgd.py
-        for flag in ("amsgrad", "maximize", "capturable", "differentiable", "fused", "foreach"):
-            if cfg.get(flag) in (None, False):
-                cfg.pop(flag, None)
-        if cfg:
-            raise NotImplementedError(f"unsupported optimizer_config entries: {sorted(cfg)}")
+        # (modules/utils.py:268-286: torch.optim.{Adam, AdamW, RMSprop, SGD}(**optimizer_config))
+        self.optimizer = FlatOptimizer(policy.net, g('optimizer', 'adam'), g('optimizer_config', {}), "optimizer_config")
         value_loss = g('value_loss', 'mse')
         if value_loss not in hip.VALUE_LOSS_KINDS:
             raise AssertionError(f"Value loss name {value_loss} does not match any implemented loss functions "
@@ -277,12 +246,6 @@ class MultiAgentPPO(PytorchTrainer):
                                   value_loss=hip.VALUE_LOSS_KINDS[value_loss], mask_invert=1)
 
         net = policy.net
-        # optimiser state on the flat layout: Adam (exp_avg, exp_avg_sq); RMSprop (momentum_buffer, square_avg, grad_avg);
-        # SGD (momentum_buffer)
-        self._m = torch.zeros_like(net.flat)
-        self._v = torch.zeros_like(net.flat) if name != 'sgd' else None
-        self._gavg = torch.zeros_like(net.flat) if name == 'rmsprop' and self._centered else None
-        self._opt_steps = 0
         self.frames = 0
         # rows (env-steps) per forward/backward chunk: bounds the activation workspace, not the arithmetic.  Default: 16 384 for
         # nets with a convolution / pooling encoder (26 KB of taped activations per frame); 2^20 for vector-observation nets,
@@ -317,88 +280,19 @@ class MultiAgentPPO(PytorchTrainer):
     # ------------------------------------------------------------------ checkpoints (mappo.py:58-66)
     def get_checkpoint(self):
         ckpt = self.policy.get_checkpoint()
-        net = self.policy.net
-        names = net.ref_names()
-        named = lambda t: net.flat_to_reference(t.detach().cpu())
-        step_t = torch.tensor(float(self._opt_steps))
-        state = {}
-        # the PopArt statistics are gradient-less nn.Parameters of the reference: listed, stateless
-        params = list(range(len(names) + (3 if net.spec.popart else 0)))
-        common = dict(maximize=False, foreach=None, differentiable=False, params=params)
-        if self._opt in ('adam', 'adamw'):
-            if self._opt_steps > 0:
-                m, v = named(self._m), named(self._v)
-                state = {i: dict(step=step_t.clone(), exp_avg=m[n], exp_avg_sq=v[n]) for i, n in enumerate(names)}
-            group = dict(lr=self._lr, betas=self._betas, eps=self._eps, weight_decay=self._weight_decay, amsgrad=False,
-                         capturable=False, fused=None, **common)
-        elif self._opt == 'rmsprop':
-            if self._opt_steps > 0:
-                sq, buf = named(self._v), named(self._m)
-                ga = named(self._gavg) if self._centered else None
-                for i, n in enumerate(names):
-                    state[i] = dict(step=step_t.clone(), square_avg=sq[n])
-                    if self._momentum > 0:
-                        state[i]["momentum_buffer"] = buf[n]
-                    if self._centered:
-                        state[i]["grad_avg"] = ga[n]
-            group = dict(lr=self._lr, momentum=self._momentum, alpha=self._alpha, eps=self._eps, centered=self._centered,
-                         weight_decay=self._weight_decay, capturable=False, **common)
-        else:
-            if self._opt_steps > 0 and self._momentum != 0:
-                buf = named(self._m)
-                state = {i: dict(momentum_buffer=buf[n]) for i, n in enumerate(names)}
-            group = dict(lr=self._lr, momentum=self._momentum, dampening=self._dampening, weight_decay=self._weight_decay,
-                         nesterov=self._nesterov, fused=None, **common)
-        ckpt.update({"optimizer_state_dict": {"state": state, "param_groups": [group]}})
+        ckpt["optimizer_state_dict"] = self.optimizer.state_dict()
         return ckpt
 
     def load_checkpoint(self, checkpoint, **kwargs):
         osd = checkpoint.get("optimizer_state_dict")
         if osd is not None:
-            net = self.policy.net
-            names = net.ref_names()
-            st = osd["state"]
-            flat_of = lambda key: net.reference_to_flat({n: st[i][key] for i, n in enumerate(names)})
-            slots = {'adam': (("exp_avg", "_m"), ("exp_avg_sq", "_v")), 'adamw': (("exp_avg", "_m"), ("exp_avg_sq", "_v")),
-                     'rmsprop': (("momentum_buffer", "_m"), ("square_avg", "_v"), ("grad_avg", "_gavg")),
-                     'sgd': (("momentum_buffer", "_m"),)}[self._opt]
-            for key, attr in slots:
-                buf = getattr(self, attr)
-                if buf is None:
-                    continue
-                if st and key in st[0] and st[0][key] is not None:
-                    buf.copy_(flat_of(key))
-                else:
-                    buf.zero_()
-            if st:
-                # SGD keeps no step count: a restored momentum buffer means "not the first step"
-                self._opt_steps = int(float(st[0]["step"])) if "step" in st[0] else 1
-            else:
-                self._opt_steps = 0
-            grp = osd["param_groups"][0]
-            # the group names its optimiser by the keys only that optimiser has (torch's load_state_dict would overwrite
-            # the group and fail on foreign state; mappo.py:58-66): a checkpoint of another kind is refused, not zero-filled
-            kind_keys = {'adam': ("betas",), 'adamw': ("betas",), 'rmsprop': ("alpha", "centered"), 'sgd': ("dampening", "nesterov")}
-            foreign = [k for kind, keys in kind_keys.items() if kind_keys[kind] != kind_keys[self._opt] for k in keys if k in grp]
-            if foreign or any(k not in grp for k in kind_keys[self._opt]):
-                raise ValueError(f"optimizer_state_dict is not a `{self._opt}` state (group keys {sorted(grp)})")
-            if self._opt == 'rmsprop' and bool(grp["centered"]) != self._centered:
-                self._centered = bool(grp["centered"])
-                self._gavg = torch.zeros_like(net.flat) if self._centered else None
-                if self._centered and st and "grad_avg" in st[0]:
-                    self._gavg.copy_(flat_of("grad_avg"))
-            if self._opt == 'sgd':
-                self._dampening, self._nesterov = grp.get("dampening", self._dampening), bool(grp.get("nesterov", self._nesterov))
-            self._lr = grp["lr"]
-            self._weight_decay = grp.get("weight_decay", self._weight_decay)
-            if self._opt in ('adam', 'adamw'):
-                self._betas, self._eps = tuple(grp["betas"]), grp["eps"]
-            elif self._opt == 'rmsprop':
-                self._alpha, self._eps = grp.get("alpha", self._alpha), grp.get("eps", self._eps)
-                self._momentum = grp.get("momentum", self._momentum)
-            else:
-                self._momentum = grp.get("momentum", self._momentum)
+            self.optimizer.load_state_dict(osd, "optimizer_state_dict")
         self.policy.load_checkpoint(checkpoint)
+
+    # bench.py saves and restores the optimiser's state through these three names
+    _m = property(lambda self: self.optimizer.m)
+    _v = property(lambda self: self.optimizer.v)
+    _opt_steps = property(lambda self: self.optimizer.steps, lambda self, n: setattr(self.optimizer, "steps", n))
 
     def distributed(self, rank=None, world_size=None, init_method=None, **kwargs):
         super().distributed(rank=rank, world_size=world_size, init_method=init_method, **kwargs)
@@ -409,6 +303,11 @@ class MultiAgentPPO(PytorchTrainer):
             from srl_amd import comm
             self._comm = comm.NativeComm.from_process_group(self.policy.device)  # None: torch.distributed collectives
         self._reducer = _BucketReducer(self.policy.net, self.grad_bucket_bytes, self._comm) if self._dist else None
+
+    def _chunks(self, n, rnn):
+        """Rows [0, n) in pieces of ``chunk_rows``: [(r0, r1), ...]."""
+        step = n if rnn is not None else self.chunk_rows   # recurrent nets walk the time axis: one piece
+        return [(r0, min(n, r0 + step)) for r0 in range(0, n, step)]
 
     def _importance_ratio(self, net, obs, avail, action, old_lp, rows, B, alive=None, pstate=None, on_reset=None):
         """exp(new_lp - old_lp) on rows [0, rows) of the sample, forward only; [rows, B, 1] float32.  Feed-forward nets go
@@ -423,9 +322,7 @@ class MultiAgentPPO(PytorchTrainer):
         rnn = None
         if net.spec.num_rnn_layers:
             rnn = self.policy._rnn_ctx_with_burn_in(obs, None, pstate, on_reset, 0, rows, B)
-        step = n_all if rnn is not None else self.chunk_rows
-        for r0 in range(0, n_all, step):
-            r1 = min(n_all, r0 + step)
+        for r0, r1 in self._chunks(n_all, rnn):
             n = r1 - r0
             logits, _ = net.forward({k: v[r0:r1] for k, v in f_obs.items()}, n, keep_tape=False, rnn=rnn)
             ent = net.ws.get("entropy", n)[:n]
@@ -448,7 +345,7 @@ class MultiAgentPPO(PytorchTrainer):
 
         # ---- the sample's leaves in their wire dtypes: on the device -- or, for a captured step (use_graph), wherever they
         # are: the native step driver copies them straight into the graph's static inputs ---------------------------------
-        graphed = (self.use_graph and not self._dist and self._opt in ('adam', 'adamw')
+        graphed = (self.use_graph and not self._dist and self.optimizer.name in ('adam', 'adamw')
                    and not any(isinstance(v, RingObs) for _, v, _ in obs_leaves(sample.obs)))  # ring rows are bound per sample
         leaf = (lambda x, kind: wire_leaf(x, kind)) if graphed else (lambda x, kind: to_device_leaf(x, dev, kind))
         L = dict(on_reset=leaf(sample.on_reset, "flag"), done=leaf(sample.done, "flag"),
@@ -490,10 +387,11 @@ class MultiAgentPPO(PytorchTrainer):
         # ---- the device part: everything between "leaves in HBM" and "terms ready"; no host synchronisation inside, so
         # it can be captured once into a hipGraph and replayed (use_graph) -----------------------------------------
         if graphed:
-            out = self._replay(L, have_adv, self._step_scalars(self.ppo_epochs), host_results=not isinstance(sample.reward, torch.Tensor))
+            out = self._replay(L, have_adv, self.optimizer.bias_corrections(self.ppo_epochs),
+                               host_results=not isinstance(sample.reward, torch.Tensor))
         else:
             out = self._device_part(L, have_adv, None)
-        self._opt_steps += self.ppo_epochs
+        self.optimizer.steps += self.ppo_epochs
         if self.popart:
             self.policy._popart_updates += self.ppo_epochs
 
@@ -553,15 +451,6 @@ class MultiAgentPPO(PytorchTrainer):
         return TrainerStepResult(stats=stats, step=self.policy.version)
 
     # ------------------------------------------------------------------ hipGraph capture of the device part
-    def _step_scalars(self, epochs):
-        """Adam bias corrections of the next `epochs` optimiser steps, float32 [epochs, 2] (what srl_adam_step derives
-        from its `step` argument, precomputed so that the captured launch carries no per-step scalar)."""
-        rows = []
-        for e in range(1, epochs + 1):
-            t = self._opt_steps + e
-            rows.append([self._lr / (1.0 - self._betas[0]**t), (1.0 - self._betas[1]**t)**0.5])
-        return np.asarray(rows, dtype=np.float32)
-
     def _replay(self, L, have_adv, scal, host_results):
         """The device part as a captured hipGraph behind the native step driver (csrc/step_plan.hip): per step ONE C call
         copies the sample's leaves (host or device) into the graph's static inputs, launches the graph and brings the
@@ -610,249 +499,272 @@ class MultiAgentPPO(PytorchTrainer):
         return dict(terms=terms_host.numpy(), nchunks=out["nchunks"], adv=adv if adv is not None else out["adv"],
                     ret=ret if ret is not None else out["ret"], owned=adv is not None)
 
+    # ------------------------------------------------------------------ the device part: an epoch loop over the phases below
     def _device_part(self, L, have_adv, dscal):
-        """GAE / statistics / (PopArt) / epochs x (forward, loss, backward, [all-reduce], clip + Adam).  Returns device
+        """GAE / statistics / (PopArt) / epochs x (forward, loss, backward, [all-reduce], clip + optimiser).  Returns device
         tensors only: per-epoch loss terms, and the padded advantages / value targets."""
-        dev = self.policy.device
         net = self.policy.net
-        on_reset, done, truncated, reward = L["on_reset"], L["done"], L["truncated"], L["reward"]
-        old_value, old_lp, action = L["old_value"], L["old_lp"], L["action"]
+        on_reset, old_value = L["on_reset"], L["old_value"]
         obs = {k[4:]: v for k, v in L.items() if k.startswith("obs.")}
         avail = obs.pop("available_action", None)
         alive = obs.pop("is_alive", None) if self.policy.masks_dead_agents else None
         pstate = {k[len("policy_state."):]: v for k, v in L.items() if k.startswith("policy_state.")}
         Tb, B = on_reset.shape[0], on_reset.shape[1]
-        boot, burn = self.bootstrap_steps, self.burn_in_steps
-        lo, hi = burn, Tb - boot
+        lo, hi = self.burn_in_steps, Tb - self.bootstrap_steps  # valid rows (mappo.py:259)
         n_valid = (hi - lo) * B
         Nc = net.spec.value_dim
-        f64 = dict(dtype=torch.float64, device=dev)
+        flat = lambda t: t[lo:hi].reshape(n_valid, *t.shape[2:])
         # step-persistent device state lives in the net's workspace: nothing below allocates in steady state
         stats_local = net.ws.get("mappo.stats_local", 3, torch.float64)[:3]
         # without a process group the global statistics ARE the local ones (no copy)
         stats_global = net.ws.get("mappo.stats_global", 3, torch.float64)[:3] if self._dist else stats_local
-        stats_work = None  # pending all-reduce of stats_global (joined right before its first reader)
-        adv_d = ret_d = None
         # what goes back to the host, in ONE float64 block zeroed once per step: per epoch the loss-term sums of every
         # row chunk (added up on the host), the gradient norm (a float32 in the low half of its slot) and, with PopArt,
         # the masked sums of the value targets
-        n_valid_rows = (Tb - self.bootstrap_steps - self.burn_in_steps) * B
-        chunk_rows = n_valid_rows if net.spec.num_rnn_layers else self.chunk_rows
-        nchunks = max(1, -(-n_valid_rows // chunk_rows))
+        chunks = self._chunks(n_valid, net.spec.num_rnn_layers or None)
+        nchunks = len(chunks)
         stride = nchunks * hip.LT_COUNT + 1 + 3 * Nc
         block = net.ws.get("mappo.out", self.ppo_epochs * stride, torch.float64)[:self.ppo_epochs * stride]
         block.zero_()
         block = block.view(self.ppo_epochs, stride)
 
+        adv_d = ret_d = None
         for epoch in range(self.ppo_epochs):
             # what the encoder blocks derive from the parameters alone goes first: it runs while the host issues the head below
             if dscal is None:
                 net.prepare_derived()
-            # ---- advantages / value targets ------------------------------------------------------------------
             if adv_d is None:
-                if have_adv:
-                    adv_d, ret_d = L["adv"], L["ret"]
-                    fused_stats = False
-                else:
-                    adv_d = net.ws.get("mappo.adv", Tb * B * Nc)[:Tb * B * Nc].view(Tb, B, Nc)
-                    ret_d = net.ws.get("mappo.ret", Tb * B * Nc)[:Tb * B * Nc].view(Tb, B, Nc)
-                    # the scan writes rows [0, Tb-1); the last row is the zero pad (:254-256).  Zeroed every step: the
-                    # workspace is shared by every sample shape this trainer sees (and by every captured graph), so the
-                    # row may hold another shape's advantages -- B * Nc floats, nothing next to the step
-                    adv_d[Tb - 1:].zero_()
-                    ret_d[Tb - 1:].zero_()
-                    fused_stats = boot == 1 and burn == 0  # the scan's own sums are those of the loss rows
-                    gws = self._gae_ws.get((B, Nc))
-                    if gws is None:  # zeroed once; afterwards the scan's own last workgroup resets it
-                        gws = self._gae_ws[(B, Nc)] = hip.gae_scan_workspace(B, Nc, dev)
-                    # PopArt: the stored values are normalised; the trace runs on de-normalised ones (mappo.py:120-124)
-                    trace_value = self.policy.denormalize_value(old_value) if self.popart else old_value
-                    ratio = None
-                    if self.vtrace:  # importance ratio of the CURRENT parameters on every rewarding step (:130-133)
-                        ratio = self._importance_ratio(net, obs, avail, action, old_lp, Tb - 1, B, alive, pstate, on_reset)
-                    hip.gae_scan(reward, trace_value, done, truncated, on_reset, self.discount_rate, self.gae_lambda,
-                                 adv_d, ret_d, stats=stats_local if fused_stats else None, imp_ratio=ratio,
-                                 workspace=gws if fused_stats else None)
-                mask_rows = on_reset[1 + lo:1 + hi]  # loss_mask = 1 - on_reset[1+burn : 1+Tb-boot]  (:260-261)
-                if not fused_stats and Nc == 1:
-                    hip.masked_stats(adv_d[lo:hi], mask_rows, stats_local, mask_invert=True)
-                elif not fused_stats:  # [n, Nc] advantages under an [n] mask: per-channel sums, the mask counted once
-                    cs = net.ws.get("mappo.col_stats", 3 * Nc, torch.float64)[:3 * Nc].view(Nc, 3)  # zeroed by the call
-                    hip.masked_stats_cols(adv_d[lo:hi].reshape(-1, Nc), mask_rows, cs, Nc, mask_invert=True)
-                    hip.fold_col_stats(cs, Nc, stats_local)
-                if self._dist:
-                    stats_global.copy_(stats_local)
-                    # one 24-byte message instead of three (utils.py:58-61), issued asynchronously: it crosses the
-                    # links while the first chunk's forward pass runs and is joined before the first loss kernel
-                    if self._comm is not None:
-                        self._comm.all_reduce_f64_async(stats_global)
-                        stats_work = self._comm
-                    else:
-                        stats_work = dist.all_reduce(stats_global, async_op=True)
-                local_n = stats_local[0:1]
-
-            flat = lambda t: t[lo:hi].reshape(n_valid, *t.shape[2:])
-            # ---- PopArt: statistics of the value targets, then the loss sees normalised targets (:263-264, :173-176) ----
-            loss_ret, pstats_local = ret_d, None
-            head_old = head_new = None
+                adv_d, ret_d, mask_rows, local_n, pending = self._advantages(net, L, obs, avail, alive, pstate, have_adv, lo, hi,
+                                                                             stats_local, stats_global)
+            loss_ret, heads = ret_d, None
             if self.popart:
-                pstats_local = block[epoch, stride - 3 * Nc:].view(Nc, 3)  # zeroed by srl_masked_stats_cols itself
-                hip.masked_stats_cols(flat(ret_d), on_reset[1 + lo:1 + hi], pstats_local, Nc, mask_invert=True)
-                pstats = net.ws.get("mappo.pstats", 3 * Nc, torch.float64)[:3 * Nc].view(Nc, 3)
-                pstats.copy_(pstats_local)
-                if self._dist and self._comm is not None:
-                    # one message instead of utils.py:121-124's three, on the SAME communicator and side stream as the
-                    # advantage statistics and the gradient buckets: one communicator orders every collective of a step
-                    self._comm.all_reduce_f64_async(pstats)
-                    self._comm.join()
-                elif self._dist:
-                    if stats_work is not None:  # never two collectives of this step in flight on different streams
-                        stats_work.wait()
-                        stats_work = None
-                    dist.all_reduce(pstats)
-                # The reference analyses the sample BEFORE this update (mappo.py:244 against :264) and rescales the head's storage
-                # in place (popart.py:50-51): the loss sees the values of the head as it was, while the backward pass, which reads
-                # the same storage, propagates through the rescaled weight, and the optimiser steps from the rescaled head.  Here
-                # the update comes first, so in an epoch that rescales the old head is kept, put back for every chunk's forward
-                # pass and replaced by the rescaled one before that chunk's backward pass.
-                head = self.policy.popart_head_params()
-                if self.policy.popart_rescales(epoch + 1):  # the reference counts per update, i.e. per epoch (popart.py:47-49)
-                    head_old = [net.ws.get(f"mappo.head_old{i}", p.numel())[:p.numel()] for i, p in enumerate(head)]
-                    head_new = [net.ws.get(f"mappo.head_new{i}", p.numel())[:p.numel()] for i, p in enumerate(head)]
-                    for dst, p in zip(head_old, head):
-                        dst.copy_(p)
-                self.policy.update_popart_from_stats(pstats, count=False, ahead=epoch)
-                if head_old is not None:
-                    for keep, back, p in zip(head_new, head_old, head):
-                        keep.copy_(p)
-                        p.copy_(back)
-                loss_ret = torch.empty_like(ret_d)
-                hip.popart_map(ret_d, net.popart_state, Nc, loss_ret, True, ns.POPART_EPS)
+                pstats_local = block[epoch, stride - 3 * Nc:].view(Nc, 3)
+                loss_ret, heads = self._popart_targets(net, ret_d, flat(ret_d), mask_rows, pstats_local, epoch, pending)
             loss_oldv = self.policy.normalize_value(old_value) if self.normalize_old_value else old_value  # :151-152
 
-            # ---- forward / loss / backward over row chunks -----------------------------------------------------------
             net.zero_grad()
-            f_obs = {k: flat(v) for k, v in obs.items()}
-            f_avail = None if avail is None else flat(avail)
-            f_alive = None if alive is None else flat(alive).reshape(-1)
-            f_action, f_oldlp, f_oldv = flat(action), flat(old_lp).reshape(-1), flat(loss_oldv).reshape(-1)
-            f_adv, f_ret, f_mask = flat(adv_d).reshape(-1), flat(loss_ret).reshape(-1), mask_rows.reshape(-1)
-            f_done, f_trunc = flat(done).reshape(-1), flat(truncated).reshape(-1)
-            # recurrent nets walk the time axis: all valid rows go through in one piece
+            rows = ({k: flat(v) for k, v in obs.items()}, None if avail is None else flat(avail),
+                    None if alive is None else flat(alive).reshape(-1), flat(L["action"]), flat(L["old_lp"]).reshape(-1),
+                    flat(loss_oldv).reshape(-1), flat(adv_d).reshape(-1), flat(loss_ret).reshape(-1), mask_rows.reshape(-1),
+                    flat(L["done"]).reshape(-1), flat(L["truncated"]).reshape(-1))
             rnn = None
             if net.spec.num_rnn_layers:  # chunk states from the sample, or from a no-grad replay of the burn-in rows
-                rnn = self.policy._rnn_ctx_with_burn_in(obs, None, pstate, on_reset, burn, hi - lo, B)
+                rnn = self.policy._rnn_ctx_with_burn_in(obs, None, pstate, on_reset, lo, hi - lo, B)
             terms = block[epoch, :nchunks * hip.LT_COUNT].view(nchunks, hip.LT_COUNT)
-            reducer = self._reducer if self._dist else None
-            # Two pipelines: even chunks on the compute stream with the policy's executor, odd chunks on a second stream
-            # with its twin (same parameters, own workspace / tape / gradient buffer).  Not for recurrent nets (one chunk),
-            # not inside a graph capture.
-            # (nor in an epoch that rescales the PopArt head: the pipelines share the parameters the chunks swap)
-            two = (self.pipelines >= 2 and nchunks >= 2 and rnn is None and dscal is None and not net.force_explicit_conv
-                   and head_old is None)
-            nets, streams = [net], [torch.cuda.current_stream()]
-            if two:
-                npipe = min(self.pipelines, nchunks)
-                if self._twin is None or len(self._twin) != npipe - 1:
-                    self._twin = [net.twin() for _ in range(npipe - 1)]
-                    self._pipe_stream = [torch.cuda.Stream(device=dev) for _ in range(npipe - 1)]
-                # the weight-range slots are shared: they are recomputed here, before the fork.  Before the very first
-                # forward pass the layers that want one are not known yet: the other pipelines then start after the first
-                # chunk, which discovers and fills them
-                first_sync = not net.refresh_weight_ranges()
-                if stats_work is not None:  # the global advantage statistics: needed by every pipeline
-                    stats_work.join() if stats_work is self._comm else stats_work.wait()
-                    stats_work = None
-                for twin, pst in zip(self._twin, self._pipe_stream):
-                    twin.zero_grad()
-                    pst.wait_stream(streams[0])
-                    nets.append(twin)
-                    streams.append(pst)
-            if reducer is not None:
-                reducer.begin([x.grad for x in nets])
-            net.chunks_of_one_update(True, pipelines=len(nets))
-            for x in nets:
-                x.reset_open_accumulations()  # (an accumulation a failed update left open is not continued)
-            for ci in range(nchunks):
-                r0, r1 = ci * chunk_rows, min(n_valid, (ci + 1) * chunk_rows)
-                n = r1 - r0
-                e = ci % len(nets)
-                cnet = nets[e]
-                cnet.last_chunk = ci + len(nets) >= nchunks  # this executor's last chunk of the update
-                if reducer is not None and ci + len(nets) >= nchunks:
-                    # a pipeline's gradients become final in the backward pass of ITS last chunk; a bucket goes out when
-                    # every pipeline has released it (api/policy.py:219-238: what DDP's bucketing does)
-                    cnet.grad_ready_hook = reducer.hook(e)
-                with torch.cuda.stream(streams[e]):
-                    c_obs = {k: v[r0:r1] for k, v in f_obs.items()}
-                    c_avail = None if f_avail is None else f_avail[r0:r1]
-                    if head_old is not None and ci > 0:
-                        for p, back in zip(head, head_old):
-                            p.copy_(back)
-                        net.params_changed()
-                    logits, value = cnet.forward(c_obs, n, keep_tape=True, rnn=rnn)
-                    if head_old is not None:
-                        for p, new in zip(head, head_new):
-                            p.copy_(new)
-                        net.params_changed()
-                    logp = cnet.ws.get("new_logp", n)[:n]
-                    ent = cnet.ws.get("entropy", n)[:n]
-                    self.policy.dist_fwd(logits, f_action[r0:r1], c_avail, logp, ent, net=cnet)
-                    self.policy.mask_dead(logp, None if f_alive is None else f_alive[r0:r1])
-                    d_lp = cnet.ws.get("d_logp", n)[:n]
-                    d_v = cnet.ws.get("d_value", n * Nc)[:n * Nc]
-                    d_ent = cnet.ws.get("d_entropy", n)[:n]
-                    if stats_work is not None:  # the global advantage statistics: first needed here
-                        stats_work.join() if stats_work is self._comm else stats_work.wait()
-                        stats_work = None
-                    hip.ppo_loss_fwd_bwd(logp, f_oldlp[r0:r1], value.reshape(-1), f_oldv[r0 * Nc:r1 * Nc], f_adv[r0 * Nc:r1 * Nc],
-                                         f_ret[r0 * Nc:r1 * Nc],
-                                         ent, f_mask[r0:r1], self._hp, stats_global, local_n, d_lp, d_v, d_ent, terms[ci],
-                                         done=f_done[r0:r1], truncated=f_trunc[r0:r1], value_dim=Nc)
-                    d_logits = cnet.ws.get("d_logits", logits.numel())[:logits.numel()].view_as(logits)
-                    d_ls = self.policy.dist_bwd(logits, f_action[r0:r1], c_avail, d_lp, d_ent, d_logits, net=cnet)
-                    cnet.backward(d_logits, d_v.view(n, Nc), d_ls)
-                if two and ci == 0 and first_sync:
-                    for pst in streams[1:]:
-                        pst.wait_stream(streams[0])
-            net.chunks_of_one_update(False)
-            for x in nets:
-                x.last_chunk = None
-            if two and reducer is None:
-                for pst in self._pipe_stream:
-                    streams[0].wait_stream(pst)
-                hip.accumulate_n(net.grad, [twin.grad for twin in self._twin])   # one launch, added in pipeline order
-
-            # ---- gradient reduction, clip, Adam (mappo.py:272-284) ---------------------------------------------------
-            if reducer is not None:  # the buckets not yet launched (folding the pipelines' slices), then wait for all of them
-                for x in nets:
-                    x.grad_ready_hook = None
-                reducer.finish(streams[1:])
-                for pst in streams[1:]:
-                    streams[0].wait_stream(pst)
-            sumsq = net.ws.get("mappo.sumsq", 1, torch.float64)[:1]  # zeroed by srl_grad_sumsq
+            # one pipeline for recurrent nets (one chunk), inside a graph capture, and in an epoch that rescales the PopArt
+            # head (the pipelines share the parameters the chunks swap)
+            alone = rnn is not None or dscal is not None or heads is not None
+            nets, streams, first_sync = self._pipelines(net, nchunks, alone, pending)
+            self._chunk_loop(net, nets, streams, first_sync, chunks, rows, rnn, heads, terms, stats_global, local_n, pending)
             slot = epoch * stride + nchunks * hip.LT_COUNT
             gnorm = block.view(-1).view(torch.float32)[2 * slot:2 * slot + 1]
-            hip.grad_sumsq(net.grad, sumsq)
-            clip = dict(grad_scale=1.0 / self._world, sumsq=sumsq, grad_norm_out=gnorm,
-                        max_norm=-1.0 if self.max_grad_norm is None else float(self.max_grad_norm))
-            if self._opt in ('adam', 'adamw'):
-                hip.adam_step(net.flat, net.grad, self._m, self._v, self._lr, self._betas[0], self._betas[1], self._eps,
-                              self._weight_decay, self._adamw, self._opt_steps + epoch + 1,
-                              step_scalars=None if dscal is None else dscal[epoch], **clip)
-            elif self._opt == 'rmsprop':
-                hip.rmsprop_step(net.flat, net.grad, self._v, self._m if self._momentum > 0 else None, self._gavg, self._lr,
-                                 self._alpha, self._eps, self._weight_decay, self._momentum, self._centered, **clip)
-            else:
-                hip.sgd_step(net.flat, net.grad, self._m if self._momentum != 0 else None, self._lr, self._momentum,
-                             self._dampening, self._weight_decay, self._nesterov, self._opt_steps + epoch == 0, **clip)
-
-            net.params_changed()  # cached per-layer weight ranges (two-plane f16 forward products) are stale
+            self._clip_and_step(self.optimizer, net, gnorm, epoch, None if dscal is None else dscal[epoch])
             if self.recompute_adv_among_epochs and epoch + 1 < self.ppo_epochs:
                 adv_d = ret_d = None
                 have_adv = False
 
         return dict(terms=block, nchunks=nchunks, adv=adv_d, ret=ret_d)
+
+    @staticmethod
+    def _join(pending):
+        """The statistics all-reduce in flight, if any, is joined by whoever reads ``stats_global`` first: ``pending`` (its
+        ``join`` or ``wait``) is empty afterwards."""
+        for join in pending:
+            join()
+        pending.clear()
+
+    def _advantages(self, net, L, obs, avail, alive, pstate, have_adv, lo, hi, stats_local, stats_global):
+        """Advantages / value targets [Tb, B, Nc] (the sample's, or the GAE scan's), the loss mask of the valid rows [lo, hi),
+        the local advantage statistics in ``stats_local`` and the global ones on their way into ``stats_global``.  Returns
+        ``(adv_d, ret_d, mask_rows, local_n, pending)``."""
+        on_reset, old_value = L["on_reset"], L["old_value"]
+        (Tb, B), Nc = on_reset.shape[:2], net.spec.value_dim
+        if have_adv:
+            adv_d, ret_d = L["adv"], L["ret"]
+            fused_stats = False
+        else:
+            adv_d = net.ws.get("mappo.adv", Tb * B * Nc)[:Tb * B * Nc].view(Tb, B, Nc)
+            ret_d = net.ws.get("mappo.ret", Tb * B * Nc)[:Tb * B * Nc].view(Tb, B, Nc)
+            # the scan writes rows [0, Tb-1); the last row is the zero pad (:254-256).  Zeroed every step: the
+            # workspace is shared by every sample shape this trainer sees (and by every captured graph), so the
+            # row may hold another shape's advantages -- B * Nc floats, nothing next to the step
+            adv_d[Tb - 1:].zero_()
+            ret_d[Tb - 1:].zero_()
+            fused_stats = self.bootstrap_steps == 1 and self.burn_in_steps == 0  # the scan's own sums are those of the loss rows
+            gws = self._gae_ws.get((B, Nc))
+            if gws is None:  # zeroed once; afterwards the scan's own last workgroup resets it
+                gws = self._gae_ws[(B, Nc)] = hip.gae_scan_workspace(B, Nc, self.policy.device)
+            # PopArt: the stored values are normalised; the trace runs on de-normalised ones (mappo.py:120-124)
+            trace_value = self.policy.denormalize_value(old_value) if self.popart else old_value
+            ratio = None
+            if self.vtrace:  # importance ratio of the CURRENT parameters on every rewarding step (:130-133)
+                ratio = self._importance_ratio(net, obs, avail, L["action"], L["old_lp"], Tb - 1, B, alive, pstate, on_reset)
+            hip.gae_scan(L["reward"], trace_value, L["done"], L["truncated"], on_reset, self.discount_rate, self.gae_lambda,
+                         adv_d, ret_d, stats=stats_local if fused_stats else None, imp_ratio=ratio,
+                         workspace=gws if fused_stats else None)
+        mask_rows = on_reset[1 + lo:1 + hi]  # loss_mask = 1 - on_reset[1+burn : 1+Tb-boot]  (:260-261)
+        if not fused_stats and Nc == 1:
+            hip.masked_stats(adv_d[lo:hi], mask_rows, stats_local, mask_invert=True)
+        elif not fused_stats:  # [n, Nc] advantages under an [n] mask: per-channel sums, the mask counted once
+            cs = net.ws.get("mappo.col_stats", 3 * Nc, torch.float64)[:3 * Nc].view(Nc, 3)  # zeroed by the call
+            hip.masked_stats_cols(adv_d[lo:hi].reshape(-1, Nc), mask_rows, cs, Nc, mask_invert=True)
+            hip.fold_col_stats(cs, Nc, stats_local)
+        pending = []
+        if self._dist:
+            stats_global.copy_(stats_local)
+            # one 24-byte message instead of three (utils.py:58-61), issued asynchronously: it crosses the
+            # links while the first chunk's forward pass runs and is joined before the first loss kernel
+            if self._comm is not None:
+                self._comm.all_reduce_f64_async(stats_global)
+                pending.append(self._comm.join)
+            else:
+                pending.append(dist.all_reduce(stats_global, async_op=True).wait)
+        return adv_d, ret_d, mask_rows, stats_local[0:1], pending
+
+    def _popart_targets(self, net, ret_d, ret_rows, mask_rows, pstats_local, epoch, pending):
+        """PopArt: statistics of the value targets into ``pstats_local``, the update of the running statistics (and, in an
+        epoch that rescales, of the head), then the loss sees normalised targets (:263-264, :173-176).  Returns ``loss_ret``
+        and ``(head, head_old, head_new)`` -- None when the epoch does not rescale."""
+        Nc = net.spec.value_dim
+        hip.masked_stats_cols(ret_rows, mask_rows, pstats_local, Nc, mask_invert=True)  # zeroes pstats_local itself
+        pstats = net.ws.get("mappo.pstats", 3 * Nc, torch.float64)[:3 * Nc].view(Nc, 3)
+        pstats.copy_(pstats_local)
+        if self._dist and self._comm is not None:
+            # one message instead of utils.py:121-124's three, on the SAME communicator and side stream as the
+            # advantage statistics and the gradient buckets: one communicator orders every collective of a step
+            self._comm.all_reduce_f64_async(pstats)
+            self._comm.join()
+        elif self._dist:
+            self._join(pending)  # never two collectives of this step in flight on different streams
+            dist.all_reduce(pstats)
+        # The reference analyses the sample BEFORE this update (mappo.py:244 against :264) and rescales the head's storage
+        # in place (popart.py:50-51): the loss sees the values of the head as it was, while the backward pass, which reads
+        # the same storage, propagates through the rescaled weight, and the optimiser steps from the rescaled head.  Here
+        # the update comes first, so in an epoch that rescales the old head is kept, put back for every chunk's forward
+        # pass and replaced by the rescaled one before that chunk's backward pass.
+        heads = None
+        if self.policy.popart_rescales(epoch + 1):  # the reference counts per update, i.e. per epoch (popart.py:47-49)
+            head = self.policy.popart_head_params()
+            head_old = [net.ws.get(f"mappo.head_old{i}", p.numel())[:p.numel()] for i, p in enumerate(head)]
+            head_new = [net.ws.get(f"mappo.head_new{i}", p.numel())[:p.numel()] for i, p in enumerate(head)]
+            heads = (head, head_old, head_new)
+            for dst, p in zip(head_old, head):
+                dst.copy_(p)
+        self.policy.update_popart_from_stats(pstats, count=False, ahead=epoch)
+        if heads is not None:
+            for keep, back, p in zip(head_new, head_old, head):
+                keep.copy_(p)
+                p.copy_(back)
+        loss_ret = torch.empty_like(ret_d)
+        hip.popart_map(ret_d, net.popart_state, Nc, loss_ret, True, ns.POPART_EPS)
+        return loss_ret, heads
+
+    def _pipelines(self, net, nchunks, alone, pending):
+        """The executors and streams the row chunks of an epoch are dealt to in turn: the policy's executor on the compute
+        stream and, unless ``alone``, its twins (same parameters, own workspace / tape / gradient buffer) on streams of
+        their own, forked here.  Returns ``(nets, streams, first_sync)``; ``first_sync``: the other pipelines may only
+        start after the first chunk."""
+        nets, streams, first_sync = [net], [torch.cuda.current_stream()], False
+        if self.pipelines >= 2 and nchunks >= 2 and not alone and not net.force_explicit_conv:
+            npipe = min(self.pipelines, nchunks)
+            if self._twin is None or len(self._twin) != npipe - 1:
+                self._twin = [net.twin() for _ in range(npipe - 1)]
+                self._pipe_stream = [torch.cuda.Stream(device=self.policy.device) for _ in range(npipe - 1)]
+            # the weight-range slots are shared: they are recomputed here, before the fork.  Before the very first
+            # forward pass the layers that want one are not known yet: the other pipelines then start after the first
+            # chunk, which discovers and fills them
+            first_sync = not net.refresh_weight_ranges()
+            self._join(pending)  # the global advantage statistics: needed by every pipeline
+            for twin, pst in zip(self._twin, self._pipe_stream):
+                twin.zero_grad()
+                pst.wait_stream(streams[0])
+                nets.append(twin)
+                streams.append(pst)
+        return nets, streams, first_sync
+
+    @staticmethod
+    def _set_head(net, head, values):
+        for p, v in zip(head, values):
+            p.copy_(v)
+        net.params_changed()
+
+    def _chunk_loop(self, net, nets, streams, first_sync, chunks, rows, rnn, heads, terms, stats_global, local_n, pending):
+        """Forward / loss / backward of every row chunk, chunk ``ci`` on pipeline ``ci % len(nets)``, then the pipelines'
+        gradients summed (and, with a process group, reduced over the ranks) into ``net.grad`` on the compute stream."""
+        reducer = self._reducer if self._dist else None
+        if reducer is not None:
+            reducer.begin([x.grad for x in nets])
+        net.chunks_of_one_update(True, pipelines=len(nets))
+        for x in nets:
+            x.reset_open_accumulations()  # (an accumulation a failed update left open is not continued)
+        head, head_old, head_new = heads or (None, None, None)
+        to_new_head = None if heads is None else (lambda: self._set_head(net, head, head_new))
+        for ci, (r0, r1) in enumerate(chunks):
+            e = ci % len(nets)
+            cnet = nets[e]
+            cnet.last_chunk = ci + len(nets) >= len(chunks)  # this executor's last chunk of the update
+            if reducer is not None and cnet.last_chunk:
+                # a pipeline's gradients become final in the backward pass of ITS last chunk; a bucket goes out when
+                # every pipeline has released it (api/policy.py:219-238: what DDP's bucketing does)
+                cnet.grad_ready_hook = reducer.hook(e)
+            with torch.cuda.stream(streams[e]):
+                if heads is not None and ci > 0:
+                    self._set_head(net, head, head_old)
+                self._chunk(cnet, rows, r0, r1, rnn, terms[ci], stats_global, local_n, pending, to_new_head)
+            if first_sync and ci == 0:
+                for pst in streams[1:]:
+                    pst.wait_stream(streams[0])
+        net.chunks_of_one_update(False)
+        for x in nets:
+            x.last_chunk = None
+        if len(nets) > 1 and reducer is None:
+            for pst in streams[1:]:
+                streams[0].wait_stream(pst)
+            hip.accumulate_n(net.grad, [twin.grad for twin in nets[1:]])   # one launch, added in pipeline order
+        if reducer is not None:  # the buckets not yet launched (folding the pipelines' slices), then wait for all of them
+            for x in nets:
+                x.grad_ready_hook = None
+            reducer.finish(streams[1:])
+            for pst in streams[1:]:
+                streams[0].wait_stream(pst)
+
+    def _chunk(self, cnet, rows, r0, r1, rnn, terms, stats_global, local_n, pending, after_forward=None):
+        """Rows [r0, r1) through executor ``cnet`` on the current stream: forward, distribution, loss with its gradient
+        (its sums into ``terms``), backward into ``cnet.grad``.  ``after_forward`` runs between the forward pass and
+        everything else (the PopArt head swap)."""
+        f_obs, f_avail, f_alive, f_action, f_oldlp, f_oldv, f_adv, f_ret, f_mask, f_done, f_trunc = rows
+        n, Nc, ws, policy = r1 - r0, cnet.spec.value_dim, cnet.ws, self.policy
+        # the rows of the chunk, `per` values each (an update of one chunk takes the tensors as they are: a view costs the
+        # host as much as a launch, and the small configurations are bound by the host)
+        cut = (lambda t, per=1: t) if n == f_mask.shape[0] else (lambda t, per=1: t[r0 * per:r1 * per])
+        c_avail = None if f_avail is None else cut(f_avail)
+        c_action = cut(f_action)
+        logits, value = cnet.forward({k: cut(v) for k, v in f_obs.items()}, n, keep_tape=True, rnn=rnn)
+        if after_forward is not None:
+            after_forward()
+        logp = ws.get("new_logp", n)[:n]
+        ent = ws.get("entropy", n)[:n]
+        policy.dist_fwd(logits, c_action, c_avail, logp, ent, net=cnet)
+        policy.mask_dead(logp, None if f_alive is None else cut(f_alive))
+        d_lp = ws.get("d_logp", n)[:n]
+        d_v = ws.get("d_value", n * Nc)[:n * Nc]
+        d_ent = ws.get("d_entropy", n)[:n]
+        self._join(pending)  # the global advantage statistics: first needed here
+        hip.ppo_loss_fwd_bwd(logp, cut(f_oldlp), value.reshape(-1), cut(f_oldv, Nc), cut(f_adv, Nc), cut(f_ret, Nc), ent,
+                             cut(f_mask), self._hp, stats_global, local_n, d_lp, d_v, d_ent, terms, done=cut(f_done),
+                             truncated=cut(f_trunc), value_dim=Nc)
+        d_logits = ws.get("d_logits", logits.numel())[:logits.numel()].view_as(logits)
+        d_ls = policy.dist_bwd(logits, c_action, c_avail, d_lp, d_ent, d_logits, net=cnet)
+        cnet.backward(d_logits, d_v.view(n, Nc), d_ls)
+
+    def _clip_and_step(self, opt, net, grad_norm_out, ahead, step_scalars=None):
+        """Global-norm clip (mappo.py:272-284) folded into ``opt``'s update of the parameters from ``net.grad``, the sum over
+        the ranks turned into the mean; ``ahead`` as in ``FlatOptimizer.step``."""
+        sumsq = net.ws.get("mappo.sumsq", 1, torch.float64)[:1]  # zeroed by srl_grad_sumsq
+        hip.grad_sumsq(net.grad, sumsq)
+        opt.step(net, ahead=ahead, grad_scale=1.0 / self._world, sumsq=sumsq, grad_norm_out=grad_norm_out,
+                 max_norm=-1.0 if self.max_grad_norm is None else float(self.max_grad_norm), step_scalars=step_scalars)
+        net.params_changed()  # cached per-layer weight ranges (two-plane f16 forward products) are stale
 
 
 register('mappo', MultiAgentPPO)

@@ -235,8 +235,8 @@ def test_config4_football_per_gpu_size():
     def one_step(rows):
         net.flat.copy_(flat0)
         net.popart_state.copy_(pop0)
-        tr._m.zero_(), tr._v.zero_()
-        tr._opt_steps = 0
+        tr.optimizer.m.zero_(), tr.optimizer.v.zero_()
+        tr.optimizer.steps = 0
         tr.policy._popart_updates = 0
         net.encoder_rows = rows
         smp = synthetic.to_sample_batch(dict(sample))

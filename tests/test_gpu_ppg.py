@@ -167,7 +167,7 @@ def test_mappg_step_flow_cache_and_checkpoint():
     assert len(ppg._cache) == 1 and "ppg_policy_distance" not in r_ppg.stats and ppg.policy.version == v0 + 1
     aux_head0 = a["auxiliary_value_head.weight"].clone()
     r2 = ppg.step(synthetic.to_sample_batch(synthetic.make_sample_arrays(seed=2, **skw)))
-    assert len(ppg._cache) == 0 and ppg._aux_steps == 4   # 2 cached samples x 2 epochs
+    assert len(ppg._cache) == 0 and ppg.aux_optimizer.steps == 4   # 2 cached samples x 2 epochs
     assert ppg.policy.version == v0 + 2 + 4               # one per PPO step (:184... mappo.py:305-307 here), one per auxiliary epoch
     for k in ("ppg_auxiliary_value_loss", "ppg_value_head_loss", "ppg_policy_distance"):
         assert np.isfinite(r2.stats[k]) and r2.stats[k] >= 0, k
@@ -182,7 +182,8 @@ def test_mappg_step_flow_cache_and_checkpoint():
     assert float(st["state"][ia]["exp_avg_sq"].abs().sum()) > 0 and st["param_groups"][0]["lr"] == 5e-4
     fresh = trainer_api.make(config.Trainer("mappg", args=targs), config.Policy("actor-critic-auxiliary", args=pargs))
     fresh.load_checkpoint(ck)
-    assert fresh._aux_steps == 4 and torch.equal(fresh._aux_m, ppg._aux_m) and torch.equal(fresh._aux_v, ppg._aux_v)
+    assert fresh.aux_optimizer.steps == 4 and torch.equal(fresh.aux_optimizer.m, ppg.aux_optimizer.m)
+    assert torch.equal(fresh.aux_optimizer.v, ppg.aux_optimizer.v)
     # ... and a state dict GENERATED BY torch.optim.Adam over parameters of the reference's shapes loads (what a reference PPG
     # checkpoint carries), and ours loads into torch's
     sd = ppg.policy.get_checkpoint()["state_dict"]
@@ -196,9 +197,10 @@ def test_mappg_step_flow_cache_and_checkpoint():
         topt.step()
     ck2 = dict(ck, aux_optimizer_state_dict=topt.state_dict())
     fresh.load_checkpoint(ck2)
-    assert fresh._aux_steps == 3 and fresh._aux_lr == 2.5e-4 and fresh._aux_betas == (0.8, 0.95) and fresh._aux_eps == 1e-6
+    aux = fresh.aux_optimizer
+    assert aux.steps == 3 and aux.lr == 2.5e-4 and aux.betas == (0.8, 0.95) and aux.eps == 1e-6
     m_ref = fresh.policy.net.reference_to_flat({n: topt.state[p_]["exp_avg"] for n, p_ in zip(names, tparams)})
-    assert torch.equal(fresh._aux_m.cpu(), m_ref.cpu())
+    assert torch.equal(fresh.aux_optimizer.m.cpu(), m_ref.cpu())
     torch.optim.Adam(tparams, lr=1e-3).load_state_dict(ck["aux_optimizer_state_dict"])   # torch accepts ours
     # episode-info averages keep their names, only the PPO step's statistics get the `ppo_` prefix (:242-253)
     assert "ppo_policy_loss" in r2.stats and "ppo_grad_norm" in r2.stats and "frames" in r2.stats

@@ -292,7 +292,7 @@ def test_mappg_step_flow_continuous_actions():
     r1 = ppg.step(synthetic.to_sample_batch(synthetic.make_sample_arrays(seed=1, **skw)))
     assert len(ppg._cache) == 1 and not any(k.startswith("ppg_") for k in r1.stats) and ppg.policy.version == v0 + 1
     r2 = ppg.step(synthetic.to_sample_batch(synthetic.make_sample_arrays(seed=2, **skw)))
-    assert len(ppg._cache) == 0 and ppg._aux_steps == 2   # one stacked entry x 2 epochs
+    assert len(ppg._cache) == 0 and ppg.aux_optimizer.steps == 2   # one stacked entry x 2 epochs
     assert ppg.policy.version == v0 + 2 + 2
     for k in ("ppg_auxiliary_value_loss", "ppg_value_head_loss"):
         assert np.isfinite(r2.stats[k]) and r2.stats[k] >= 0, k
@@ -300,6 +300,7 @@ def test_mappg_step_flow_continuous_actions():
     ck = ppg.get_checkpoint()
     fresh = trainer_api.make(config.Trainer("mappg", args=targs), config.Policy("actor-critic-auxiliary", args=pargs))
     fresh.load_checkpoint(ck)
-    assert fresh._aux_steps == 2 and torch.equal(fresh._aux_m, ppg._aux_m) and torch.equal(fresh._aux_v, ppg._aux_v)
+    assert fresh.aux_optimizer.steps == 2 and torch.equal(fresh.aux_optimizer.m, ppg.aux_optimizer.m)
+    assert torch.equal(fresh.aux_optimizer.v, ppg.aux_optimizer.v)
     a, b = ppg.policy.get_checkpoint()["state_dict"], fresh.policy.get_checkpoint()["state_dict"]
     assert list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)

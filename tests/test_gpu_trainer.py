@@ -723,21 +723,25 @@ def test_cnn_step_at_the_benchmarked_dispatch(kernels, frames, monkeypatch):
         assert counts["gemm_f32"] > 0, counts
 
 
-def test_checkpoint_roundtrip_and_reuse():
-    trainer = make_trainer(C1_POLICY, dict(popart=False, optimizer_config=dict(lr=1e-3), recompute_adv_on_reuse=False))
+@pytest.mark.parametrize("name,cfg,torch_cls", [
+    ("adam", dict(lr=1e-3), torch.optim.Adam),
+    ("rmsprop", dict(lr=1e-3, momentum=0.9, centered=True), torch.optim.RMSprop),
+    ("sgd", dict(lr=1e-2, momentum=0.9, nesterov=True), torch.optim.SGD)], ids=["adam", "rmsprop", "sgd"])
+def test_checkpoint_roundtrip_and_reuse(name, cfg, torch_cls):
+    targs = dict(popart=False, optimizer=name, optimizer_config=cfg, recompute_adv_on_reuse=False)
+    trainer = make_trainer(C1_POLICY, targs)
     arrays = synthetic.make_sample_arrays(seed=1, T=16, B=4, obs_spec=synthetic.CARTPOLE_OBS, action_dims=2)
     sample = synthetic.to_sample_batch(arrays)
     trainer.step(sample)
     adv_first = sample.analyzed_result.adv.copy()
     ckpt = copy.deepcopy(trainer.get_checkpoint())
     assert set(ckpt) == {"steps", "state_dict", "optimizer_state_dict"} and ckpt["steps"] == 0
-    # torch's own Adam accepts the optimiser state (same structure as the reference's checkpoints)
+    # torch's own optimiser of that kind accepts the state (same structure as the reference's checkpoints)
     params = [torch.nn.Parameter(v.clone()) for v in ckpt["state_dict"].values()]
-    torch.optim.Adam(params, lr=1e-3).load_state_dict(ckpt["optimizer_state_dict"])
+    torch_cls(params, **cfg).load_state_dict(ckpt["optimizer_state_dict"])
     r1 = trainer.step(sample)  # re-use: advantages in the sample are kept (recompute_adv_on_reuse=False)
     assert np.array_equal(sample.analyzed_result.adv, adv_first)
-    other = make_trainer(dict(C1_POLICY, seed=99), dict(popart=False, optimizer_config=dict(lr=1e-3),
-                                                        recompute_adv_on_reuse=False))
+    other = make_trainer(dict(C1_POLICY, seed=99), targs)
     other.load_checkpoint(ckpt)
     assert other.policy.version == 0
     r2 = other.step(sample)
