@@ -131,9 +131,11 @@ __device__ __forceinline__ uint32_t h2_xor32(uint32_t x, bool upper) {
 #endif
 }
 
-#ifndef SRL_H2C_SCHED
-#define SRL_H2C_SCHED 1
-#endif
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression in its body
+template <class F, int... I> __device__ __forceinline__ void h2_static_for_(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void h2_static_for(F&& f) { h2_static_for_(f, std::make_integer_sequence<int, N>{}); }
 
 // k-blocks (tap, channel block) of a block's MFMA chain whose tap row is in the row mask RM (bit r = taps r * TPR .. + TPR - 1)
 template <int NKB> struct H2ActiveKb { int n; int kb[NKB]; };
@@ -142,6 +144,30 @@ template <int RM, int NTAP, int CB, int TPR> constexpr H2ActiveKb<NTAP * CB> h2_
   for (int kb = 0; kb < NTAP * CB; ++kb)
     if ((RM >> ((kb / CB) / TPR)) & 1) a.kb[a.n++] = kb;
   return a;
+}
+// Tap rows that can contribute to block bi of an image, and how many taps make a row.  A data gradient's first and last blocks
+// see only zero border through some rows (conv3's 9 x 9 outputs on the 11-wide grid skip 12 of their 63 tap-blocks):
+//   conv3 dgrad: outputs 16 bi .. + 15 of the 9-wide image; tap row ky reads dz row y - ky, which exists for 0 <= y - ky <= 6:
+//     block 0 (y = 0, 1) never through ky = 2, block 4 (y = 7, 8) never through ky = 0, block 5 (y = 8) only through ky = 2;
+//   conv2 dgrad: outputs 16 bi .. + 15 of the 10-wide class image; tap row dy reads dz row a - dy, which exists for
+//     0 <= a - dy <= 8: block 6 (a = 9 alone) only through dy = 1;
+//   forward kernels: one row = everything, nothing is skipped.
+template <int ID> constexpr int h2c_tpr() { return ID == H2C_D3 ? 3 : (ID == H2C_D2 ? 2 : H2Geo<ID>::NTAP); }
+template <int ID> constexpr int h2c_row_mask(int bi) {
+  if (ID == H2C_D3) return bi == 0 ? 0b011 : (bi == 4 ? 0b110 : (bi == 5 ? 0b100 : 0b111));
+  if (ID == H2C_D2) return bi == 6 ? 0b10 : 0b11;
+  return (1 << 30) - 1;
+}
+template <int ID> constexpr int h2c_nkb(int bi) {   // active k-blocks of block bi
+  int n = 0;
+  for (int kb = 0; kb < H2Geo<ID>::NTAP * H2Geo<ID>::CB; ++kb)
+    if ((h2c_row_mask<ID>(bi) >> ((kb / H2Geo<ID>::CB) / h2c_tpr<ID>())) & 1) ++n;
+  return n;
+}
+template <int ID> constexpr int h2c_kbs_before(int jb0, int jj, int nb_img) {   // active k-blocks of blocks jb0 .. jb0 + jj - 1 of a batch
+  int g = 0;
+  for (int k = 0; k < jj; ++k) g += h2c_nkb<ID>((jb0 + k) % nb_img);
+  return g;
 }
 
 template <int ID, int NSLOT>
@@ -326,12 +352,13 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
   float amax = 0.f;
 
   // ---- the deferred epilogue of a block: what the NEXT block's MFMA chain runs beside
-  struct Meta {
-    uint32_t pixoff;   // pixel index of this lane's position inside its image
-    bool ok;           // lane holds a real output
+  struct Meta {         // (no padding bytes: the struct is copied from block to block, and a copied hole is a stack slot)
     long img;          // image (uniform)
-    uint32_t bits[CGW];   // data gradients: the ReLU-derivative bits of this lane's four channels per channel group (bits 0..3)
+    uint32_t pixoff;   // pixel index of this lane's position inside its image
+    uint32_t ok;       // lane holds a real output
+    uint32_t bits[2];  // data gradients: the ReLU-derivative bits of this lane's four channels per channel group (bits 0..3)
   };
+  static_assert(CGW <= 2 && sizeof(Meta) == 24, "");
   // Stores go through buffer descriptors whose extent is the tensor: a lane without a real output uses an out-of-range offset,
   // which the hardware drops -- no divergent branch in the epilogue.
   // The image's base goes into the VECTOR offset and soffset is the constant 0, on purpose: a buffer store of more than 64 bits
@@ -343,151 +370,131 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
   const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)(a.n * OIMGB), 0x00020000);
   const __amdgpu_buffer_rsrc_t r_mo = __builtin_amdgcn_make_buffer_rsrc(MASK_OUT ? (void*)a.mask_out : a.out, 0, (int)(a.n * MIMGB), 0x00020000);
   constexpr uint32_t OOB = 0x80000000u;
-  auto epilogue1 = [&](const h2_f32x4& acc, const Meta& m, const float (&bqc)[4], uint32_t lane_out_c, uint32_t lane_mout_c, uint32_t mbits) {
-    float v[4];
-    constexpr bool CLAMP = ID == H2C_F2 || ID == H2C_F3;   // data gradients take no activation (srl_h2_conv checks)
+  // The epilogue of channel group c in pieces, so that the chain below can give each piece a gap of its own: piece 0 scale + bias +
+  // clamp (+ the ReLU-derivative AND) and amax, piece 1 the split, the exchange and the store, piece 2 (forward kernels) the sign
+  // nibbles' byte.  ev carries a group's four values from piece 0 to the others.  Every value's arithmetic is the one-piece
+  // epilogue's.
+  constexpr int EPP = MASK_OUT ? 3 : 2;     // pieces per channel group
+  constexpr int NEP = CGW * EPP;            // ... per block
+  float ev[CGW][4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = CLAMP ? fmaxf(acc[r] * inv + bqc[r], lo) : acc[r] * inv + bqc[r];
+  for (int c = 0; c < CGW; ++c) ev[c][0] = ev[c][1] = ev[c][2] = ev[c][3] = 0.f;
+  auto epi_piece = [&](int k, const h2_f32x4 (&accs)[CGW], const Meta& m) {
+    const int c = k / EPP, q = k - c * EPP;
+    float (&v)[4] = ev[c];
     const bool ok = m.ok;
     const uint32_t img32 = (uint32_t)m.img;
-    if (MASK_IN) {   // bit r -> all ones / zero (v_bfe_i32), and: two vector instructions per value
+    typedef uint32_t h2_u32x4 __attribute__((ext_vector_type(4)));
+#if __has_builtin(__builtin_amdgcn_permlane32_swap)
+    typedef unsigned h2_u32x2 __attribute__((ext_vector_type(2)));
+#endif
+    if (q == 0) {
+      constexpr bool CLAMP = ID == H2C_F2 || ID == H2C_F3;   // data gradients take no activation (srl_h2_conv checks)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = __uint_as_float(__float_as_uint(v[r]) & (uint32_t)__builtin_amdgcn_sbfe((int)mbits, r, 1));
-    }
-    {
+      for (int r = 0; r < 4; ++r) v[r] = CLAMP ? fmaxf(accs[c][r] * inv + bq[c][r], lo) : accs[c][r] * inv + bq[c][r];
+      if (MASK_IN) {   // bit r -> all ones / zero (v_bfe_i32), and: two vector instructions per value
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = __uint_as_float(__float_as_uint(v[r]) & (uint32_t)__builtin_amdgcn_sbfe((int)m.bits[c], r, 1));
+      }
       // (vector instructions cost what matrix instructions cost here, DESIGN 4: max3, and the exchanges below without selects)
       const float m3 = __builtin_fmaxf(__builtin_fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
       const float m5 = __builtin_fmaxf(__builtin_fmaxf(m3, fabsf(v[3])), amax);
       amax = m.ok ? m5 : amax;
-    }
-    const uint32_t ooff = ok ? m.pixoff * PIXB + lane_out_c : OOB;
-    typedef uint32_t h2_u32x4 __attribute__((ext_vector_type(4)));
-    if (ROUTED) {
-      h2_u32x4 d = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-      __builtin_amdgcn_raw_buffer_store_b128(d, r_out, ooff + img32 * (uint32_t)OIMGB, 0, 0);
-    } else {
-      // two pieces of the four values; lanes (quad, quad ^ 2) = (L, L + 32) complete each other's 16-byte chunks: the lower one
-      // ends up with the first pieces of elements 0..7 of group g_out, the upper one with the second pieces.
-      // v_permlane32_swap a, b exchanges a's upper 32 lanes with b's lower 32: with a = first pieces, b = second pieces, the
-      // lower lane holds (own first, partner's first) and the upper lane (partner's second, own second) afterwards -- no selects.
-      uint32_t h0a, h0b, h1a, h1b;
-      h2_split_pair(v[0], v[1], oscale, h0a, h1a);
-      h2_split_pair(v[2], v[3], oscale, h0b, h1b);
-      h2_u32x4 chunk;
+    } else if (q == 1) {
+      const uint32_t ooff = ok ? m.pixoff * PIXB + lane_out[c] : OOB;
+      if (ROUTED) {
+        h2_u32x4 d = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        __builtin_amdgcn_raw_buffer_store_b128(d, r_out, ooff + img32 * (uint32_t)OIMGB, 0, 0);
+      } else {
+        // two pieces of the four values; lanes (quad, quad ^ 2) = (L, L + 32) complete each other's 16-byte chunks: the lower one
+        // ends up with the first pieces of elements 0..7 of group g_out, the upper one with the second pieces.
+        // v_permlane32_swap a, b exchanges a's upper 32 lanes with b's lower 32: with a = first pieces, b = second pieces, the
+        // lower lane holds (own first, partner's first) and the upper lane (partner's second, own second) afterwards -- no selects.
+        uint32_t h0a, h0b, h1a, h1b;
+        h2_split_pair(v[0], v[1], oscale, h0a, h1a);
+        h2_split_pair(v[2], v[3], oscale, h0b, h1b);
+        h2_u32x4 chunk;
 #if __has_builtin(__builtin_amdgcn_permlane32_swap)
-      typedef unsigned h2_u32x2 __attribute__((ext_vector_type(2)));
-      const h2_u32x2 sa = __builtin_amdgcn_permlane32_swap(h0a, h1a, false, false);
-      const h2_u32x2 sb = __builtin_amdgcn_permlane32_swap(h0b, h1b, false, false);
-      chunk[0] = sa[0]; chunk[1] = sb[0]; chunk[2] = sa[1]; chunk[3] = sb[1];
+        const h2_u32x2 sa = __builtin_amdgcn_permlane32_swap(h0a, h1a, false, false);
+        const h2_u32x2 sb = __builtin_amdgcn_permlane32_swap(h0b, h1b, false, false);
+        chunk[0] = sa[0]; chunk[1] = sb[0]; chunk[2] = sa[1]; chunk[3] = sb[1];
 #else
-      const uint32_t r0 = h2_xor32(up ? h0a : h1a, up), r1 = h2_xor32(up ? h0b : h1b, up);
-      chunk[0] = up ? r0 : h0a; chunk[1] = up ? r1 : h0b; chunk[2] = up ? h1a : r0; chunk[3] = up ? h1b : r1;
+        const uint32_t r0 = h2_xor32(up ? h0a : h1a, up), r1 = h2_xor32(up ? h0b : h1b, up);
+        chunk[0] = up ? r0 : h0a; chunk[1] = up ? r1 : h0b; chunk[2] = up ? h1a : r0; chunk[3] = up ? h1b : r1;
 #endif
-      __builtin_amdgcn_raw_buffer_store_b128(chunk, r_out, ooff + img32 * (uint32_t)OIMGB, 0, 0);
-      if (MASK_OUT) {
-        uint32_t nib = (v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u);
-#if __has_builtin(__builtin_amdgcn_permlane32_swap)
-        const h2_u32x2 sn = __builtin_amdgcn_permlane32_swap(nib, nib, false, false);   // lower lanes: (own, partner's)
-        const uint32_t byte = sn[0] | (sn[1] << 4);
-#else
-        const uint32_t byte = nib | (h2_xor32(nib, up) << 4);
-#endif
-        const uint32_t moff = (ok && !up) ? m.pixoff * (GE::OCH / 8) + lane_mout_c : OOB;
-        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)byte, r_mo, moff + img32 * (uint32_t)MIMGB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(chunk, r_out, ooff + img32 * (uint32_t)OIMGB, 0, 0);
       }
+    } else {
+      uint32_t nib = (v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u);
+#if __has_builtin(__builtin_amdgcn_permlane32_swap)
+      const h2_u32x2 sn = __builtin_amdgcn_permlane32_swap(nib, nib, false, false);   // lower lanes: (own, partner's)
+      const uint32_t byte = sn[0] | (sn[1] << 4);
+#else
+      const uint32_t byte = nib | (h2_xor32(nib, up) << 4);
+#endif
+      const uint32_t moff = (ok && !up) ? m.pixoff * (GE::OCH / 8) + lane_mout[c] : OOB;
+      __builtin_amdgcn_raw_buffer_store_b8((unsigned char)byte, r_mo, moff + img32 * (uint32_t)MIMGB, 0, 0);
     }
-  };
-  auto epilogue = [&](const h2_f32x4 (&accs)[CGW], const Meta& m) {
-#pragma unroll
-    for (int c = 0; c < CGW; ++c) epilogue1(accs[c], m, bq[c], lane_out[c], lane_mout[c], m.bits[c]);
   };
 
-  // ---- one block: 3 NKB MFMAs on the block's entries, fragments fetched PD k-blocks ahead (LDS latency is ~4-8 MFMAs), with
-  // the PREVIOUS block's epilogue inside the chain -- early in it for wavefronts 0-3, in the middle for wavefronts 4-7: the two
-  // wavefronts of a SIMD (w, w + 4) run the same code between the same barriers, and what overlaps one's vector work and
-  // stores is the other's matrix work.  (sched_group_barrier was tried for a per-instruction interleave: with the directives
-  // in the block the compiler placed a vector write to a store's data register directly behind the store -- a missing wait
-  // state, wrong results -- so the order is written out in the source instead.)
-  // (conv2's data gradient, two channel groups per wavefront: one k-block ahead -- with two, the two instantiations of the
-  // position half below spill 20 bytes and the kernel runs at 352 us instead of 286)
+  // ---- one batch of one position half: its blocks' MFMA chains as ONE pinned instruction stream (sched_barrier(0) behind every
+  // MFMA: the interleave below is the schedule, as in h2wgrad_kernel).  A block is 3 NKB MFMAs (per channel group) on the block's
+  // 16 entries; k-block i's fragment pair feeds one MFMA triple per channel group.
+  //   * Fragments: a ring of PD + 1 register sets that runs THROUGH the blocks of the batch.  The pair of k-block i + PD is read
+  //     behind the first and the second MFMA of k-block i; in a block's last PD k-blocks those are the first pairs of the NEXT
+  //     block (the jj loop is unrolled: its slot offset, entries and row mask are constants, a dense enumeration's per-lane row
+  //     skip is formed one gap earlier).  Only a batch's first block opens with a burst behind the barrier.  Every address is one
+  //     lane register + immediate: conv2 forward's swizzle table is added to the SLOT once per batch, the block's offset
+  //     (a multiple of 2 KB) rides in the immediate.
+  //   * The PREVIOUS block's epilogue, in pieces (epi_piece), one per gap behind a third MFMA: from k-block 1 on for wavefronts
+  //     0-3, from the middle on for wavefronts 4-7 -- the two wavefronts of a SIMD (w, w + 4) run the same code between the same
+  //     barriers, and what overlaps one's vector work and stores is the other's matrix work.  What a short block leaves over goes
+  //     into its last gap.  (sched_group_barrier was tried for a per-instruction interleave: with the directives in the block the
+  //     compiler placed a vector write to a store's data register directly behind the store -- a missing wait state, wrong
+  //     results -- so the order is written out in the source instead.)
+  //   * This block's Meta (entry arithmetic, the mask bits' LDS read) behind the last but one triple.
+  // Per accumulator the MFMA sequence (operands, order) is what the compiler-scheduled version had: results are bit-identical.
+  // Measured (LAB_NOTEBOOK 15): with the DMA block at the top this stream is level with the compiler's schedule (+5 / -4 / 0 / -4 us);
+  // what it is kept for is the DMA block's place in it (below): -22 / -5 / -18 / -13 us per 16 384-image chunk in the update.
+  // (conv2's data gradient, two channel groups per wavefront: one k-block ahead -- with two the kernel spills)
   constexpr int PD = CB == 1 ? 3 : (ID == H2C_D2 ? 1 : 2);
+  constexpr int TPR = h2c_tpr<ID>();
+  static_assert(ID != H2C_D3 || (NB_IMG == 6 && GE::GW == 11 && GE::OW == 9 && GE::NTAP == 9 && GE::SRC != H2S_ROWSWZ), "h2c_row_mask: conv3's");
+  static_assert(ID != H2C_D2 || (NB_IMG == 7 && GE::GW == 11 && GE::OW == 10 && GE::NTAP == 4), "h2c_row_mask: conv2's");
+  static_assert(GE::SRC != H2S_ROWSWZ || (GE::G == 1 && ((NB_IMG - 1) * 16 + GE::tap_u(GE::NTAP - 1) + 8) * 128 < 65536), "table register + immediate");
   const bool late = wid >= 4;
-  // rows_c: the tap rows that can contribute to this block (a data gradient's first and last blocks of an image see only
-  // zero border through some: conv3's 9 x 9 outputs on the 11-wide grid skip 12 of their 63 tap-blocks); all rows otherwise
-  auto block = [&](auto rows_c, const uint8_t* xb, h2_f32x4 (&pacc)[CGW], Meta& pm, const Meta& nm) {
-    constexpr int TPR = ID == H2C_D3 ? 3 : (ID == H2C_D2 ? 2 : GE::NTAP);   // taps per tap row (one row = everything, where nothing is skipped)
-    constexpr H2ActiveKb<NKB> AK = h2_active_kbs<decltype(rows_c)::value, GE::NTAP, CB, TPR>();
-    h2_f32x4 acc[CGW];
-#pragma unroll
-    for (int c = 0; c < CGW; ++c) acc[c] = h2_f32x4{0.f, 0.f, 0.f, 0.f};
-    h2_f16x8 xr[PD + 1][2];
-    const uint8_t* tq0[8];
-    const uint8_t* tq1[8];
-    if (GE::SRC == H2S_ROWSWZ) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        tq0[u] = xb + swz_d0[u];
-        tq1[u] = xb + swz_d1[u];
-      }
-    }
-    auto fetch = [&](int i) {   // i-th active k-block
-      const int kb = AK.kb[i];
-      const int t = kb / CB, c = kb - t * CB;
-      if (GE::SRC == H2S_ROWSWZ) {
-        const int U = GE::tap_u(t), u8 = U & 7;
-        xr[i % (PD + 1)][0] = *reinterpret_cast<const h2_f16x8*>(tq0[u8] + (U - u8) * 128);
-        xr[i % (PD + 1)][1] = *reinterpret_cast<const h2_f16x8*>(tq1[u8] + (U - u8) * 128);
-      } else {
-        const int off = (c * 8) * PLANE_B + GE::tap_u(t) * 16;
-        xr[i % (PD + 1)][0] = *reinterpret_cast<const h2_f16x8*>(xb + off);
-        xr[i % (PD + 1)][1] = *reinterpret_cast<const h2_f16x8*>(xb + off + PLANE_B);
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < PD; ++i) fetch(i);
-#pragma unroll
-    for (int i = 0; i < AK.n; ++i) {
-      if (i + PD < AK.n) fetch(i + PD);
-      if (i == 1 && !late) epilogue(pacc, pm);
-      if (i == AK.n / 2 + 1 && late) epilogue(pacc, pm);
-      const int kb = AK.kb[i];
-      const int t = kb / CB, c = kb - t * CB;
-      const int kw = GE::tap_k(t) * CB + c;
-#pragma unroll
-      for (int cc = 0; cc < CGW; ++cc) {
-        acc[cc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[cc][kw][1], xr[i % (PD + 1)][0], acc[cc], 0, 0, 0);
-        acc[cc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[cc][kw][0], xr[i % (PD + 1)][1], acc[cc], 0, 0, 0);
-        acc[cc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[cc][kw][0], xr[i % (PD + 1)][0], acc[cc], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < CGW; ++c) pacc[c] = acc[c];
-    pm = nm;
-  };
+  // The next batch's DMA instructions (NDW per wavefront, one block; the slot is free from the batch's barrier on, so any point
+  // before the next batch's vmcnt(0) is the same to the slot protocol): one half of the wavefronts issues its block at the top of
+  // the batch, the other half behind its triple DMA_AT -- the two wavefronts of a SIMD (w, w + 4) then do not both stand in the
+  // DMA path's queue while the matrix pipe idles (h2tn.h's and h2wgrad_kernel's finding).  Which half and where: measured per
+  // instantiation (LAB_NOTEBOOK 15); conv2 forward holds back wavefronts 4-7, the others wavefronts 0-3.
+  constexpr bool DMA_HOLD_LATE = ID == H2C_F2;
+  constexpr int DMA_AT = ID == H2C_F2 || ID == H2C_F3 ? 16 : 24;
 
   h2_f32x4 pacc[CGW];
 #pragma unroll
   for (int c = 0; c < CGW; ++c) pacc[c] = h2_f32x4{0.f, 0.f, 0.f, 0.f};
   Meta pm = {};
-  pm.ok = false;
-  // this lane's entry inside a block, walked block by block: (oy, ox) of entry 16 bi + p
+  pm.ok = 0u;
   // phc_c: the wavefront's position half as a constant (two instantiations, chosen by a uniform branch per batch): every block's
   // index inside its image is then known at compile time, and with it the entry arithmetic and the row masks (conv2 forward
   // 302 -> 277 us, conv3 forward 198 -> 188, conv3 data gradient 278 -> 267, conv2 data gradient 290 -> 286)
-  auto compute = [&](auto phc_c, long b, int s) {
+  auto compute = [&](auto phc_c, long b, int s, long bn, int sn) {
     constexpr int phc = decltype(phc_c)::value;
+    constexpr int NJ = NBT / NPH;
+    constexpr int ESZ = GE::SRC == H2S_ROWSWZ ? 128 : 16;   // bytes from one entry to the next
     const uint8_t* slot = lds + s * SLOTM + lane_base;
     const uint8_t* mreg = lds + s * SLOTM + SLOT;
-#pragma unroll
-    for (int jj = 0; jj < NBT / NPH; ++jj) {   // unrolled: a block's accumulators are handed to the next block's chain by renaming
-      const int jb = phc * (NBT / NPH) + jj;
-      const int il = jb / NB_IMG, bi = jb - il * NB_IMG;
+    // this lane's entry inside block bi: (oy, ox) of entry 16 bi + p
+    constexpr int EW = GE::DENSE ? GE::OW : GE::GW;   // entries per row of the enumeration
+    auto oy_of = [&](int bi) { return ((bi * 16 + p) * (65536 / EW + 1)) >> 16; };   // e < 128
+    auto meta_of = [&](int il, int bi) {
       const int e = bi * 16 + p;
-      constexpr int EW = GE::DENSE ? GE::OW : GE::GW;   // entries per row of the enumeration
-      const int oy = (e * (65536 / EW + 1)) >> 16, ox = e - oy * EW;   // e < 128
+      const int oy = oy_of(bi), ox = e - oy * EW;
       Meta nm;
       nm.img = b * GE::G + il;
-      nm.ok = ox < GE::OW && oy < GE::OH && nm.img < a.n;
+      nm.ok = ox < GE::OW && oy < GE::OH && nm.img < a.n ? 1u : 0u;
+      nm.bits[0] = nm.bits[1] = 0u;
       nm.pixoff = (uint32_t)(oy * pix_step_y + ox * pix_step_x);
 #pragma unroll
       for (int c = 0; c < CGW; ++c) {
@@ -498,50 +505,149 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
           else nm.bits[c] = *reinterpret_cast<const uint32_t*>(mreg + il * MIMGB + (po + mi_pix[c]) * 4) >> mi_shift[c];
         }
       }
-      // (dense enumeration: output (oy, ox) sits at grid entry oy * GW + ox = e + oy * (GW - OW))
-      const uint8_t* xb_ = slot + (il * GE::NPIX_L + bi * 16) * (GE::SRC == H2S_ROWSWZ ? 128 : 16) +
-                           (GE::DENSE ? oy * ((GE::GW - GE::OW) * 16) : 0);
-      if (ID == H2C_D3) {
-        // output rows of block bi: outputs 16 bi .. + 15 of the 9-wide image; tap row ky reads dz row y - ky, which exists for
-        // 0 <= y - ky <= 6: block 0 (y = 0, 1) never through ky = 2, block 4 (y = 7, 8) never through ky = 0, block 5 (y = 8) only
-        // through ky = 2
-        static_assert(ID != H2C_D3 || (NB_IMG == 6 && GE::GW == 11 && GE::OW == 9 && GE::NTAP == 9 && GE::SRC != H2S_ROWSWZ),
-                      "row masks below are conv3's");
-        if (bi == 0) block(std::integral_constant<int, 0b011>{}, xb_, pacc, pm, nm);
-        else if (bi == 4) block(std::integral_constant<int, 0b110>{}, xb_, pacc, pm, nm);
-        else if (bi == 5) block(std::integral_constant<int, 0b100>{}, xb_, pacc, pm, nm);
-        else block(std::integral_constant<int, 0b111>{}, xb_, pacc, pm, nm);
-      } else if (ID == H2C_D2) {
-        // class-grid rows of block bi: outputs 16 bi .. + 15 of the 10-wide class image; tap row dy reads dz row a - dy, which
-        // exists for 0 <= a - dy <= 8: block 6 (a = 9 alone) only through dy = 1
-        static_assert(ID != H2C_D2 || (NB_IMG == 7 && GE::GW == 11 && GE::OW == 10 && GE::NTAP == 4), "row mask below is conv2's");
-        if (bi == 6) block(std::integral_constant<int, 0b10>{}, xb_, pacc, pm, nm);
-        else block(std::integral_constant<int, 0b11>{}, xb_, pacc, pm, nm);
-      } else {
-        block(std::integral_constant<int, (1 << 30) - 1>{}, xb_, pacc, pm, nm);
+      return nm;
+    };
+    // the lane register of a block's reads (dense enumeration: output (oy, ox) sits at grid entry oy * GW + ox = e + oy * (GW - OW));
+    // the block's first entry, (il * NPIX_L + bi * 16) * ESZ, is part of the immediate
+    auto xbase_of = [&](int bi) -> const uint8_t* { return GE::DENSE ? slot + oy_of(bi) * ((GE::GW - GE::OW) * 16) : slot; };
+    const uint8_t* tq0[8];
+    const uint8_t* tq1[8];
+    if (GE::SRC == H2S_ROWSWZ) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        tq0[u] = slot + swz_d0[u];
+        tq1[u] = slot + swz_d1[u];
       }
     }
+    h2_f16x8 xr[PD + 1][2];
+    // conv3 forward: tap (2, 0) of block bi and tap (0, 2) of block bi + 1 of the same image are the same 16 entries
+    // (16 bi + 18 = 16 (bi + 1) + 2).  They are read once, into a set of their own that the ring does not touch (the compiler
+    // found the same reuse in the unpinned code: the LDS instruction count is what it was).
+    constexpr bool KEEP = ID == H2C_F3;
+    constexpr int KEEP_OUT_T = 6, KEEP_IN_T = 2;
+    static_assert(!KEEP || (GE::tap_u(KEEP_OUT_T) == 16 + GE::tap_u(KEEP_IN_T) && KEEP_OUT_T * CB - PD > KEEP_IN_T * CB + CB - 1 && KEEP_IN_T * CB >= PD),
+                  "kept taps: same entries, re-read only behind their second use, never part of a burst");
+    h2_f16x8 xk[CB][2];
+    auto fetch = [&](int kb, int r, int h, const uint8_t* xb, int boff, bool has_pred, bool has_succ) {   // piece h of k-block kb into ring set r
+      const int t = kb / CB, c = kb - t * CB;
+      if (KEEP && has_pred && t == KEEP_IN_T) return;   // the previous block's kept fragment
+      if (KEEP && has_succ && t == KEEP_OUT_T) {
+        xk[c][h] = *reinterpret_cast<const h2_f16x8*>(xb + boff + (c * 8 + h) * PLANE_B + GE::tap_u(t) * 16);
+        return;
+      }
+      if (GE::SRC == H2S_ROWSWZ) {
+        const int U = GE::tap_u(t), u8 = U & 7;
+        if (h == 0) xr[r][0] = *reinterpret_cast<const h2_f16x8*>(tq0[u8] + boff + (U - u8) * 128);
+        else xr[r][1] = *reinterpret_cast<const h2_f16x8*>(tq1[u8] + boff + (U - u8) * 128);
+      } else {
+        xr[r][h] = *reinterpret_cast<const h2_f16x8*>(xb + boff + (c * 8 + h) * PLANE_B + GE::tap_u(t) * 16);
+      }
+    };
+
+    const bool dma = bn < nbatch;
+    if (dma && late != DMA_HOLD_LATE) issue(bn, sn);
+    const uint8_t* xbc = xbase_of((phc * NJ) % NB_IMG);
+    {   // the batch's burst: nothing of it may be read before its barrier
+      constexpr int il0 = (phc * NJ) / NB_IMG, bi0 = (phc * NJ) % NB_IMG;
+      constexpr H2ActiveKb<NKB> AK0 = h2_active_kbs<h2c_row_mask<ID>(bi0), GE::NTAP, CB, TPR>();
+#pragma unroll
+      for (int i = 0; i < PD; ++i) {
+        fetch(AK0.kb[i], i, 0, xbc, (il0 * GE::NPIX_L + bi0 * 16) * ESZ, false, false);
+        fetch(AK0.kb[i], i, 1, xbc, (il0 * GE::NPIX_L + bi0 * 16) * ESZ, false, false);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    h2_static_for<NJ>([&](auto jj_c) {   // unrolled: a block's accumulators are handed to the next block's chain by renaming
+      constexpr int jj = decltype(jj_c)::value;
+      constexpr int jb = phc * NJ + jj, il = jb / NB_IMG, bi = jb - il * NB_IMG;
+      constexpr bool LASTB = jj + 1 == NJ;
+      constexpr int jbn = LASTB ? jb : jb + 1, iln = jbn / NB_IMG, bin = jbn - iln * NB_IMG;
+      constexpr H2ActiveKb<NKB> AK = h2_active_kbs<h2c_row_mask<ID>(bi), GE::NTAP, CB, TPR>();
+      constexpr H2ActiveKb<NKB> AKN = h2_active_kbs<h2c_row_mask<ID>(bin), GE::NTAP, CB, TPR>();
+      constexpr int N = AK.n, NT = N * CGW;                      // k-blocks, MFMA triples of this block
+      static_assert(N >= PD + 1 && AKN.n >= PD, "the ring reaches one block ahead at most");
+      constexpr int G0 = h2c_kbs_before<ID>(phc * NJ, jj, NB_IMG);   // k-blocks of the batch before this block: the ring's phase
+      constexpr int boff = (il * GE::NPIX_L + bi * 16) * ESZ, boffn = (iln * GE::NPIX_L + bin * 16) * ESZ;
+      constexpr int E_EARLY = CGW, E_LATE = (N / 2 + 1) * CGW;   // first triple with an epilogue piece behind it
+      constexpr int XN_AT = (N - PD - 1) * CGW;                  // the next block's lane register: one k-block before its first read
+      constexpr int META_AT = NT - 2;
+      constexpr bool HAS_PRED = KEEP && jj > 0 && bi > 0, HAS_SUCC = KEEP && !LASTB && iln == il && bin == bi + 1;
+      h2_f32x4 acc[CGW];
+#pragma unroll
+      for (int c = 0; c < CGW; ++c) acc[c] = h2_f32x4{0.f, 0.f, 0.f, 0.f};
+      const uint8_t* xbn = xbc;
+      Meta nm = pm;   // (set behind triple META_AT)
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int kb = AK.kb[i];
+        const int t = kb / CB, c = kb - t * CB;
+        const int kw = GE::tap_k(t) * CB + c;
+        const int r = (G0 + i) % (PD + 1);
+        const int ip = i + PD, rp = (G0 + ip) % (PD + 1);
+        const bool pf_here = ip < N, pf_next = ip >= N && !LASTB;
+        const bool kept = (HAS_PRED && t == KEEP_IN_T) || (HAS_SUCC && t == KEEP_OUT_T);
+        const h2_f16x8& x0 = kept ? xk[c][0] : xr[r][0];
+        const h2_f16x8& x1 = kept ? xk[c][1] : xr[r][1];
+#pragma unroll
+        for (int cc = 0; cc < CGW; ++cc) {
+          const int T = i * CGW + cc;
+          acc[cc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[cc][kw][1], x0, acc[cc], 0, 0, 0);
+          if (cc == 0) {
+            if (pf_here) fetch(AK.kb[ip], rp, 0, xbc, boff, HAS_PRED, HAS_SUCC);
+            else if (pf_next) fetch(AKN.kb[ip - N], rp, 0, xbn, boffn, false, false);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          acc[cc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[cc][kw][0], x1, acc[cc], 0, 0, 0);
+          if (cc == 0) {
+            if (pf_here) fetch(AK.kb[ip], rp, 1, xbc, boff, HAS_PRED, HAS_SUCC);
+            else if (pf_next) fetch(AKN.kb[ip - N], rp, 1, xbn, boffn, false, false);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          acc[cc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[cc][kw][0], x0, acc[cc], 0, 0, 0);
+          if (T == XN_AT && !LASTB && GE::DENSE) xbn = xbase_of(bin);
+          if (T == META_AT) nm = meta_of(il, bi);
+          if (T >= E_EARLY && T - E_EARLY < NEP && !late) {
+#pragma unroll
+            for (int k = T - E_EARLY; k < (T == NT - 1 ? NEP : T - E_EARLY + 1); ++k) epi_piece(k, pacc, pm);
+          }
+          if (T >= E_LATE && T - E_LATE < NEP && late) {
+#pragma unroll
+            for (int k = T - E_LATE; k < (T == NT - 1 ? NEP : T - E_LATE + 1); ++k) epi_piece(k, pacc, pm);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (G0 * CGW + T == DMA_AT) {
+            if (dma && late == DMA_HOLD_LATE) issue(bn, sn);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CGW; ++c) pacc[c] = acc[c];
+      pm = nm;
+      xbc = xbn;
+    });
   };
 
   // ring of NSLOT slots: batches b, b + grid, ... of this workgroup; the DMA of the batch NSLOT-1 ahead is issued right
   // after the barrier that frees its slot.  The last block's stores of a batch are issued inside the NEXT batch's first
   // block, so the vmcnt(0) at the top of a batch rarely waits for a store.
   long b = blockIdx.x;
+  const long gstep = gridDim.x;   // read once: behind the loop's asm statements it would be loaded again per batch
 #pragma unroll
   for (int s = 0; s < NSLOT - 1; ++s)
-    if (b + (long)s * gridDim.x < nbatch) issue(b + (long)s * gridDim.x, s);
+    if (b + (long)s * gstep < nbatch) issue(b + (long)s * gstep, s);
   int s_cur = 0, s_nxt = NSLOT - 1;
-  for (; b < nbatch; b += gridDim.x) {
+  for (; b < nbatch; b += gstep) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    const long bn = b + (long)(NSLOT - 1) * gridDim.x;
-    if (bn < nbatch) issue(bn, s_nxt);
-    if (ph == 0) compute(std::integral_constant<int, 0>{}, b, s_cur);
-    else compute(std::integral_constant<int, NPH - 1>{}, b, s_cur);
+    const long bn = b + (long)(NSLOT - 1) * gstep;
+    if (ph == 0) compute(std::integral_constant<int, 0>{}, b, s_cur, bn, s_nxt);
+    else compute(std::integral_constant<int, NPH - 1>{}, b, s_cur, bn, s_nxt);
     s_cur = s_cur + 1 == NSLOT ? 0 : s_cur + 1;
     s_nxt = s_nxt + 1 == NSLOT ? 0 : s_nxt + 1;
   }
-  epilogue(pacc, pm);
+#pragma unroll
+  for (int k = 0; k < NEP; ++k) epi_piece(k, pacc, pm);
   {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
