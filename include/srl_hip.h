@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SRL_HIP_ABI_VERSION 21
+#define SRL_HIP_ABI_VERSION 22
 
 int srl_abi_version(void);
 const char* srl_last_error(void);
@@ -378,8 +378,8 @@ typedef struct srl_gemm_desc {
   uint32_t* mask_out;
   const uint32_t* dact_mask;
   /* B is srl_presplit's output instead of float32 (same shape, pitch and orientation): accepted only where the product takes
-   * the two-piece kernel -- both ranges given, M > 64, N > 64, K >= 64, aligned operands, and not the small-product path (more
-   * than 65 536 outputs or K > 512).  b_absmax must be the float srl_presplit was given. */
+   * the two-piece kernel (srl_gemm_family() == SRL_FAMILY_TWO) -- both ranges given, M > 64, N > 64, K >= 64, aligned operands,
+   * and not the small-product path (more than 65 536 outputs or K > 512).  b_absmax must be the float srl_presplit was given. */
   int32_t b_presplit;
   /* B (b_kmajor 1, N a multiple of 32, ldb == N) is h2p rows (the pre-split format of the srl_h2_* kernels) under this scale
    * (device float) instead of float32: a weight-gradient product dZ^T X whose X was never written as float32.  Needs a_absmax
@@ -391,6 +391,20 @@ typedef struct srl_gemm_desc {
  * the w_presplit / wt_presplit arguments of the convolution entry points).  n a multiple of 4, 16-byte aligned pointers. */
 int srl_presplit(void* stream, const float* src, const float* absmax, float* dst, int64_t n);
 int srl_gemm(void* stream, const srl_gemm_desc* d);
+/* The kernel family srl_gemm / the srl_conv2d_* entry points send a call to (ABI 22).  The entry points branch on the same
+ * rule, so the answer is what runs; it depends on the descriptor, on which ranges are given and on the A/B switches
+ * SRL_MFMA / SRL_F16X2 / SRL_SMALL_GEMM / SRL_OBS_BF16, read per call.  Host-only: no stream, no launch, no device. */
+enum srl_family {
+  SRL_FAMILY_SKINNY = 0,   /* one extent <= 16: bandwidth kernels on the vector units (skinny.h) */
+  SRL_FAMILY_F32 = 1,      /* float32 MFMA (gemm_core.h): one matrix-core product per multiply-add */
+  SRL_FAMILY_X3 = 2,       /* three bf16 pieces per float32 operand, six products (first layer: byte frames x three bf16 planes, three) */
+  SRL_FAMILY_X3_SMALL = 3, /* the same pieces on 64 x 64 tiles with 64-deep k-steps: products of <= 65 536 outputs, K <= 512 */
+  SRL_FAMILY_TWO = 4       /* two f16 pieces per operand, three products: the ONLY family that accepts a pre-split B / w / wt
+                            * (first-layer backward: byte frames x two f16 pieces of dz, two products) */
+};
+/* Reads the extents, pitches, orientations, the alignment of A / B / C and which optional pointers are non-NULL; dereferences
+ * none of them.  -1: NULL descriptor. */
+int srl_gemm_family(const srl_gemm_desc* d);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (eps 1e-5, elementwise affine) over the last dimension D of [rows, D].
@@ -457,6 +471,13 @@ typedef struct srl_conv_desc {
 /* 1 if the implicit path handles this geometry.  first_layer: 0 = NHWC activation layer, 1 = observation layer
  * with a planar (NCHW) observation, 2 = observation layer with a channels-last (NHWC) observation. */
 int srl_conv2d_supported(const srl_conv_desc* d, int first_layer);
+/* The family (enum srl_family above) one pass of a layer runs on, or -1 for a geometry the pass rejects.  flags: RANGES = the
+ * caller hands over both operand ranges (first-layer backward: dz_absmax); IS_U8 / CHANNELS_LAST describe a first layer's frames.
+ * Data gradient: the family of the parity classes that have taps (a class no tap reaches is only zeroed).  First layer: of
+ * srl_conv2d_obs_fwd / _bwd with a 16-byte aligned workspace; a batch walked in several runs is judged by its first run. */
+enum { SRL_PASS_FWD = 0, SRL_PASS_DGRAD = 1, SRL_PASS_WGRAD = 2, SRL_PASS_OBS_FWD = 3, SRL_PASS_OBS_BWD = 4 };
+enum { SRL_FAMILY_RANGES = 1, SRL_FAMILY_IS_U8 = 2, SRL_FAMILY_CHANNELS_LAST = 4 };
+int srl_conv2d_family(const srl_conv_desc* d, int pass, int flags);
 /* y[n,OH,OW,Cout] = act(conv(x[n,H,W,Cin], w) + bias) */
 /* x_absmax / w_absmax / y_absmax (and the dz_absmax / dx_absmax of the gradient entry points below): as srl_gemm_desc's
  * a_absmax / b_absmax / out_absmax (NULL: three bf16 planes, no tracking). */
@@ -464,7 +485,7 @@ int srl_conv2d_supported(const srl_conv_desc* d, int first_layer);
  * element e of y is > 0 -- the one bit the backward pass needs of y where it is only the ReLU derivative that is wanted
  * (srl_conv2d_nhwc_dgrad's x_mask, srl_gemm_desc's dact_mask): modules/cnn.py:118. */
 /* w_presplit != 0: `w` is srl_presplit(w, w_absmax): accepted only where the layer takes the two-piece kernel (both ranges,
- * Cout in 33..., KH*KW*Cin >= 64). */
+ * Cout in 33..., KH*KW*Cin >= 64: srl_conv2d_family(d, SRL_PASS_FWD, SRL_FAMILY_RANGES) == SRL_FAMILY_TWO). */
 int srl_conv2d_nhwc_fwd(void* stream, const srl_conv_desc* d, const float* x, const float* w, const float* bias,
                         float* y, const float* x_absmax, const float* w_absmax, float* y_absmax, uint32_t* y_mask,
                         int w_presplit);
@@ -483,7 +504,7 @@ int srl_conv2d_dgrad_repack(void* stream, const srl_conv_desc* d, const float* w
 /* x_mask (dact == 1, x_act NULL, Cin a multiple of 32): the sign bits of x_act as written by the producing layer's y_mask -- the same dx at 1/32
  * of the bytes read for the derivative. */
 /* wt_presplit != 0: `wt` is srl_presplit(wt, w_absmax) of the regrouped weights: two-piece kernel only (both ranges, Cout a
- * multiple of 16, more than 32 packed columns). */
+ * multiple of 16, more than 32 columns per product: srl_conv2d_family(d, SRL_PASS_DGRAD, SRL_FAMILY_RANGES) == SRL_FAMILY_TWO). */
 int srl_conv2d_nhwc_dgrad(void* stream, const srl_conv_desc* d, const float* dz, const float* wt, const float* x_act,
                           int dact, float* dx, const float* dz_absmax, const float* w_absmax, float* dx_absmax,
                           const uint32_t* x_mask, int wt_presplit);

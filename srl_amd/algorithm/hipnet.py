@@ -753,11 +753,12 @@ class HipNet:
         y = self._buf(f"{tag}{L.prefix}.y", x.rows, L.out_features)
         w_range = self._weight_range(L.prefix, L.out_features * L.in_features) if x_range is not None else None
         w, pre = self._p(f"{L.prefix}.weight"), None
-        if hip.gemm_two_piece(x.rows, L.out_features, L.in_features, x.ptr, x.ld, w, L.in_features, x_range, w_range):
+        fam = hip.gemm_family(x.rows, L.out_features, L.in_features, x.ptr, x.ld, w, L.in_features, x_range, w_range)
+        if fam == hip.FAMILY_TWO:
             pre = self._presplit(f"{L.prefix}.w2h", w, L.out_features * L.in_features, w_range)  # also serves the data gradient
         hip.gemm(x.rows, L.out_features, L.in_features, x.ptr, x.ld, 0, pre or w, L.in_features, 0,
                  y.ptr, y.ld, bias=self._p(f"{L.prefix}.bias"), act=L.act, a_absmax=x_range, b_absmax=w_range,
-                 b_presplit=pre is not None)
+                 b_presplit=pre is not None, family=fam)
         return y, None
 
     def _wgrad(self, out_f, in_f, rows, dz: Buf, x_ptr, x_ld, gw_ptr, gb_ptr=None, dz_range=None, x_range=None):
@@ -795,12 +796,14 @@ class HipNet:
         w_range = self._weight_range(L.prefix, L.out_features * L.in_features) if dz_range is not None else None
         x_mask = x.mask if in_act == hip.ACT_RELU else None
         w, pre = self._p(f"{L.prefix}.weight"), None
-        if hip.gemm_two_piece(x.rows, L.in_features, L.out_features, dz.ptr, dz.ld, w, L.in_features, dz_range, w_range):
+        fam = hip.gemm_family(x.rows, L.in_features, L.out_features, dz.ptr, dz.ld, w, L.in_features, dz_range, w_range,
+                              b_kmajor=True)
+        if fam == hip.FAMILY_TWO:
             pre = self._presplit(f"{L.prefix}.w2h", w, L.out_features * L.in_features, w_range)  # the forward pass's copy
         hip.gemm(x.rows, L.in_features, L.out_features, dz.ptr, dz.ld, 0, pre or w, L.in_features,
                  1, dx.ptr, dx.ld, dact_src=x.ptr if in_act and x_mask is None else None, ld_dact=x.ld, dact=in_act,
                  accumulate=dx_accumulate, a_absmax=dz_range, b_absmax=w_range, out_absmax=dx_range, dact_mask=x_mask,
-                 b_presplit=pre is not None)
+                 b_presplit=pre is not None, family=fam)
         return dx
 
     def _ln_fwd(self, L: ns.LayerNormSpec, x: Buf, tag: str):
@@ -1306,11 +1309,12 @@ class HipNet:
         w_range = self._weight_range(L.prefix, L.cout * kdim) if st.cur_range is not None and not L.pad else None
         xr = st.cur_range if w_range is not None else None
         w, pre = self._p(f"{L.prefix}.weight"), None
-        if hip.conv2d_fwd_two_piece(desc, xr, w_range):
+        fam = hip.conv2d_family(desc, hip.PASS_FWD, w_range is not None)
+        if fam == hip.FAMILY_TWO:
             pre = self._presplit(f"{L.prefix}.w2h", w, L.cout * kdim, w_range)
         hip.conv2d_nhwc_fwd(desc, x.ptr, pre or w, self._p(f"{L.prefix}.bias"),
                             y.ptr, x_absmax=xr, w_absmax=w_range, y_absmax=y_range, y_mask=y.mask,
-                            presplit=pre is not None)
+                            presplit=pre is not None, family=fam)
         return y_range
 
     def _conv_explicit_fwd(self, L, first, x: Buf, y: Buf, P: Buf, n, h, w, kdim):
@@ -1549,11 +1553,12 @@ class HipNet:
         x_mask = x.mask if in_act == hip.ACT_RELU else None  # the derivative from sign bits, not floats
         wr = self._weight_range(L.prefix, L.cout * kdim) if two else None
         wtp, pre = wt.data_ptr(), None
-        if hip.conv2d_dgrad_two_piece(desc, g_range if two else None, wr):
+        fam = hip.conv2d_family(desc, hip.PASS_DGRAD, two)
+        if fam == hip.FAMILY_TWO:
             pre = self._presplit(f"{L.prefix}.wt2h", wtp, hip.conv2d_dgrad_weight_elems(desc), wr)
         hip.conv2d_nhwc_dgrad(desc, g.ptr, pre or wtp, x.ptr if in_act and x_mask is None else None, in_act,
                               dx.ptr, dz_absmax=g_range if two else None, w_absmax=wr,
-                              dx_absmax=dx_range, x_mask=x_mask, presplit=pre is not None)
+                              dx_absmax=dx_range, x_mask=x_mask, presplit=pre is not None, family=fam)
         return self._crop(L, dx, n, tag), dx_range
 
     def _conv_explicit_wgrad(self, rec, g, g_range):

@@ -149,6 +149,8 @@ bool dgrad_uniform(const DgradClass* cls, int nc) {
     u = u && cls[i].th == cls[0].th && cls[i].tw == cls[0].tw && cls[i].ra == cls[0].ra && cls[i].rb == cls[0].rb;
   return u;
 }
+// ... and the packed columns are float4-stageable: the repack and the data gradient then work on ONE product of nc * Cin columns
+bool dgrad_packed(const srl_conv_desc* d, const DgradClass* cls, int nc) { return dgrad_uniform(cls, nc) && (nc * d->Cin) % 4 == 0; }
 
 // ---- finalisation of the first-layer backward from the per-position products Q and column sums R --------------------
 // dw[o,k] += sum_pos gamma[p(pos,k)] * Q[pos,o,k] + beta[p(pos,k)] * R[pos,o];   db[o] += sum_pos R[pos,o]
@@ -320,6 +322,76 @@ static long images_per_launch(const srl_conv_desc* d, int in_esize) {
   return lim;
 }
 
+// The batch in runs of images_per_launch: fn(the run's descriptor, its first image) for each, until one fails.  (An empty
+// batch still makes one call: the argument checks of the run function hold for it too.)
+template <class F>
+static int for_each_run(const srl_conv_desc* d, int in_esize, F fn) {
+  const long run = images_per_launch(d, in_esize);
+  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {
+    srl_conv_desc s = *d;
+    s.n = d->n - i0 < run ? d->n - i0 : run;
+    const int rc = fn(s, i0);
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+// ---- which kernel family takes a pass (enum srl_family): the run functions' argument checks and launch branches switch on these,
+// srl_conv2d_family answers with them.  `ranges`: the caller handed over both operands' ranges.  Tile shapes stay with the launches.
+static int conv_fwd_family(const srl_conv_desc* d, bool ranges) {
+  const long Kp = (long)d->KH * d->KW * d->Cin;
+  if (!use_bf16x3() || Kp < 64 || d->Cout <= 32) return SRL_FAMILY_F32;
+  return piece_family(ranges);
+}
+
+static int conv_wgrad_family(const srl_conv_desc* d, bool ranges) {
+  if (!use_bf16x3() || d->Cout <= 32) return SRL_FAMILY_F32;  // (32-row tiles: float32 MFMA only)
+  return piece_family(ranges);
+}
+
+// of the parity classes that have taps (the others are zeroed by a float32 launch with an empty k loop): they share ncols
+static int conv_dgrad_family(const srl_conv_desc* d, bool ranges) {
+  DgradClass cls[64];
+  const int nc = dgrad_classes(d, cls);
+  const long ncols = (dgrad_packed(d, cls, nc) ? nc : 1) * (long)d->Cin;
+  // the step mask skips whole taps: a k-step of the piece kernels must not straddle two
+  if (!use_bf16x3() || d->Cout % K3 != 0 || ncols <= 32) return SRL_FAMILY_F32;
+  return piece_family(ranges);
+}
+
+// first layer, given a 16-byte aligned workspace: the byte kernels of obs_bf16.h (X3), for the backward with a bound of |dz| on the
+// Atari geometry the block kernel of obs_h2.h (TWO), the float32 MFMA forms otherwise
+static int conv_obs_family(const srl_conv_desc* d, bool bwd, int is_u8, int channels_last, bool dz_range, const void* obs) {
+  if (!obs_bf16_ok(d, is_u8, channels_last, obs)) return SRL_FAMILY_F32;
+  if (!bwd) return SRL_FAMILY_X3;
+  const int OH = conv_out(d->H, d->KH, d->stride), OW = conv_out(d->W, d->KW, d->stride);
+  const long P = (long)OH * OW;
+  if (dz_range && d->Cin == 64 && d->KH == 2 && d->KW == 2 && d->stride == 1 && d->Cout == 32 && OH % srlobs::kBlkH == 0 &&
+      OW % srlobs::kBlkW == 0 && d->n * P * 128 < 0xffffffffL)
+    return SRL_FAMILY_TWO;
+  return (P * d->Cout) % 4 == 0 ? SRL_FAMILY_X3 : SRL_FAMILY_F32;
+}
+
+extern "C" int srl_conv2d_family(const srl_conv_desc* d, int pass, int flags) {
+  const bool ranges = (flags & SRL_FAMILY_RANGES) != 0;
+  const int is_u8 = (flags & SRL_FAMILY_IS_U8) != 0, cl = (flags & SRL_FAMILY_CHANNELS_LAST) != 0;
+  const bool first = pass == SRL_PASS_OBS_FWD || pass == SRL_PASS_OBS_BWD;
+  if (!srl_conv2d_supported(d, first ? 1 + cl : 0)) return -1;
+  switch (pass) {
+    case SRL_PASS_FWD: return conv_fwd_family(d, ranges);
+    case SRL_PASS_WGRAD: return conv_wgrad_family(d, ranges);
+    case SRL_PASS_DGRAD: return d->stride <= 8 ? conv_dgrad_family(d, ranges) : -1;
+    case SRL_PASS_OBS_FWD:
+    case SRL_PASS_OBS_BWD: {
+      srl_conv_desc s = *d;  // what the entry point's first run sees
+      const long run = images_per_launch(d, is_u8 ? 1 : 4);
+      if (s.n > run) s.n = run;
+      return conv_obs_family(&s, pass == SRL_PASS_OBS_BWD, is_u8, cl, ranges, nullptr);
+    }
+  }
+  return -1;
+}
+
 // Order of the 16-deep k-steps of a forward convolution (k = (kh, kw, c), c fastest).  Every tile re-reads its input
 // patch region once per tap that reaches a pixel, and with ~100 tiles in flight per XCD the regions of all of them (10 MB
 // for conv2 of the Atari stack) do not stay in the 4 MB L2 between two taps in ascending order.  Taps that read the SAME
@@ -356,20 +428,19 @@ static int conv2d_nhwc_fwd_run(void* stream, const srl_conv_desc* d, const float
   g.mask_out = y_mask;
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  const bool x3 = use_bf16x3() && Kp >= 64;  // bf16 matrix cores, three exact pieces per float32 operand
-  if (x3) fwd_kstep_order(d, &g);
-  SRL_CHECK_ARG(!w_presplit || (x3 && x_absmax && w_absmax && use_f16x2() && d->Cout > 32),
-                "w_presplit: only layers that take the two-piece kernel");
+  const int family = conv_fwd_family(d, x_absmax && w_absmax);
+  if (family != SRL_FAMILY_F32) fwd_kstep_order(d, &g);  // (the piece kernels' k-step permutation)
+  SRL_CHECK_ARG(!w_presplit || family == SRL_FAMILY_TWO, "w_presplit: only layers that take the two-piece kernel");
   g.b_presplit = w_presplit;
-  if (x3 && x_absmax && w_absmax && use_f16x2() && d->Cout > 32) {
+  if (family == SRL_FAMILY_TWO) {
     // both operands' ranges are known: two f16 pieces each, three products (gemm_bf16x3.h, NP == 2)
     rc = d->Cout > 64 ? launch3<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3, 2>(st, g, 1, 1)
                       : launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3, 2>(st, g, 1, 1);
-  } else
-  if (d->Cout > 64) rc = x3 ? launch3<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1)
-                            : launch<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
-  else if (d->Cout > 32) rc = x3 ? launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1)
-                                 : launch<256, 64, 4, 1, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
+  } else if (family == SRL_FAMILY_X3) {  // bf16 matrix cores, three exact pieces per float32 operand
+    rc = d->Cout > 64 ? launch3<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1)
+                      : launch3<192, 64, 2, 2, false, false, SRC_CONV, SRC_PLAIN, K3>(st, g, 1, 1);
+  } else if (d->Cout > 64) rc = launch<128, 128, 2, 2, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
+  else if (d->Cout > 32) rc = launch<256, 64, 4, 1, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
   else rc = launch<256, 32, 4, 1, false, false, SRC_CONV, SRC_PLAIN>(st, g, 1, 1);
   SRL_CHECK_ARG(rc == 0, "grid too large");
   SRL_LAUNCH_CHECK();
@@ -380,17 +451,12 @@ extern "C" int srl_conv2d_nhwc_fwd(void* stream, const srl_conv_desc* d, const f
                                    const float* bias, float* y, const float* x_absmax, const float* w_absmax,
                                    float* y_absmax, uint32_t* y_mask, int w_presplit) {
   SRL_CHECK_ARG(srl_conv2d_supported(d, 0), "unsupported geometry (needs Cin, Cout multiples of 4)");
-  const long run = images_per_launch(d, 4);
   const long in_e = (long)d->H * d->W * d->Cin;
   const long out_e = (long)conv_out(d->H, d->KH, d->stride) * conv_out(d->W, d->KW, d->stride) * d->Cout;
-  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {
-    srl_conv_desc s = *d;
-    s.n = d->n - i0 < run ? d->n - i0 : run;
-    const int rc = conv2d_nhwc_fwd_run(stream, &s, x + i0 * in_e, w, bias, y + i0 * out_e, x_absmax, w_absmax, y_absmax,
-                                       y_mask ? y_mask + i0 * out_e / 32 : nullptr, w_presplit);
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return for_each_run(d, 4, [&](const srl_conv_desc& s, long i0) {
+    return conv2d_nhwc_fwd_run(stream, &s, x + i0 * in_e, w, bias, y + i0 * out_e, x_absmax, w_absmax, y_absmax,
+                               y_mask ? y_mask + i0 * out_e / 32 : nullptr, w_presplit);
+  });
 }
 
 extern "C" int64_t srl_conv2d_wgrad_workspace(const srl_conv_desc* d) {
@@ -427,11 +493,11 @@ static int conv2d_nhwc_wgrad_run(void* stream, const srl_conv_desc* d, const flo
   hipStream_t st = (hipStream_t)stream;
   int rc;
   g.range_a = dz_absmax; g.range_b = x_absmax;
-  if (bm == 64 && use_bf16x3() && x_absmax && dz_absmax && use_f16x2())  // both ranges known: two f16 pieces per operand
+  const int family = conv_wgrad_family(d, x_absmax && dz_absmax);
+  if (family == SRL_FAMILY_TWO)  // both ranges known: two f16 pieces per operand
     rc = launch3<64, 256, 1, 4, true, true, SRC_PLAIN, SRC_CONV, K3, 2>(st, g, 1, nsplit);
-  else
-  if (bm == 64) rc = use_bf16x3() ? launch3<64, 256, 1, 4, true, true, SRC_PLAIN, SRC_CONV, K3>(st, g, 1, nsplit)
-                                  : launch<64, 256, 1, 4, true, true, SRC_PLAIN, SRC_CONV>(st, g, 1, nsplit);
+  else if (family == SRL_FAMILY_X3) rc = launch3<64, 256, 1, 4, true, true, SRC_PLAIN, SRC_CONV, K3>(st, g, 1, nsplit);
+  else if (bm == 64) rc = launch<64, 256, 1, 4, true, true, SRC_PLAIN, SRC_CONV>(st, g, 1, nsplit);
   else rc = launch<32, 256, 1, 4, true, true, SRC_PLAIN, SRC_CONV>(st, g, 1, nsplit);
   SRL_CHECK_ARG(rc == 0, "grid too large");
   SRL_LAUNCH_CHECK();
@@ -445,16 +511,11 @@ static int conv2d_nhwc_wgrad_run(void* stream, const srl_conv_desc* d, const flo
 extern "C" int srl_conv2d_nhwc_wgrad(void* stream, const srl_conv_desc* d, const float* x, const float* dz, float* dw,
                                      float* workspace, float* dbias, const float* x_absmax, const float* dz_absmax) {
   SRL_CHECK_ARG(srl_conv2d_supported(d, 0), "unsupported geometry");
-  const long run = images_per_launch(d, 4);
   const long in_e = (long)d->H * d->W * d->Cin;
   const long out_e = (long)conv_out(d->H, d->KH, d->stride) * conv_out(d->W, d->KW, d->stride) * d->Cout;
-  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {  // every run adds into dw / dbias
-    srl_conv_desc s = *d;
-    s.n = d->n - i0 < run ? d->n - i0 : run;
-    const int rc = conv2d_nhwc_wgrad_run(stream, &s, x + i0 * in_e, dz + i0 * out_e, dw, workspace, dbias, x_absmax, dz_absmax);
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return for_each_run(d, 4, [&](const srl_conv_desc& s, long i0) {  // every run adds into dw / dbias
+    return conv2d_nhwc_wgrad_run(stream, &s, x + i0 * in_e, dz + i0 * out_e, dw, workspace, dbias, x_absmax, dz_absmax);
+  });
 }
 
 extern "C" int64_t srl_conv2d_dgrad_weight_elems(const srl_conv_desc* d) {
@@ -466,7 +527,7 @@ extern "C" int srl_conv2d_dgrad_repack(void* stream, const srl_conv_desc* d, con
   SRL_CHECK_ARG(check_desc(d) == 0 && w && wt && d->stride <= 8, "bad descriptor");
   DgradClass cls[64];
   const int nc = dgrad_classes(d, cls);
-  const bool packed = dgrad_uniform(cls, nc) && (nc * d->Cin) % 4 == 0;
+  const bool packed = dgrad_packed(d, cls, nc);
   for (int i = 0; i < nc; ++i) {
     const DgradClass& c = cls[i];
     const int total = c.th * c.tw * d->Cout * d->Cin;
@@ -496,7 +557,9 @@ static int conv2d_nhwc_dgrad_run(void* stream, const srl_conv_desc* d, const flo
   // reach a pixel do not depend on its class), so they are packed side by side along N: ONE GEMM with
   // N = classes * Cin whose column groups land on the classes' pixels -- A is staged once for all of them and the
   // tile is 128 wide instead of 32.
-  const bool uniform = dgrad_uniform(cls, nc) && (nc * d->Cin) % 4 == 0;
+  const bool uniform = dgrad_packed(d, cls, nc);
+  const int family = conv_dgrad_family(d, dz_absmax && w_absmax);
+  SRL_CHECK_ARG(!wt_presplit || family == SRL_FAMILY_TWO, "wt_presplit: only layers that take the two-piece kernel");
   for (int i = 0; i < (uniform ? 1 : nc); ++i) {
     const DgradClass& c = cls[i];
     if (c.ra == 0 || c.rb == 0) continue;
@@ -548,19 +611,17 @@ static int conv2d_nhwc_dgrad_run(void* stream, const srl_conv_desc* d, const flo
     }
     g.range_a = dz_absmax; g.range_b = w_absmax; g.out_absmax = dx_absmax;
     int rc;
-    const bool x3 = use_bf16x3() && d->Cout % K3 == 0;  // the step mask skips whole taps: a k-step must not straddle two
-    const bool two_piece = g.K > 0 && x3 && dz_absmax && w_absmax && use_f16x2() && ncols > 32;
-    SRL_CHECK_ARG(!wt_presplit || two_piece, "wt_presplit: only layers that take the two-piece kernel");
     g.b_presplit = wt_presplit;
     if (g.K == 0) {  // no tap reaches this class: gradient is zero there (k loop is empty, epilogue writes 0)
       rc = launch<256, 32, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN>(st, g, 1, 1);
-    } else if (x3 && dz_absmax && w_absmax && use_f16x2() && ncols > 32) {  // both ranges known: two f16 pieces per operand
+    } else if (family == SRL_FAMILY_TWO) {  // both ranges known: two f16 pieces per operand
       rc = ncols > 64 ? launch3<128, 128, 2, 2, false, true, SRC_DGRAD, SRC_PLAIN, K3, 2>(st, g, batch, 1)
                       : launch3<256, 64, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN, K3, 2>(st, g, batch, 1);
-    } else if (ncols > 64) rc = x3 ? launch3<128, 128, 2, 2, false, true, SRC_DGRAD, SRC_PLAIN, K3>(st, g, batch, 1)
-                                   : launch<128, 128, 2, 2, false, true, SRC_DGRAD, SRC_PLAIN>(st, g, batch, 1);
-    else if (ncols > 32) rc = x3 ? launch3<256, 64, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN, K3>(st, g, batch, 1)
-                                 : launch<256, 64, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN>(st, g, batch, 1);
+    } else if (family == SRL_FAMILY_X3) {
+      rc = ncols > 64 ? launch3<128, 128, 2, 2, false, true, SRC_DGRAD, SRC_PLAIN, K3>(st, g, batch, 1)
+                      : launch3<256, 64, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN, K3>(st, g, batch, 1);
+    } else if (ncols > 64) rc = launch<128, 128, 2, 2, false, true, SRC_DGRAD, SRC_PLAIN>(st, g, batch, 1);
+    else if (ncols > 32) rc = launch<256, 64, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN>(st, g, batch, 1);
     else rc = launch<256, 32, 4, 1, false, true, SRC_DGRAD, SRC_PLAIN>(st, g, batch, 1);
     SRL_CHECK_ARG(rc == 0, "grid too large");
   }
@@ -572,17 +633,12 @@ extern "C" int srl_conv2d_nhwc_dgrad(void* stream, const srl_conv_desc* d, const
                                      const float* x_act, int dact, float* dx, const float* dz_absmax, const float* w_absmax,
                                      float* dx_absmax, const uint32_t* x_mask, int wt_presplit) {
   SRL_CHECK_ARG(srl_conv2d_supported(d, 0) && d->stride <= 8, "unsupported geometry");
-  const long run = images_per_launch(d, 4);
   const long in_e = (long)d->H * d->W * d->Cin;
   const long out_e = (long)conv_out(d->H, d->KH, d->stride) * conv_out(d->W, d->KW, d->stride) * d->Cout;
-  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {
-    srl_conv_desc s = *d;
-    s.n = d->n - i0 < run ? d->n - i0 : run;
-    const int rc = conv2d_nhwc_dgrad_run(stream, &s, dz + i0 * out_e, wt, x_act ? x_act + i0 * in_e : nullptr, dact, dx + i0 * in_e,
-                                         dz_absmax, w_absmax, dx_absmax, x_mask ? x_mask + i0 * in_e / 32 : nullptr, wt_presplit);
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return for_each_run(d, 4, [&](const srl_conv_desc& s, long i0) {
+    return conv2d_nhwc_dgrad_run(stream, &s, dz + i0 * out_e, wt, x_act ? x_act + i0 * in_e : nullptr, dact, dx + i0 * in_e,
+                                 dz_absmax, w_absmax, dx_absmax, x_mask ? x_mask + i0 * in_e / 32 : nullptr, wt_presplit);
+  });
 }
 
 extern "C" int64_t srl_conv2d_obs_fwd_workspace(const srl_conv_desc* d) {
@@ -647,7 +703,7 @@ static int conv2d_obs_fwd_run(void* stream, const srl_conv_desc* d, const void* 
   g.out_absmax = y_absmax;
   g.mask_out = y_mask;
   int rc;
-  if (workspace && aligned16(workspace) && obs_bf16_ok(d, is_u8, channels_last, obs)) {
+  if (workspace && aligned16(workspace) && conv_obs_family(d, false, is_u8, channels_last, false, obs) == SRL_FAMILY_X3) {
     // bytes x (three exact bf16 planes of the folded weights) on the bf16 matrix cores: obs_bf16.h
     const int P = OH * OW;
     uint16_t* wq = reinterpret_cast<uint16_t*>(workspace);
@@ -758,21 +814,15 @@ extern "C" int srl_conv2d_obs_fwd(void* stream, const srl_conv_desc* d, const vo
                                   float* y_absmax, uint32_t* y_mask, int reuse_folded) {
   SRL_CHECK_ARG(srl_conv2d_supported(d, channels_last ? 2 : 1),
                 "unsupported geometry (planar: KW, W, stride, H*W multiples of 4; channels-last: Cin multiple of 4)");
-  const long run = images_per_launch(d, is_u8 ? 1 : 4);
   const long in_b = (long)d->H * d->W * d->Cin * (is_u8 ? 1 : 4);
   const long out_e = (long)conv_out(d->H, d->KH, d->stride) * conv_out(d->W, d->KW, d->stride) * d->Cout;
-  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {
-    srl_conv_desc s = *d;
-    s.n = d->n - i0 < run ? d->n - i0 : run;
+  return for_each_run(d, is_u8 ? 1 : 4, [&](const srl_conv_desc& s, long i0) {
     // with a slot index the frames (and their statistics) are addressed through it: only the index moves on
     const long adv = row_index ? 0 : i0;
-    const int rc = conv2d_obs_fwd_run(stream, &s, static_cast<const uint8_t*>(obs) + adv * in_b, is_u8, channels_last, mean + adv,
-                                      rstd + adv, gamma, beta, w, bias, y + i0 * out_e, workspace,
-                                      row_index ? row_index + i0 : nullptr, y_absmax, y_mask ? y_mask + i0 * out_e / 32 : nullptr,
-                                      reuse_folded || i0 > 0);
-    if (rc != 0) return rc;
-  }
-  return 0;
+    return conv2d_obs_fwd_run(stream, &s, static_cast<const uint8_t*>(obs) + adv * in_b, is_u8, channels_last, mean + adv,
+                              rstd + adv, gamma, beta, w, bias, y + i0 * out_e, workspace, row_index ? row_index + i0 : nullptr,
+                              y_absmax, y_mask ? y_mask + i0 * out_e / 32 : nullptr, reuse_folded || i0 > 0);
+  });
 }
 
 extern "C" int srl_conv2d_obs_fold_h2(void* stream, const srl_conv_desc* d, const float* gamma, const float* beta, const float* w,
@@ -792,20 +842,15 @@ extern "C" int srl_conv2d_obs_fwd_h2(void* stream, const srl_conv_desc* d, const
   SRL_CHECK_ARG(!records || aligned16(records), "records: 16-byte aligned");
   SRL_CHECK_ARG(ent_order == 0 || (ent_order == 2 && conv_out(d->H, d->KH, d->stride) % 2 == 0 && conv_out(d->W, d->KW, d->stride) % 2 == 0),
                 "ent_order: 0 (raster) or 2 (parity-class major: even output extents)");
-  const long run = images_per_launch(d, 1);
   const long in_b = (long)d->H * d->W * d->Cin;
   const long out_e = (long)conv_out(d->H, d->KH, d->stride) * conv_out(d->W, d->KW, d->stride) * d->Cout;
-  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {
-    srl_conv_desc s = *d;
-    s.n = d->n - i0 < run ? d->n - i0 : run;
+  return for_each_run(d, 1, [&](const srl_conv_desc& s, long i0) {
     const long adv = row_index ? 0 : i0;
-    const int rc = conv2d_obs_fwd_run(stream, &s, static_cast<const uint8_t*>(obs) + adv * in_b, 1, 1, mean + adv, rstd + adv, gamma,
-                                      beta, w, bias, nullptr, workspace, row_index ? row_index + i0 : nullptr, y_absmax,
-                                      y_mask ? y_mask + i0 * out_e / 32 : nullptr, reuse_folded || i0 > 0,
-                                      static_cast<uint8_t*>(y_h2) + i0 * out_e * 4, y_scale, ent_order, static_cast<uint4*>(records));
-    if (rc != 0) return rc;
-  }
-  return 0;
+    return conv2d_obs_fwd_run(stream, &s, static_cast<const uint8_t*>(obs) + adv * in_b, 1, 1, mean + adv, rstd + adv, gamma,
+                              beta, w, bias, nullptr, workspace, row_index ? row_index + i0 : nullptr, y_absmax,
+                              y_mask ? y_mask + i0 * out_e / 32 : nullptr, reuse_folded || i0 > 0,
+                              static_cast<uint8_t*>(y_h2) + i0 * out_e * 4, y_scale, ent_order, static_cast<uint4*>(records));
+  });
 }
 
 // sample ranges per block of positions of obs_bwd_h2_kernel: one workgroup per CU
@@ -857,8 +902,8 @@ static int conv2d_obs_bwd_run(void* stream, const srl_conv_desc* d, const void* 
   if (first && hipMemsetAsync(R, 0, sizeof(float) * 2 * P * d->Cout, st) != hipSuccess) return -EIO;
   const ObsIndex ix{d->Cin, d->H, d->W, d->KH, d->KW, d->stride, OW, channels_last ? 1 : 0};
   // the Atari geometry with a measured bound of |dz|: blocks of 2 x 4 positions per workgroup, frames and dz by LDS-DMA (obs_h2.h)
-  if (dz_absmax && obs_bf16_ok(d, is_u8, channels_last, obs) && d->Cin == 64 && d->KH == 2 && d->KW == 2 &&
-      d->stride == 1 && d->Cout == 32 && OH % srlobs::kBlkH == 0 && OW % srlobs::kBlkW == 0 && d->n * (long)P * 128 < 0xffffffffL) {
+  const int family = conv_obs_family(d, true, is_u8, channels_last, dz_absmax != nullptr, obs);
+  if (family == SRL_FAMILY_TWO) {
     srlobs::BwdH2Args a{};
     const long n_pad = srl_ceil_div(d->n, (long)srlobs::kTile) * srlobs::kTile;
     float* rstd_max = C + (((long)P * d->Cout + 3) & ~3L);
@@ -887,7 +932,7 @@ static int conv2d_obs_bwd_run(void* stream, const srl_conv_desc* d, const void* 
     SRL_LAUNCH_CHECK();
     return 0;
   }
-  if (obs_bf16_ok(d, is_u8, channels_last, obs) && (P * d->Cout) % 4 == 0) {
+  if (family == SRL_FAMILY_X3) {
     srlobs::BwdArgs a{};
     a.g = obs_geom(d, obs, mean, rstd, OW, row_index);
     a.dz = dz; a.R = R; a.C = C; a.P = P;
@@ -951,21 +996,15 @@ extern "C" int srl_conv2d_obs_bwd(void* stream, const srl_conv_desc* d, const vo
                                   float* workspace, const int32_t* row_index, int phase, const float* dz_absmax) {
   SRL_CHECK_ARG(srl_conv2d_supported(d, channels_last ? 2 : 1), "unsupported geometry");
   SRL_CHECK_ARG(phase >= 0 && phase <= 3, "phase: bit 0 opens, bit 1 closes an accumulation over calls");
-  const long run = images_per_launch(d, is_u8 ? 1 : 4);
   const long in_b = (long)d->H * d->W * d->Cin * (is_u8 ? 1 : 4);
   const long out_e = (long)conv_out(d->H, d->KH, d->stride) * conv_out(d->W, d->KW, d->stride) * d->Cout;
-  for (long i0 = 0; i0 < d->n || i0 == 0; i0 += run) {  // every run adds into dw / db / dgamma / dbeta
-    srl_conv_desc s = *d;
-    s.n = d->n - i0 < run ? d->n - i0 : run;
+  return for_each_run(d, is_u8 ? 1 : 4, [&](const srl_conv_desc& s, long i0) {  // every run adds into dw / db / dgamma / dbeta
     const long adv = row_index ? 0 : i0;
     // several runs per call: each closes its own accumulation, unless the caller accumulates over calls -- then the runs of a
-    // call are links of that chain
-    const bool only = d->n <= run || phase == 3;
-    const int rc = conv2d_obs_bwd_run(stream, &s, static_cast<const uint8_t*>(obs) + adv * in_b, is_u8, channels_last, mean + adv,
-                                      rstd + adv, gamma, beta, w, dz + i0 * out_e, dw, db, dgamma, dbeta, workspace,
-                                      row_index ? row_index + i0 : nullptr,
-                                      only ? phase : ((i0 == 0 ? phase & 1 : 0) | (i0 + run >= d->n ? phase & 2 : 0)), dz_absmax);
-    if (rc != 0) return rc;
-  }
-  return 0;
+    // call are links of that chain (the first opens it if the call does, the last closes it if the call does)
+    const int run_phase = phase == 3 ? 3 : (i0 == 0 ? phase & 1 : 0) | (i0 + s.n >= d->n ? phase & 2 : 0);
+    return conv2d_obs_bwd_run(stream, &s, static_cast<const uint8_t*>(obs) + adv * in_b, is_u8, channels_last, mean + adv,
+                              rstd + adv, gamma, beta, w, dz + i0 * out_e, dw, db, dgamma, dbeta, workspace,
+                              row_index ? row_index + i0 : nullptr, run_phase, dz_absmax);
+  });
 }

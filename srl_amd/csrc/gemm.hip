@@ -38,12 +38,22 @@ int launch_cfg(hipStream_t st, const GemmArgs& g, int akm, int bkm, int split) {
   return launch_or<BM, BN, WM, WN, true>(st, g, akm, bkm, split);
 }
 
-inline bool small_gemm() {  // SRL_SMALL_GEMM=0: the tiny products on the general kernels (A/B)
-  const char* e = getenv("SRL_SMALL_GEMM");
-  return !(e && e[0] == '0');
+// float4 staging needs 16-byte aligned rows and a contiguous extent that is a multiple of 4
+inline bool vec_a(const srl_gemm_desc* d) { return aligned16(d->A) && d->lda % 4 == 0 && (d->a_kmajor ? d->M : d->K) % 4 == 0; }
+inline bool vec_b(const srl_gemm_desc* d) { return aligned16(d->B) && d->ldb % 4 == 0 && (d->b_kmajor ? d->N : d->K) % 4 == 0; }
+
+// The kernel family that takes a product: srl_gemm's argument checks and its launch branch both switch on this.
+int gemm_family(const srl_gemm_desc* d) {
+  if (srlskinny::skinny_kind(d)) return SRL_FAMILY_SKINNY;  // one extent <= 16: bandwidth kernels instead of padded MFMA tiles
+  if (!use_bf16x3() || !vec_a(d) || !vec_b(d)) return SRL_FAMILY_F32;
+  if (small_gemm() && d->M * d->N <= 65536 && d->K >= 4 && d->K <= 512) return SRL_FAMILY_X3_SMALL;
+  if (d->M <= 64 || d->N <= 32 || d->K < 64) return SRL_FAMILY_F32;
+  return d->N > 64 ? piece_family(d->a_absmax && (d->b_absmax || d->b_h2_scale)) : SRL_FAMILY_X3;  // (no two-piece 256 x 64 tile)
 }
 
 }  // namespace
+
+extern "C" int srl_gemm_family(const srl_gemm_desc* d) { return d ? gemm_family(d) : -1; }
 
 extern "C" int srl_gemm(void* stream, const srl_gemm_desc* d) {
   SRL_CHECK_ARG(d != nullptr, "null descriptor");
@@ -59,7 +69,14 @@ extern "C" int srl_gemm(void* stream, const srl_gemm_desc* d) {
                 "dact_mask: the ReLU derivative, instead of dact_src; N and ld_dact multiples of 32");
   if (d->M == 0 || d->N == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (srlskinny::try_skinny(st, d)) {  // one extent <= 16: bandwidth kernels instead of padded MFMA tiles
+  const int family = gemm_family(d);
+  SRL_CHECK_ARG(!d->b_h2_scale || (family == SRL_FAMILY_TWO && d->b_kmajor && d->N % 32 == 0 && d->ldb == d->N && !d->b_presplit),
+                "b_h2_scale: a k-major dense B of h2p rows (N a multiple of 32, ldb == N) on the two-piece kernel (a_absmax given)");
+  SRL_CHECK_ARG(!d->b_presplit || family == SRL_FAMILY_TWO,
+                "b_presplit: only products that take the two-piece kernel (both ranges, M > 64, N > 64, K >= 64, aligned operands, "
+                "more than 65 536 outputs or K > 512)");
+  if (family == SRL_FAMILY_SKINNY) {
+    srlskinny::launch_skinny(st, d, srlskinny::skinny_kind(d));
     srl_count_dispatch(SRL_DISP_SKINNY);
     SRL_LAUNCH_CHECK();
     return 0;
@@ -83,10 +100,7 @@ extern "C" int srl_gemm(void* stream, const srl_gemm_desc* d) {
   } else {
     g.o.out = d->C; g.o.ldo = d->ldc; g.slab = 0; g.accumulate = d->accumulate;
   }
-  // float4 staging needs 16-byte aligned rows and a contiguous extent that is a multiple of 4
-  const long a_contig = d->a_kmajor ? d->M : d->K, b_contig = d->b_kmajor ? d->N : d->K;
-  g.vec_a = aligned16(d->A) && d->lda % 4 == 0 && a_contig % 4 == 0;
-  g.vec_b = aligned16(d->B) && d->ldb % 4 == 0 && b_contig % 4 == 0;
+  g.vec_a = vec_a(d); g.vec_b = vec_b(d);
   if (d->a_colsum) {
     SRL_CHECK_ARG(d->a_kmajor && g.vec_a && g.vec_b,
                   "a_colsum needs a k-major A and float4-stageable operands (16-byte aligned, pitches % 4 == 0)");
@@ -98,25 +112,17 @@ extern "C" int srl_gemm(void* stream, const srl_gemm_desc* d) {
                 "the data-gradient one (0, 1)");
   int rc;
   if (nsplit == 1) g.out_absmax = d->out_absmax;
-  const bool small = use_bf16x3() && small_gemm() && g.vec_a && g.vec_b && d->M * d->N <= 65536 && d->K >= 4 && d->K <= 512;
-  const bool two = !small && use_bf16x3() && d->a_absmax && (d->b_absmax || d->b_h2_scale) && use_f16x2() && g.vec_a && g.vec_b &&
-                   d->M > 64 && d->N > 64 && d->K >= 64;
-  SRL_CHECK_ARG(!d->b_h2_scale || (two && d->b_kmajor && d->N % 32 == 0 && d->ldb == d->N && !d->b_presplit),
-                "b_h2_scale: a k-major dense B of h2p rows (N a multiple of 32, ldb == N) on the two-piece kernel (a_absmax given)");
-  SRL_CHECK_ARG(!d->b_presplit || (two && nsplit >= 1),
-                "b_presplit: only products that take the two-piece kernel (both ranges, M > 64, N > 64, K >= 64, aligned operands, "
-                "more than 65 536 outputs or K > 512)");
-  if (small) {
+  if (family == SRL_FAMILY_X3_SMALL) {
     // A product of a few thousand outputs (the layers of the CartPole-sized configurations) is a latency chain: on 256 x 64
     // tiles it is ONE workgroup walking K in 16-deep steps, a memory latency each (9-11 us for 256 x 64 x 64).  64 x 64
     // tiles with 64-deep steps: several workgroups, and K <= 64 arrives with one round of loads.
     rc = launch3_or<64, 64, 2, 2, 3, 64>(st, g, d->a_kmajor, d->b_kmajor, nsplit);
   } else
-  if (two) {
+  if (family == SRL_FAMILY_TWO) {
     // the caller knows both operands' ranges: two f16 pieces per operand, three products (gemm_bf16x3.h, NP == 2)
     rc = launch3_or<128, 128, 2, 2, 2>(st, g, d->a_kmajor, d->b_kmajor, nsplit);
   } else
-  if (use_bf16x3() && g.vec_a && g.vec_b && d->M > 64 && d->N > 32 && d->K >= 64) {
+  if (family == SRL_FAMILY_X3) {
     // bf16 matrix cores, three exact pieces per float32 operand (2.67x fewer matrix-pipe cycles)
     rc = d->N > 64 ? launch3_or<128, 128, 2, 2>(st, g, d->a_kmajor, d->b_kmajor, nsplit)
                    : launch3_or<256, 64, 4, 1>(st, g, d->a_kmajor, d->b_kmajor, nsplit);

@@ -501,4 +501,12 @@ inline bool use_bf16x3() {
   return !(e && e[0] == 'f');
 }
 
+inline bool small_gemm() {  // SRL_SMALL_GEMM=0: the tiny products on the general kernels (A/B)
+  const char* e = getenv("SRL_SMALL_GEMM");
+  return !(e && e[0] == '0');
+}
+
+// The family of a product the piece kernels take (enum srl_family): two f16 pieces when the caller knows both ranges
+inline int piece_family(bool ranges) { return ranges && use_f16x2() ? SRL_FAMILY_TWO : SRL_FAMILY_X3; }
+
 }  // namespace srlgemm

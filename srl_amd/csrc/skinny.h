@@ -6,7 +6,7 @@
 //   skinny_m :  C[M<=16, N] += A[K, M]^T B[K, N]  (+ column sums of A)  its weight (and bias) gradient
 //   skinny_k :  C[M, N]    (+)= (A[M, K<=16] B[K, N]) * act'(Y)        its data gradient
 //
-// try_skinny() returns 1 when it took the call, 0 when the shapes / alignments want the MFMA path.
+// skinny_kind() names the kernel that takes a call, or none when the shapes / alignments want the MFMA path.
 #pragma once
 #include "srl_common.h"
 
@@ -245,12 +245,28 @@ inline int col_threads(long N) {  // threads across the columns: a power of two 
   return ct;
 }
 
-inline int try_skinny(hipStream_t st, const srl_gemm_desc* d) {
+// Which of the three kernels takes the product (pure host rule; 0: none, the MFMA path)
+enum { SKINNY_NONE = 0, SKINNY_N, SKINNY_M, SKINNY_K };
+inline int skinny_kind(const srl_gemm_desc* d) {
   const long M = d->M, N = d->N, K = d->K;
-  if (M == 0 || N == 0 || d->mask_out || d->dact_mask) return 0;  // sign masks: the MFMA epilogue's business
-  // ---- forward of a narrow head
+  if (M == 0 || N == 0 || d->mask_out || d->dact_mask) return SKINNY_NONE;  // sign masks: the MFMA epilogue's business
   if (!d->a_kmajor && !d->b_kmajor && N <= 16 && M >= 64 && K >= 4 && K % 4 == 0 && d->lda % 4 == 0 && d->ldb % 4 == 0 &&
-      al16(d->A) && al16(d->B) && !d->dact_src && d->split_k <= 1 && !d->a_colsum && N * K * 4 <= 48 * 1024) {
+      al16(d->A) && al16(d->B) && !d->dact_src && d->split_k <= 1 && !d->a_colsum && N * K * 4 <= 48 * 1024)
+    return SKINNY_N;
+  if (d->a_kmajor && d->b_kmajor && M <= 16 && K >= 256 && N % 4 == 0 && d->ldb % 4 == 0 && d->ldc % 4 == 0 && al16(d->B) &&
+      al16(d->C) && d->accumulate && !d->bias && !d->act && !d->dact_src)
+    return SKINNY_M;
+  if (!d->a_kmajor && d->b_kmajor && K <= 16 && K >= 1 && M >= 64 && N % 4 == 0 && d->ldb % 4 == 0 && d->ldc % 4 == 0 &&
+      al16(d->B) && al16(d->C) && !d->bias && !d->act && d->split_k <= 1 && !d->a_colsum &&
+      (!d->dact_src || (d->ld_dact % 4 == 0 && al16(d->dact_src))))
+    return SKINNY_K;
+  return SKINNY_NONE;
+}
+
+inline void launch_skinny(hipStream_t st, const srl_gemm_desc* d, int kind) {
+  const long M = d->M, N = d->N, K = d->K;
+  // ---- forward of a narrow head
+  if (kind == SKINNY_N) {
     long blocks = srl_ceil_div(M, 32L);  // every workgroup stages B once: few, fat workgroups
     if (blocks > 512) blocks = 512;
     const size_t lds = (size_t)N * K * 4;
@@ -269,11 +285,10 @@ inline int try_skinny(hipStream_t st, const srl_gemm_desc* d) {
     else
       hipLaunchKernelGGL(skinny_n_kernel<16>, dim3((unsigned)blocks), dim3(256), lds, st, d->A, d->lda, d->B, d->ldb, d->C,
                          d->ldc, d->bias, M, (int)N, (int)K, d->act, d->accumulate);
-    return 1;
+    return;
   }
   // ---- weight (and bias) gradient of a narrow head: C += A^T B over many rows
-  if (d->a_kmajor && d->b_kmajor && M <= 16 && K >= 256 && N % 4 == 0 && d->ldb % 4 == 0 && d->ldc % 4 == 0 && al16(d->B) &&
-      al16(d->C) && d->accumulate && !d->bias && !d->act && !d->dact_src) {
+  if (kind == SKINNY_M) {
     const long xblocks = srl_ceil_div(N, 16L);
     long slabs = srl_ceil_div(1024L, xblocks);
     if (slabs * 64 * 8 > K) slabs = srl_ceil_div(K, 64L * 8);  // at least 8 rows per row-lane
@@ -286,12 +301,10 @@ inline int try_skinny(hipStream_t st, const srl_gemm_desc* d) {
     else
       hipLaunchKernelGGL(skinny_m_kernel<16>, grid, dim3(256), 0, st, d->A, d->lda, d->B, d->ldb, d->C, d->ldc, (int)M, N, K,
                          rpb, d->a_colsum);
-    return 1;
+    return;
   }
   // ---- data gradient through a narrow head: C (+)= A B with a short K
-  if (!d->a_kmajor && d->b_kmajor && K <= 16 && K >= 1 && M >= 64 && N % 4 == 0 && d->ldb % 4 == 0 && d->ldc % 4 == 0 &&
-      al16(d->B) && al16(d->C) && !d->bias && !d->act && d->split_k <= 1 && !d->a_colsum &&
-      (!d->dact_src || (d->ld_dact % 4 == 0 && al16(d->dact_src)))) {
+  if (kind == SKINNY_K) {
     const int ct = col_threads(N);
     const long xblocks = srl_ceil_div(N, 4L * ct);
     const long nrt = 256 / ct;
@@ -305,9 +318,8 @@ inline int try_skinny(hipStream_t st, const srl_gemm_desc* d) {
     else
       hipLaunchKernelGGL(skinny_k_kernel<16>, grid, dim3(256), 0, st, d->A, d->lda, d->B, d->ldb, d->C, d->ldc, M, N, (int)K,
                          d->dact_src, d->ld_dact, d->dact, d->accumulate, ct);
-    return 1;
+    return;
   }
-  return 0;
 }
 
 }  // namespace srlskinny

@@ -1253,8 +1253,8 @@ def test_mlp_chain_fused(rows, dims, acts):
 @needs_f16x2
 def test_presplit_weights_give_the_same_bits():
     """srl_presplit + b_presplit / presplit=True: a B operand split once instead of in every tile -- the same pieces, so the
-    same results bit for bit: dense forward and data-gradient orientations, the forward convolution, the strided and the
-    stride-1 data gradient (with sign masks); and a product that does not take the two-piece kernel refuses it."""
+    same results bit for bit: dense forward and data-gradient orientations, the forward convolution, the strided (packed and
+    class-by-class) and the stride-1 data gradient (with sign masks); and a product that does not take the two-piece kernel refuses it."""
     rng = np.random.default_rng(11)
     M, N, K = 1000, 512, 3136
     a, w = dev(rng.standard_normal((M, K)).astype(np.float32)), dev((rng.standard_normal((N, K)) * 0.02).astype(np.float32))
@@ -1277,7 +1277,8 @@ def test_presplit_weights_give_the_same_bits():
     assert torch.equal(g0, g1)
     with pytest.raises(hip.HipError, match="b_presplit"):  # no ranges: three bf16 pieces, which cannot take pre-split pieces
         hip.gemm(M, N, K, a.data_ptr(), K, 0, w2.data_ptr(), K, 0, y1.data_ptr(), N, b_presplit=True)
-    for (n, H, Cin, k, s_, Cout) in ((600, 20, 32, 4, 2, 64), (600, 9, 64, 3, 1, 64)):
+    # (the third: odd H under stride 2 -- the parity classes' row grids differ, so each is a product of its own on its block of wt)
+    for (n, H, Cin, k, s_, Cout) in ((600, 20, 32, 4, 2, 64), (600, 9, 64, 3, 1, 64), (600, 21, 64, 4, 2, 64)):
         x = dev(np.maximum(rng.standard_normal((n, H, H, Cin)), 0).astype(np.float32))
         cw = dev((rng.standard_normal((Cout, k, k, Cin)) / np.sqrt(k * k * Cin)).astype(np.float32))
         cb = dev(rng.standard_normal(Cout).astype(np.float32))

@@ -47,9 +47,9 @@ def test_float32_restatement_reproduces_reference_golden(tag, golden):
         assert np.array_equal(sd["log_std"].numpy(), pert["log_std"])
 
 
-def test_library_exports_gaussian_aux_loss_at_abi_21():
+def test_library_exports_gaussian_aux_loss_at_abi_22():
     lib = ctypes.CDLL(hip.library_path())
     assert hasattr(lib, "srl_ppg_aux_loss_gaussian_fwd_bwd")
     assert "srl_ppg_aux_loss_gaussian_fwd_bwd" in hip.EXPORTED_SYMBOLS
     lib.srl_abi_version.restype = ctypes.c_int
-    assert lib.srl_abi_version() == 21 and hip.ABI_VERSION == 21
+    assert lib.srl_abi_version() == 22 and hip.ABI_VERSION == 22
