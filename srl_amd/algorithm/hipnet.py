@@ -30,7 +30,8 @@ from typing import Dict, NamedTuple, Optional
 import torch
 
 from srl_amd import hip
-from srl_amd.algorithm import netspec as ns
+from srl_amd.algorithm import netspec as ns, rnnpath
+from srl_amd.algorithm.rnnpath import RnnCtx  # (policies import it from here)
 from srl_amd.runtime.obs_ring import RingObs
 
 
@@ -42,18 +43,6 @@ class Buf(NamedTuple):
     # device pointer of the sign bits of a ReLU output (bit e of the word array = element e of the buffer is > 0), written
     # by the producing convolution: all that a data gradient needs of the activation (srl_hip.h: y_mask / x_mask / dact_mask)
     mask: Optional[int] = None
-
-
-class RnnCtx(NamedTuple):
-    """How the n = T*B time-major rows of a forward pass are laid out for the recurrent layers: chunks of C time
-    steps (T % C == 0), N = (T/C)*B environment columns per step; h0[tag] float32 [layers, N, H] initial states
-    ("a:" actor / shared backbone, "c:" critic backbone); reset uint8 [C, N] chunk-major on_reset flags, or None
-    (rollout: the state is used as given, actor_critic_policy.py:476-481)."""
-    T: int
-    B: int
-    C: int
-    h0: dict
-    reset: Optional[torch.Tensor]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -90,9 +79,6 @@ class ConvSaved(NamedTuple):
 LnHeadsSaved = NamedTuple("LnHeadsSaved", [("mean", torch.Tensor), ("rstd", torch.Tensor), ("heads", list)])
 ObsLnSaved = NamedTuple("ObsLnSaved", [("is_u8", bool), ("mean", torch.Tensor), ("rstd", torch.Tensor), ("n", int)])
 ConvNdSaved = NamedTuple("ConvNdSaved", [("P", Buf), ("n", int), ("sp", tuple)])   # sp: the (padded) input volume
-LstmSaved = NamedTuple("LstmSaved", [("inp", Buf), ("pre", Buf), ("hin", Buf), ("cin", Buf), ("cnew", Buf)])   # one per layer
-GruSaved = NamedTuple("GruSaved", [("inp", Buf), ("gi", Buf), ("gh", Buf), ("hin", Buf)])                      # one per layer
-RnnSaved = NamedTuple("RnnSaved", [("layers", list), ("ctx", RnnCtx)])
 
 
 class FusedChain(NamedTuple):
@@ -288,7 +274,7 @@ class HipNet:
         self._amax_next = -1
         self._gmax_next = -1
         self._infer = False
-        self._cm = False
+        self._cm = False   # the forward pass in flight runs on chunk-major rows (rnnpath.chunk_major)
         self._mlp_cache = {}   # descriptors of the fused blocks over THIS executor's parameter and gradient pointers
         # set by the trainer's chunk loop before every chunk (True: this executor's last chunk of the update; None outside the loop):
         # what may accumulate over the chunks of an update in an executor's own workspace is closed behind the last one
@@ -823,161 +809,6 @@ class HipNet:
                           self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"), dx_absmax=dx_range if dx else None)
         return dx
 
-    # ------------------------------------------------------------------ recurrent layers (GRU + auto reset)
-    def _gru_fwd(self, G: ns.GruSpec, x: Buf, tag: str):
-        """x: time-major [T*B, H].  Returns (y time-major [T*B, H], saved, last states [layers, N, H])."""
-        ctx = self._rnn
-        if ctx is None:
-            raise hip.HipError("recurrent backbone: forward() needs the `rnn` context (chunking, states, on_reset)")
-        T, B, C, H, I0 = ctx.T, ctx.B, ctx.C, G.hidden, G.input_dim   # (layer 0 reads I0 columns, the others H)
-        n, K = T * B, T // C
-        N = K * B
-        assert x.rows == n and x.cols == I0 and x.ld == I0 and T % C == 0
-        if K > 1 and not self._cm:
-            xc = self._buf(f"{tag}{G.prefix}.xc", n, I0)
-            hip.chunk_rows(x.ptr, xc.ptr, T, B, C, I0)
-        else:  # (one chunk, or the whole pass runs on chunk-major rows already)
-            xc = x
-        h0 = ctx.h0[tag]
-        SW = G.state_width
-        assert tuple(h0.shape) == (G.layers, N, SW) and h0.dtype == torch.float32 and h0.is_contiguous()
-        rs = ctx.reset
-        rptr = (lambda c: rs.data_ptr() + c * N) if rs is not None else (lambda c: None)
-        last = self.ws.get(f"{tag}{G.prefix}.last", G.layers * N * SW)[:G.layers * N * SW].view(G.layers, N, SW)
-        inp, saved = xc, []
-        for l in range(G.layers if G.kind == "lstm" else 0):
-            w_ih, w_hh = self._p(f"{G.prefix}.weight_ih_l{l}"), self._p(f"{G.prefix}.weight_hh_l{l}")
-            b_ih, b_hh = self._p(f"{G.prefix}.bias_ih_l{l}"), self._p(f"{G.prefix}.bias_hh_l{l}")
-            pre = self._buf(f"{tag}{G.prefix}.gi{l}", n, 4 * H)
-            hin = self._buf(f"{tag}{G.prefix}.hin{l}", n, H)
-            cin = self._buf(f"{tag}{G.prefix}.cin{l}", n, H)
-            cnew = self._buf(f"{tag}{G.prefix}.cnew{l}", n, H)
-            y = self._buf(f"{tag}{G.prefix}.y{l}", n, H)
-            hip.gemm(n, 4 * H, inp.cols, inp.ptr, inp.ld, 0, w_ih, inp.cols, 0, pre.ptr, 4 * H, bias=b_ih)  # every step at once
-            # the stored state is cat(h, c) per row (autoreset_rnn.py:31-39); both halves are reset together
-            hip.copy2d(h0[l].data_ptr(), SW, y.ptr, H, N, H)
-            hip.gru_mask_state(y.ptr, rptr(0), N, H, hin.ptr)
-            hip.copy2d(h0[l].data_ptr() + 4 * H, SW, y.ptr, H, N, H)
-            hip.gru_mask_state(y.ptr, rptr(0), N, H, cin.ptr)
-            seq = hip.rnn_seq_supported("lstm", H)  # the chunk's time loop inside one launch (csrc/rnn_seq.hip)
-            if seq:
-                hip.lstm_seq_fwd(pre.ptr, w_hh, b_hh, hin.ptr, cin.ptr, rptr(0), N, H, C, y.ptr, cnew.ptr)
-            for c in range(0 if seq else C):
-                o4, o1 = 4 * c * N * 4 * H, 4 * c * N * H
-                hip.gemm(N, 4 * H, H, hin.ptr + o1, H, 0, w_hh, H, 0, pre.ptr + o4, 4 * H, bias=b_hh, accumulate=True)
-                nxt = c + 1 < C
-                o1n = 4 * (c + 1) * N * H
-                hip.lstm_cell_fwd(pre.ptr + o4, cin.ptr + o1, rptr(c + 1) if nxt else None, N, H, y.ptr + o1, cnew.ptr + o1,
-                                  hin.ptr + o1n if nxt else None, cin.ptr + o1n if nxt else None)
-            hip.copy2d(y.ptr + 4 * (C - 1) * N * H, H, last[l].data_ptr(), SW, N, H)
-            hip.copy2d(cnew.ptr + 4 * (C - 1) * N * H, H, last[l].data_ptr() + 4 * H, SW, N, H)
-            saved.append(LstmSaved(inp, pre, hin, cin, cnew))
-            inp = y
-        for l in range(G.layers if G.kind == "gru" else 0):
-            w_ih, w_hh = self._p(f"{G.prefix}.weight_ih_l{l}"), self._p(f"{G.prefix}.weight_hh_l{l}")
-            b_ih, b_hh = self._p(f"{G.prefix}.bias_ih_l{l}"), self._p(f"{G.prefix}.bias_hh_l{l}")
-            gi = self._buf(f"{tag}{G.prefix}.gi{l}", n, 3 * H)
-            gh = self._buf(f"{tag}{G.prefix}.gh{l}", n, 3 * H)
-            hin = self._buf(f"{tag}{G.prefix}.hin{l}", n, H)
-            y = self._buf(f"{tag}{G.prefix}.y{l}", n, H)
-            hip.gemm(n, 3 * H, inp.cols, inp.ptr, inp.ld, 0, w_ih, inp.cols, 0, gi.ptr, 3 * H, bias=b_ih)  # every step at once
-            hip.gru_mask_state(h0[l].data_ptr(), rptr(0), N, H, hin.ptr)
-            seq = hip.rnn_seq_supported("gru", H)
-            if seq:
-                hip.gru_seq_fwd(gi.ptr, gh.ptr, w_hh, b_hh, hin.ptr, rptr(0), N, H, C, y.ptr)
-            for c in range(0 if seq else C):
-                o3, o1 = 4 * c * N * 3 * H, 4 * c * N * H
-                hip.gemm(N, 3 * H, H, hin.ptr + o1, H, 0, w_hh, H, 0, gh.ptr + o3, 3 * H, bias=b_hh)
-                nxt = c + 1 < C
-                hip.gru_cell_fwd(gi.ptr + o3, gh.ptr + o3, hin.ptr + o1, rptr(c + 1) if nxt else None, N, H, y.ptr + o1,
-                                 hin.ptr + 4 * (c + 1) * N * H if nxt else None)
-            hip.copy2d(y.ptr + 4 * (C - 1) * N * H, H, last[l].data_ptr(), H, N, H)
-            saved.append(GruSaved(inp, gi, gh, hin))
-            inp = y
-        if K > 1 and not self._cm:
-            ytm = self._buf(f"{tag}{G.prefix}.ytm", n, H)
-            hip.chunk_rows(inp.ptr, ytm.ptr, T, B, C, H, inverse=True)
-        else:
-            ytm = inp
-        return ytm, RnnSaved(saved, ctx), last
-
-    def _gru_bwd(self, G: ns.GruSpec, saved_all: RnnSaved, dy: Buf, in_act: int, need_dx: bool, tag: str) -> Optional[Buf]:
-        saved, ctx = saved_all.layers, saved_all.ctx
-        T, B, C, H = ctx.T, ctx.B, ctx.C, G.hidden
-        n, K = T * B, T // C
-        N = K * B
-        rs = ctx.reset
-        rptr = (lambda c: rs.data_ptr() + c * N) if rs is not None else (lambda c: None)
-        if K > 1 and not self._cm:
-            dyc = self._buf(f"{tag}{G.prefix}.dyc", n, H)
-            assert dy.ld == H
-            hip.chunk_rows(dy.ptr, dyc.ptr, T, B, C, H)
-        else:
-            dyc = dy
-        dout = dyc
-        for l in range(G.layers - 1 if G.kind == "lstm" else -1, -1, -1):
-            inp, pre, hin, cin, cnew = saved[l]
-            w_ih, w_hh = self._p(f"{G.prefix}.weight_ih_l{l}"), self._p(f"{G.prefix}.weight_hh_l{l}")
-            dh = [self._buf(f"{tag}{G.prefix}.dh{i}", N, H) for i in range(2)]
-            dc = [self._buf(f"{tag}{G.prefix}.dc{i}", N, H) for i in range(2)]
-            ch = cc = None
-            seq = hip.rnn_seq_supported("lstm", H)
-            assert seq or dout.ld == H, "the per-step cells read d y in rows of H"
-            if seq:
-                hip.lstm_seq_bwd(dout.ptr, dout.ld, pre.ptr, w_hh, cin.ptr, cnew.ptr, rptr(0), N, H, C)
-            for c in range(-1 if seq else C - 1, -1, -1):
-                o4, o1 = 4 * c * N * 4 * H, 4 * c * N * H
-                hip.lstm_cell_bwd(dout.ptr + 4 * c * N * dout.ld, ch, cc, rptr(c + 1) if c + 1 < C else None, pre.ptr + o4,
-                                  cin.ptr + o1, cnew.ptr + o1, N, H, dc[c & 1].ptr)
-                hip.gemm(N, H, 4 * H, pre.ptr + o4, 4 * H, 0, w_hh, H, 1, dh[c & 1].ptr, H)  # d h_in(c) = d pre . W_hh
-                ch, cc = dh[c & 1].ptr, dc[c & 1].ptr
-            # bias gradients (column sums of d pre) come out of the weight-gradient kernels
-            self._wgrad(4 * H, H, n, pre, hin.ptr, H, self._g(f"{G.prefix}.weight_hh_l{l}"),
-                        self._g(f"{G.prefix}.bias_hh_l{l}"))
-            self._wgrad(4 * H, inp.cols, n, pre, inp.ptr, inp.ld, self._g(f"{G.prefix}.weight_ih_l{l}"),
-                        self._g(f"{G.prefix}.bias_ih_l{l}"))
-            if l == 0 and not need_dx:
-                return None
-            dx = self._buf(f"{tag}{G.prefix}.dx{l}", n, inp.cols)
-            act = in_act if l == 0 else 0
-            hip.gemm(n, inp.cols, 4 * H, pre.ptr, 4 * H, 0, w_ih, inp.cols, 1, dx.ptr, inp.cols, dact_src=inp.ptr if act else None,
-                     ld_dact=inp.ld, dact=act)
-            dout = dx
-        for l in range(G.layers - 1 if G.kind == "gru" else -1, -1, -1):
-            inp, gi, gh, hin = saved[l]
-            w_ih, w_hh = self._p(f"{G.prefix}.weight_ih_l{l}"), self._p(f"{G.prefix}.weight_hh_l{l}")
-            dh = [self._buf(f"{tag}{G.prefix}.dh{i}", N, H) for i in range(2)]
-            carry = None
-            seq = hip.rnn_seq_supported("gru", H)
-            assert seq or dout.ld == H, "the per-step cells read d y in rows of H"
-            if seq:
-                hip.gru_seq_bwd(dout.ptr, dout.ld, gi.ptr, gh.ptr, w_hh, hin.ptr, rptr(0), N, H, C)
-            for c in range(-1 if seq else C - 1, -1, -1):
-                o3, o1 = 4 * c * N * 3 * H, 4 * c * N * H
-                cur = dh[c & 1]
-                hip.gru_cell_bwd(dout.ptr + 4 * c * N * dout.ld, carry, rptr(c + 1) if c + 1 < C else None, gi.ptr + o3,
-                                 gh.ptr + o3, hin.ptr + o1, N, H, cur.ptr)
-                # d h_in(c) = dh*z + d gh . W_hh: the carry of step c-1 (masked there by on_reset[c])
-                hip.gemm(N, H, 3 * H, gh.ptr + o3, 3 * H, 0, w_hh, H, 1, cur.ptr, H, accumulate=True)
-                carry = cur.ptr
-            # parameter gradients over all steps at once (gi / gh now hold d gi / d gh)
-            self._wgrad(3 * H, H, n, gh, hin.ptr, H, self._g(f"{G.prefix}.weight_hh_l{l}"),
-                        self._g(f"{G.prefix}.bias_hh_l{l}"))
-            self._wgrad(3 * H, inp.cols, n, gi, inp.ptr, inp.ld, self._g(f"{G.prefix}.weight_ih_l{l}"),
-                        self._g(f"{G.prefix}.bias_ih_l{l}"))
-            if l == 0 and not need_dx:
-                return None
-            dx = self._buf(f"{tag}{G.prefix}.dx{l}", n, inp.cols)
-            act = in_act if l == 0 else 0  # layer 0 reads the (activated) output of the dense stack
-            hip.gemm(n, inp.cols, 3 * H, gi.ptr, 3 * H, 0, w_ih, inp.cols, 1, dx.ptr, inp.cols, dact_src=inp.ptr if act else None,
-                     ld_dact=inp.ld, dact=act)
-            dout = dx
-        if K > 1 and not self._cm:
-            dxt = self._buf(f"{tag}{G.prefix}.dxt", n, dout.cols)
-            hip.chunk_rows(dout.ptr, dxt.ptr, T, B, C, dout.cols, inverse=True)
-            return dxt
-        return dout
-
     # ------------------------------------------------------------------ encoders: one forward handler per layer spec
     # A handler `(self, st, L)` runs layer L on `st.cur`, appends its record to `st.tape` (with the record's `out_cols`: only
     # the handler knows it) and moves `st` on.  FWD_HANDLERS picks it by spec class; a new layer kind adds one handler here, one
@@ -1126,9 +957,8 @@ class HipNet:
 
     @_fwd(ns.GruSpec, emits=("gru",))
     def _fwd_gru(self, st, L):
-        y, saved, last = self._gru_fwd(L, st.cur, st.tag)
+        y, saved, self.last_state[st.tag] = rnnpath.forward(self, L, st.cur, st.tag, self._rnn, self._cm)
         st.tape.append(Rec("gru", L, st.cur, saved, st.cur_act, L.hidden))
-        self.last_state[st.tag] = last
         st.advance(y)
 
     @_fwd(ns.ObsLayerNormSpec, emits=("obsln",))
@@ -1430,7 +1260,7 @@ class HipNet:
 
     @_bwd("gru")
     def _bwd_gru(self, rec, g, g_range, need_dx, tag, below, dv):
-        return self._gru_bwd(rec.layer, rec.saved, g, rec.in_act, need_dx, tag), None
+        return rnnpath.backward(self, rec.layer, rec.saved, g, rec.in_act, need_dx, tag), None
 
     @_bwd("obsln")
     def _bwd_obsln(self, rec, g, g_range, need_dx, tag, below, dv):
@@ -1851,29 +1681,12 @@ class HipNet:
         if sp.num_rnn_layers and (rnn is None or rnn.T * rnn.B != n):
             raise hip.HipError("recurrent backbone: `rnn` context missing or inconsistent with the row count")
         atot = sum(sp.act_dims)
-        logits_t = self.ws.get("logits", n * atot)
-        value_t = self.ws.get("value", n * sp.value_dim)
-        # Recurrent nets over vector observations, more than one chunk: the recurrent layers want the rows chunk-major (step c of
-        # every chunk side by side), everything else is row-wise.  Instead of re-ordering the 64-wide features in front of and
-        # behind every recurrent layer, in both directions (8 launches, 0.45 ms of the SMAC-sized step), the OBSERVATIONS are put
-        # into chunk-major order once, the whole pass runs on them, and only the heads' outputs (and their gradients on the way
-        # back) are put back into time-major order: a fifth of the bytes.
-        encs = list(sp.obs_encoders) + ([] if sp.shared_backbone else list(sp.state_encoders))
-        cm = bool(sp.num_rnn_layers and rnn is not None and rnn.T // rnn.C > 1
-                  and sp.std_type != "shared_learnable" and sp.aux_head is None
-                  and all(isinstance(obs.get(e.key), torch.Tensor) and obs[e.key].dim() == 2 and obs[e.key].dtype == torch.float32
-                          and obs[e.key].is_contiguous() for e in encs))
-        self._cm = cm
-        logits_out, value_out = logits_t, value_t
+        logits_t = logits_out = self.ws.get("logits", n * atot)
+        value_t = value_out = self.ws.get("value", n * sp.value_dim)
+        self._cm = cm = rnnpath.chunk_major(sp, rnn, obs)   # the whole pass on chunk-major rows; the heads' outputs put back below
         if cm:
-            obs = dict(obs)
-            for key in {e.key for e in encs}:
-                x = obs[key]
-                xc = self.ws.get(f"cm.obs.{key}", x.numel())[:x.numel()].view(x.shape)
-                hip.chunk_rows(x.data_ptr(), xc.data_ptr(), rnn.T, rnn.B, rnn.C, x.shape[1])
-                obs[key] = xc
-            logits_t = self.ws.get("cm.logits", n * atot)
-            value_t = self.ws.get("cm.value", n * sp.value_dim)
+            obs = rnnpath.obs_chunk_major(self, rnn, obs)
+            logits_t, value_t = self.ws.get("cm.logits", n * atot), self.ws.get("cm.value", n * sp.value_dim)
         # CartPole-sized nets: trunk + head of a separate actor / critic as one launch each (trunk only when the heads share it)
         # (not with PPG's auxiliary value head: it reads the actor trunk's features beside the actor head)
         heads_in = not sp.shared_backbone and sp.std_type != "shared_learnable" and sp.aux_head is None
@@ -1922,11 +1735,9 @@ class HipNet:
                      aux_t.data_ptr(), sp.value_dim, bias=self._p(f"{sp.aux_head.prefix}.bias"))
             self.aux_value = aux_t[:n * sp.value_dim].view(n, sp.value_dim)
         self._tape = PassTape(n, a_feat, a_act, a_tape, c_feat, c_act, c_tape, cm, rnn) if keep_tape else None
-        if cm:  # the heads' outputs back into time-major order
-            hip.chunk_rows(logits_t.data_ptr(), logits_out.data_ptr(), rnn.T, rnn.B, rnn.C, atot, inverse=True)
-            hip.chunk_rows(value_t.data_ptr(), value_out.data_ptr(), rnn.T, rnn.B, rnn.C, sp.value_dim, inverse=True)
-            logits_t, value_t = logits_out, value_out
-        return logits_t[:n * atot].view(n, atot), value_t[:n * sp.value_dim].view(n, sp.value_dim)
+        if cm:
+            rnnpath.heads_time_major(rnn, (logits_t, logits_out, atot), (value_t, value_out, sp.value_dim))
+        return logits_out[:n * atot].view(n, atot), value_out[:n * sp.value_dim].view(n, sp.value_dim)
 
     def backward(self, d_logits: torch.Tensor, d_value: torch.Tensor, d_log_std_rows: Optional[torch.Tensor] = None,
                  d_aux: Optional[torch.Tensor] = None):
@@ -1942,16 +1753,11 @@ class HipNet:
         # workspace buffers the tape points at (logits, value, a_feat, mlp.y); inference beside training uses an executor of its own)
         t = self._tape
         n, a_feat, a_act, a_tape, c_feat, c_act, c_tape = t.n, t.a_feat, t.a_act, t.a_tape, t.c_feat, t.c_act, t.c_tape
-        self._cm, self._rnn = t.cm, t.rnn
         atot = sum(sp.act_dims)
         dl = Buf(d_logits.data_ptr(), atot, n, atot)
         dv = Buf(d_value.data_ptr(), sp.value_dim, n, sp.value_dim)
-        if self._cm:  # the pass ran on chunk-major rows (forward()): so do the gradients
-            rnn = self._rnn
-            dlc, dvc = self._buf("cm.d_logits", n, atot), self._buf("cm.d_value", n, sp.value_dim)
-            hip.chunk_rows(dl.ptr, dlc.ptr, rnn.T, rnn.B, rnn.C, atot)
-            hip.chunk_rows(dv.ptr, dvc.ptr, rnn.T, rnn.B, rnn.C, sp.value_dim)
-            dl, dv = dlc, dvc
+        if t.cm:  # the pass ran on chunk-major rows (forward()): so do the gradients
+            dl, dv = rnnpath.rows(self, t.rnn, "cm.d_logits", dl), rnnpath.rows(self, t.rnn, "cm.d_value", dv)
         a_head_in, c_head_in = a_tape.head_in, c_tape is not None and c_tape.head_in
         da = None if a_head_in else self._linear_bwd(sp.actor_head, a_feat, dl, a_act, True, "a:")
         if sp.std_type == "shared_learnable":

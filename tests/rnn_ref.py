@@ -1,5 +1,5 @@
 """A plain restatement of one chunk of the auto-reset recurrent layer (LSTM / GRU), buffer by buffer as the HIP kernels see it
-(csrc/rnn_seq.hip, csrc/gru.hip, `HipNet._gru_fwd / _gru_bwd`), in torch on the CPU with autograd for the backward.
+(csrc/rnn_seq.hip, csrc/gru.hip, `srl_amd/algorithm/rnnpath.py`), in torch on the CPU with autograd for the backward.
 
 Run in float64 it is the reference the kernels are held to (tests/test_gpu_rnn.py); run in float32 it measures how far an honest
 float32 evaluation of the same arithmetic lands from float64, which sets the tolerance.  tests/test_rnn_reference.py holds it

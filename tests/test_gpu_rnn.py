@@ -1,6 +1,6 @@
 """The recurrent kernels, entry point by entry point, against a float64 restatement of the auto-reset LSTM / GRU (tests/rnn_ref.py).
 
-Two paths carry a chunk of C steps over N rows, and both are driven here the way `HipNet._gru_fwd / _gru_bwd` drives them, on the
+Two paths carry a chunk of C steps over N rows, and both are driven here the way `rnnpath.forward / backward` drives them, on the
 same buffers (`pre` / `gi` = W_ih x + b_ih, `hin[0]` / `cin[0]` masked by srl_gru_mask_state, `reset[c]` for c in [0, C)):
   seq   srl_{lstm,gru}_seq_{fwd,bwd} (csrc/rnn_seq.hip): the whole time loop in one launch, H in {32, 64}, gates on the hardware's
         exp2 / rcp (SRL_RNN_FASTMATH);
@@ -264,6 +264,8 @@ NET_CASES = [  # (kind, H, layers, T, B, SRL_RNN_SEQ): chunk_len 10, ragged B
     ("lstm", 128, 1, 20, 19, "1"),
     ("lstm", 64, 1, 20, 23, "1"),
     ("lstm", 64, 1, 20, 23, "0"),
+    ("lstm", 32, 2, 20, 5, "1"),      # two LSTM layers (layer 1 reads layer 0's y): the time loop
+    ("lstm", 16, 2, 20, 5, "1"),      # ... and per-step
 ]
 
 

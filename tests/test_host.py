@@ -425,3 +425,32 @@ def test_every_layer_kind_has_its_forward_and_backward_handler():
     assert HipNet.FWD_KINDS and set(HipNet.FWD_KINDS) <= set(HipNet.BWD_HANDLERS), set(HipNet.FWD_KINDS) - set(HipNet.BWD_HANDLERS)
     assert set(HipNet.BWD_OWN_RELEASE) <= set(HipNet.BWD_HANDLERS)
     assert all(callable(f) for f in list(HipNet.FWD_HANDLERS.values()) + list(HipNet.BWD_HANDLERS.values()))
+
+
+def test_chunk_major_decision_truth_table():
+    """rnnpath.chunk_major(spec, rnn, obs): a whole pass runs on chunk-major rows for a recurrent net with more than one chunk and
+    2-D contiguous float32 observations under every encoder key -- and for nothing else, one change at a time."""
+    from srl_amd.algorithm.rnnpath import RnnCtx, chunk_major
+    base = dict(obs_dim={"a": 5, "b": 3}, action_dim=2, hidden_dim=8, num_dense_layers=1, num_rnn_layers=1, popart=False,
+                layernorm=True, shared_backbone=False)
+    spec = lambda **kw: ns.build_netspec(**dict(base, **kw))[0]
+    T, B, C = 8, 3, 4
+    rnn = RnnCtx(T, B, C, {}, None)
+    obs = {"a": torch.zeros(T * B, 5), "b": torch.zeros(T * B, 3)}
+    assert chunk_major(spec(), rnn, obs) is True
+    assert chunk_major(spec(shared_backbone=True), rnn, obs) is True
+    assert chunk_major(spec(rnn_type="lstm", num_rnn_layers=2), rnn, obs) is True
+    false_for = {
+        "one chunk": (spec(), RnnCtx(C, 2 * B, C, {}, None), obs),
+        "no recurrent layers": (spec(num_rnn_layers=0), rnn, obs),
+        "no context": (spec(), None, obs),
+        "shared_learnable": (spec(continuous_action=True, std_type="shared_learnable"), rnn, obs),
+        "auxiliary value head": (spec(auxiliary_head=True), rnn, obs),
+        "uint8 observation": (spec(), rnn, dict(obs, b=torch.zeros(T * B, 3, dtype=torch.uint8))),
+        "3-D observation": (spec(), rnn, dict(obs, b=torch.zeros(T * B, 1, 3))),
+        "non-contiguous view": (spec(), rnn, dict(obs, a=torch.zeros(T * B, 10)[:, ::2])),
+        "missing key": (spec(), rnn, {"a": obs["a"]}),
+    }
+    assert chunk_major(spec(continuous_action=True, std_type="fixed"), rnn, obs) is True   # (only the shared log-sigma head refuses)
+    for what, args in false_for.items():
+        assert chunk_major(*args) is False, what
