@@ -274,6 +274,69 @@ int srl_categorical_sample(void* stream, const float* logits, int ld_logits, con
                            uint64_t seed, uint64_t offset, int64_t* action_out, float* logp, int64_t row0);
 
 /* ------------------------------------------------------------------------------------------------
+ * Deep Q-learning with a dueling head (added at ABI 22: additive, the version is unchanged).
+ *
+ * Both networks end in an advantage head adv [rows, A] (row pitch ld_*) and a value head v [rows, 1]; every entry point forms
+ *   Q[a] = (v + adv[a]) - mean_a adv                                          (atari_dqn_policy.py:99-101, float32)
+ * itself, and "greedy" is the FIRST maximal index of the online Q, as torch.argmax documents.
+ *
+ * The TD step: DeepQLearning.step between the two forward passes and the backward pass
+ * (legacy/algorithm/q_learning/deep_q_learning.py:117-181), AtariDQNPolicy's gathers (atari_dqn_policy.py:218-231), n_step_return
+ * (legacy/algorithm/modules/n_step_return.py:11-50) and both scalar transforms (modules/utils.py:324-335).  Rows are time-major,
+ * row = t * B + b, T rows per column AFTER the burn-in steps were dropped; n = bootstrap_steps, S = T - n loss rows.
+ *   tq[t]  = Q_target[t, greedy[t]]  (double_q)  or  max_a Q_target[t, a]                       t < T
+ *   tq'[t] = inverse_scalar_transform(tq[t], eps)  if apply_scalar_transform                    float64 -> float32 (utils.py:335)
+ *   ret[t] = n-step return of reward[t..], nex_value = tq'[t+1..], nex_done = done[t+1..], nex_truncated = truncated[t+1..],
+ *            bootstrapping in advance where the next step is truncated                          float64 -> float32 (:50)
+ *   y[t]   = scalar_transform(ret[t], eps)  if apply_scalar_transform                           float64 -> float32 (utils.py:328)
+ *   q[t]   = Q_online[t, action[t]],  mask[t] = 1 - done[t]                                     t < S
+ *   loss   = sum weight[b] l(q, y) mask / sum mask         l: value_loss 0 mse, 1 huber(delta), 2 smoothl1(beta = delta)
+ * Outputs: d_adv [T*B, A] (row pitch ld_dadv; columns >= A are left alone) and d_v [T*B] = d loss / d head outputs, with
+ * g = d loss / d q:  d_adv[a] = g (1[a == action] - 1/A), d_v = g, zero for rows t >= S;
+ * terms float64[SRL_DQ_COUNT] (zeroed, then written): sums over the masked loss rows of weight * l, q, y, q and y denormalised
+ * for logging (inverse_scalar_transform with its DEFAULT eps when apply_scalar_transform, deep_q_learning.py:190-192), |q - y|;
+ * the largest masked |q - y|; and sum mask;
+ * priorities float32[B] = eta max_t(|q - y| mask) + (1 - eta) sum_t(|q - y| mask) / sum_t mask  (:175-179; a column whose loss
+ * rows are all done gives 0/0 = NaN as there).
+ * action int32 [T*B] with entries in [0, A); reward float32, done / truncated uint8 [T*B]; weight float32 [B] or NULL
+ * (sample.metadata["sampling_weight"], :154-157).  Two launches: one thread per row (dueling combine, gathers, the mask count), then
+ * one thread per column walking time (return, loss, gradient, statistics); d_v and column 0 of d_adv carry the first one's results
+ * to the second. */
+typedef struct srl_dqn_hparams {
+  double gamma;                      /* deep_q_learning.py:40  default 0.99 */
+  double scalar_transform_eps;       /* :57  default 1e-3 */
+  double priority_interpolation_eta; /* :60  default 0.9 */
+  float huber_delta;                 /* value_loss_config delta / beta */
+  int32_t n;                         /* bootstrap_steps, :41 */
+  int32_t apply_scalar_transform;    /* :54  default 1 */
+  int32_t double_q;                  /* atari_dqn_policy.py:124  default 1 */
+  int32_t value_loss;                /* 0 mse, 1 huber, 2 smoothl1 */
+  int32_t pad_;
+} srl_dqn_hparams;
+
+enum { SRL_DQ_VLOSS = 0, SRL_DQ_Q = 1, SRL_DQ_Y = 2, SRL_DQ_QINV = 3, SRL_DQ_YINV = 4, SRL_DQ_TD = 5, SRL_DQ_TDMAX = 6,
+       SRL_DQ_MASK = 7, SRL_DQ_COUNT = 8 };
+
+int srl_dqn_td_fwd_bwd(void* stream, const float* adv, int64_t ld_adv, const float* v, const float* target_adv,
+                       int64_t ld_target_adv, const float* target_v, const int32_t* action, const float* reward,
+                       const uint8_t* done, const uint8_t* truncated, const float* weight, int T, int B, int A,
+                       const srl_dqn_hparams* hp, float* d_adv, int64_t ld_dadv, float* d_v, double* terms, float* priorities);
+
+/* The rollout head (atari_dqn_policy.py:255-276) over n rows.  One Philox4x32-10 draw per row, counter and key words laid out
+ * as the categorical sampler above documents, with head word 0: u = (x0 >> 8) 2^-24; the row exploits (action = greedy) iff
+ * is_eval[row] (uint8, nullable) or u > epsilon[row], and otherwise takes action = floor((x1 >> 8) 2^-24 A).  The reference draws
+ * from torch's generator, so the stream differs from it.  action int64 [n]; value = Q_online[action]; target_value =
+ * Q_target[greedy] (double_q) or max_a Q_target. */
+int srl_epsilon_greedy_sample(void* stream, const float* adv, int64_t ld_adv, const float* v, const float* target_adv,
+                              int64_t ld_target_adv, const float* target_v, const float* epsilon, const uint8_t* is_eval, long n,
+                              int A, int double_q, uint64_t seed, uint64_t offset, int64_t row0, int64_t* action, float* value,
+                              float* target_value);
+
+/* target = target (1 - tau) + param tau over flat float32 buffers, one launch (modules/utils.py:299-309, each product and the
+ * sum rounded as torch rounds them); tau == 1 copies param exactly (hard_update, :313-321). */
+int srl_polyak_update(void* stream, float* target, const float* param, int64_t n, double tau);
+
+/* ------------------------------------------------------------------------------------------------
  * Phasic Policy Gradient, auxiliary phase (ABI 15).
  *
  * srl_categorical_log_softmax: out[i, head h] = masked logits - logsumexp over the head -- the `.logits` of the

@@ -1,0 +1,225 @@
+"""``atari-dqn``: the dueling double-DQN agent on the HIP kernels.
+
+Mirror of ``AtariDQNPolicy`` (reference ``legacy/algorithm/q_learning/game_policies/atari_dqn_policy.py:117-302``): the same
+constructor keywords and defaults, the same ``state_dict`` names (``net.conv1.weight`` ... ``net.fc_v.2.bias``, then the same under
+``target_net.``), ``analyze(target="dqn", burn_in_steps=...)`` and ``rollout``, ``soft_target_update`` / ``hard_target_update``.
+
+The online and the target network are two executors over two parameter sets of one ``NetSpec``
+(``netspec.build_atari_dqn_netspec``); the convolution trunk runs once per pass per network, both towers' first Linear being one
+product.  ``analyze`` does not gather: it returns both networks' head outputs for every row, and the trainer's TD kernel
+(``csrc/dqn.hip``) forms Q, the greedy action and the gathers itself.  ``rollout`` samples with ``srl_epsilon_greedy_sample``.
+
+DIFFERENCES: exploration draws come from a counter-based Philox stream keyed by ``(seed, call counter)`` instead of torch's
+generator.  ``num_rnn_layers > 0`` (R2D2) and ``dueling=False`` raise ``NotImplementedError`` at construction.
+"""
+import dataclasses
+from collections import OrderedDict
+from typing import Optional
+
+import numpy as np
+import torch
+
+from srl_amd import hip
+from srl_amd.algorithm import netspec as ns
+from srl_amd.algorithm.actor_critic import to_device_leaf
+from srl_amd.algorithm.hipnet import HipNet
+from srl_amd.api import policy as policy_api
+from srl_amd.api.env_utils import DiscreteAction
+from srl_amd.namedarray import NamedArray
+
+
+class DQNPolicyState(policy_api.PolicyState, NamedArray):
+
+    def __init__(self, hx: np.ndarray, epsilon: np.ndarray):
+        super().__init__(hx=hx, epsilon=epsilon)
+
+
+class DQNRolloutAnalyzedResult(policy_api.AnalyzedResult, NamedArray):
+
+    def __init__(self, value: np.ndarray, target_value: np.ndarray, ret: Optional[np.ndarray] = None):
+        super().__init__(value=value, target_value=target_value, ret=ret)
+
+
+@dataclasses.dataclass
+class DQNHeadOutputs:
+    """``analyze(target="dqn")``: both networks' head outputs for the ``T x B`` rows behind the burn-in steps, time-major
+    (row = t * B + b) -- what ``hip.dqn_td_fwd_bwd`` reads.  The online outputs are on the tape: ``backward_dqn`` follows."""
+    adv: torch.Tensor  # [T*B, A] online advantages
+    value: torch.Tensor  # [T*B, 1] online state values
+    target_adv: torch.Tensor  # [T*B, A]
+    target_value: torch.Tensor  # [T*B, 1]
+    action: torch.Tensor  # int32 [T*B]
+    T: int
+    B: int
+
+
+class AtariDQNPolicy(policy_api.Policy):
+
+    def __init__(self,
+                 act_dim: int,
+                 dueling: bool,
+                 chunk_len: int = 40,
+                 use_double_q: bool = True,
+                 seed: int = 42,
+                 num_rnn_layers: int = 0,
+                 hidden_dim: int = 512,
+                 rnn_type: str = 'gru',
+                 rnn_include_last_action: bool = False,
+                 rnn_include_last_reward: bool = False,
+                 use_env_epsilon: bool = True,
+                 epsilon_scheduler=None):
+        super().__init__()
+        if num_rnn_layers > 0:
+            raise NotImplementedError("atari-dqn: num_rnn_layers > 0 (the recurrent R2D2 agent) is not implemented on the HIP path")
+        if not dueling:
+            raise NotImplementedError("atari-dqn: dueling=False is not implemented on the HIP path (the kernels form "
+                                      "Q = v + adv - mean adv themselves)")
+        if not use_env_epsilon and epsilon_scheduler is None:
+            raise ValueError("atari-dqn: use_env_epsilon=False needs an epsilon_scheduler (an object with `get(step)`)")
+        np.random.seed(seed)  # atari_dqn_policy.py:134
+        self.spec, init = ns.build_atari_dqn_netspec(int(act_dim), hidden_dim, seed=seed)
+        self._net = HipNet(self.spec, self.device)
+        self._net.load_reference_state(init)
+        # the target network: its own parameter state; it takes no gradient and keeps no tape
+        self._target = HipNet(self.spec, self.device)
+        self._target.grad = self._target.grad[:0]
+        self._target.load_reference_state(init)
+        self.use_double_q = bool(use_double_q)
+        self._act_dim = int(act_dim)
+        self._chunk_len = int(chunk_len)
+        self._use_env_epsilon = bool(use_env_epsilon)
+        self._exploration = epsilon_scheduler
+        self._default_policy_state = DQNPolicyState(hx=None, epsilon=np.ones(1, dtype=np.float32))
+        self._version = -1
+        self._seed = int(seed)
+        self._rollout_calls = 0
+        self._analysis = None
+
+    # ------------------------------------------------------------------ bookkeeping (api/policy.py:205-288)
+    @property
+    def default_policy_state(self):
+        return self._default_policy_state
+
+    @property
+    def version(self) -> int:
+        return self._version
+
+    @property
+    def net(self) -> HipNet:
+        return self._net
+
+    @property
+    def target_net(self) -> HipNet:
+        return self._target
+
+    def inc_version(self):
+        self._version += 1
+
+    def parameters(self):
+        return [self._net.flat]
+
+    def train_mode(self):
+        pass
+
+    def eval_mode(self):
+        pass
+
+    def distributed(self):
+        if torch.distributed.is_initialized():
+            raise NotImplementedError("atari-dqn: data-parallel training is not implemented")
+
+    def get_checkpoint(self):
+        sd = OrderedDict((f"net.{k}", v) for k, v in self._net.reference_state().items())
+        sd.update((f"target_net.{k}", v) for k, v in self._target.reference_state().items())
+        return {"steps": self._version, "state_dict": sd}
+
+    def load_checkpoint(self, checkpoint):
+        sd = checkpoint["state_dict"]
+        parts = {"net.": {}, "target_net.": {}}
+        for k, v in sd.items():
+            pre = next((p for p in parts if k.startswith(p)), None)
+            if pre is None:
+                raise KeyError(f"state_dict mismatch: unexpected {k}")
+            parts[pre][k[len(pre):]] = v
+        self._net.load_reference_state(parts["net."])
+        self._target.load_reference_state(parts["target_net."])
+        self._version = checkpoint.get("steps", 0)
+
+    # ------------------------------------------------------------------ target network (atari_dqn_policy.py:295-299)
+    def soft_target_update(self, tau):
+        hip.require_gpu()
+        hip.polyak_update(self._target.flat, self._net.flat, tau)
+        self._target.params_changed()
+
+    def hard_target_update(self):
+        self.soft_target_update(1.0)
+
+    # ------------------------------------------------------------------ training-side analysis
+    def analyze(self, sample, target="dqn", **kwargs):
+        if target == "dqn":
+            return self._dqn_analyze(sample, **kwargs)
+        raise NotImplementedError(f"Unkown analyze target {target}.")
+
+    def _dqn_analyze(self, sample, burn_in_steps=0) -> DQNHeadOutputs:
+        """Rows [burn_in_steps, Tb) of ``sample`` (leaves ``[Tb, B, ...]``) through both networks (:168-236).  Without a recurrent
+        layer the reference's chunking only permutes independent rows, so they are evaluated in place; its shape requirement
+        (``modules/utils.py:176``) is kept."""
+        hip.require_gpu()
+        burn = int(burn_in_steps)
+        Tb, B = sample.on_reset.shape[0], sample.on_reset.shape[1]
+        T = Tb - burn
+        chunks = max(T, 0) // self._chunk_len  # (:169-173: 44 steps with chunk_len=40 are one chunk of 44)
+        if chunks == 0 or T % chunks:
+            raise ValueError(f"atari-dqn: {Tb} steps less {burn} burn-in steps do not split into {chunks} equal chunks "
+                             f"(chunk_len={self._chunk_len})")
+        n = T * B
+        frames = to_device_leaf(sample.obs.obs, self.device, "obs")[burn:]
+        obs = {"obs": frames.reshape(n, *frames.shape[2:])}
+        action = to_device_leaf(sample.action.x, self.device, "index")[burn:].reshape(n)
+        tadv, tv = self._target.forward(obs, n, keep_tape=False)
+        adv, v = self._net.forward(obs, n, keep_tape=True)
+        self._analysis = n
+        return DQNHeadOutputs(adv, v, tadv, tv, action, T, B)
+
+    def backward_dqn(self, d_adv: torch.Tensor, d_v: torch.Tensor):
+        """Back-propagate d loss / d (advantages, state values) of the last ``analyze`` into ``net.grad``."""
+        n = self._analysis
+        self._net.backward(d_adv.reshape(n, -1), d_v.reshape(n, 1))
+        self._analysis = None
+
+    # ------------------------------------------------------------------ inference (:238-289)
+    def rollout(self, requests: policy_api.RolloutRequest, **kwargs) -> policy_api.RolloutResult:
+        hip.require_gpu()
+        frames = requests.obs.obs
+        if frames.dtype not in (np.uint8, torch.uint8):
+            raise AssertionError(frames.dtype)  # :240
+        n = int(frames.shape[0])
+        if self._use_env_epsilon:  # the environment provides epsilon as an observation
+            eps_host = np.asarray(requests.obs.epsilon, dtype=np.float32).reshape(n, 1)
+        else:
+            eps_host = np.full((n, 1), self._exploration.get(max(0, self.version)), dtype=np.float32)
+        is_eval = np.asarray(requests.is_evaluation).reshape(-1)
+        is_eval = to_device_leaf(np.broadcast_to(is_eval, (n,)) if is_eval.size == 1 else is_eval, self.device, "flag")
+        obs = {"obs": to_device_leaf(frames, self.device, "obs")}
+        eps = to_device_leaf(eps_host, self.device, "real").reshape(n)
+        self._net.begin_serving()
+        self._target.begin_serving()
+        try:
+            adv, v = self._net.forward(obs, n, keep_tape=False)
+            tadv, tv = self._target.forward(obs, n, keep_tape=False)
+            action = torch.empty((n, 1), dtype=torch.int64, device=self.device)
+            value = torch.empty((n, 1), dtype=torch.float32, device=self.device)
+            target_value = torch.empty((n, 1), dtype=torch.float32, device=self.device)
+            hip.epsilon_greedy_sample(adv, v, tadv, tv, eps, is_eval, self.use_double_q, self._seed, self._rollout_calls, action,
+                                      value, target_value)
+            self._rollout_calls += 1
+            out = [t.cpu().numpy() for t in (action, value, target_value)]
+        finally:
+            self._net.end_serving()
+            self._target.end_serving()
+        return policy_api.RolloutResult(action=DiscreteAction(out[0]),
+                                        policy_state=DQNPolicyState(hx=None, epsilon=eps_host),
+                                        analyzed_result=DQNRolloutAnalyzedResult(value=out[1], target_value=out[2]))
+
+
+policy_api.register("atari-dqn", AtariDQNPolicy)

@@ -1704,6 +1704,15 @@ class HipNet:
                                                     head=sp.actor_head if heads_in else None, head_out=logits_t, lnheads=lnh)
         if sp.shared_backbone:
             c_feat, c_act, c_tape = a_feat, a_act, None
+            if sp.dueling:   # the trunk closes in both towers' first Linear as one product: each head reads its half of the columns,
+                # as dense rows of its own (two small copies: the heads' products and data gradients then run as every other head's)
+                H, both = sp.hidden_dim, a_feat
+                a_feat, c_feat = self._buf("a:dueling.adv_in", n, H), self._buf("a:dueling.v_in", n, H)
+                hip.copy2d(both.ptr, both.ld, a_feat.ptr, H, n, H)
+                hip.copy2d(both.ptr + 4 * H, both.ld, c_feat.ptr, H, n, H)
+                # the encoder ends in that Linear's ReLU (the other encoders end in a LayerNorm or a plain Linear, and the walk over
+                # an empty backbone reports no activation): the heads' data gradients apply its derivative
+                a_act = c_act = sp.obs_encoders[0].layers[-1].act
         else:
             fc = self._fused_fwd("c:", sp.state_encoders, sp.critic_backbone, sp.critic_head if heads_in else None, obs, n,
                                  out=value_t if heads_in else None)
@@ -1759,6 +1768,18 @@ class HipNet:
         if t.cm:  # the pass ran on chunk-major rows (forward()): so do the gradients
             dl, dv = rnnpath.rows(self, t.rnn, "cm.d_logits", dl), rnnpath.rows(self, t.rnn, "cm.d_value", dv)
         a_head_in, c_head_in = a_tape.head_in, c_tape is not None and c_tape.head_in
+        if sp.dueling:   # each head's data gradient goes to its half of the trunk output's columns
+            H = sp.hidden_dim
+            da = self._buf("a:dueling.dx", n, 2 * H)
+            d_a = self._linear_bwd(sp.actor_head, a_feat, dl, a_act, True, "a:")
+            d_c = self._linear_bwd(sp.critic_head, c_feat, dv, c_act, True, "a:")
+            hip.copy2d(d_a.ptr, d_a.ld, da.ptr, 2 * H, n, H)
+            hip.copy2d(d_c.ptr, d_c.ld, da.ptr + 4 * H, 2 * H, n, H)
+            self._release([sp.actor_head.prefix, sp.critic_head.prefix])
+            self._trunk_bwd("a:", a_tape, da)
+            self._join_side()
+            self._tape = None
+            return
         da = None if a_head_in else self._linear_bwd(sp.actor_head, a_feat, dl, a_act, True, "a:")
         if sp.std_type == "shared_learnable":
             dls = Buf(d_log_std_rows.data_ptr(), atot, n, atot)

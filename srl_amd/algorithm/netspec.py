@@ -287,6 +287,9 @@ class NetSpec:
     rnn_state_width: int = 0  # per-layer width of the stored policy state (H, or 2H for LSTM: cat(h, c))
     popart_keys: Tuple[str, str, str] = ()  # state_dict keys of the float64 running statistics (set in __post_init__)
     aux_head: Optional[LinearSpec] = None  # PPG: auxiliary value head on the actor's features (`auxiliary_head=True`)
+    # the dueling Q network: the shared trunk's output is 2 * hidden_dim wide (both towers' first Linear as one product); the
+    # actor head (advantages) reads columns [0, hidden_dim), the critic head (state value) [hidden_dim, 2 * hidden_dim)
+    dueling: bool = False
 
     def __post_init__(self):
         if not self.popart_keys:
@@ -892,4 +895,43 @@ def build_dmlab_netspec(obs_shapes: Dict, action_dim: int, hidden_dim: int = 512
     # ``hidden_dim`` of a NetSpec is the width the heads read
     spec = NetSpec(encs, backbone, None, None, LinearSpec("actor_head", feat, action_dim, 0), LinearSpec("critic_head", feat, 1, 0),
                    [action_dim], feat, 1, True, b.params, off, bool(popart), num_rnn_layers, None, width)
+    return spec, (b.values if b.init else None)
+
+
+def build_atari_dqn_netspec(act_dim: int, hidden_dim: int = 512, seed: Optional[int] = None):
+    """``_AtariDQN`` with ``dueling=True`` and no recurrent layers (``q_learning/game_policies/atari_dqn_policy.py:29-101``): 4 x 84 x 84
+    frames ``/ 255``, ``Conv2d(4, 32, 8, 4) -> Conv2d(32, 64, 4, 2) -> Conv2d(64, 64, 3, 1)`` with ReLU behind each, Flatten, and two
+    towers ``fc`` = Linear(3136, H)-ReLU-Linear(H, A) (advantages) and ``fc_v`` = Linear(3136, H)-ReLU-Linear(H, 1) (state value).
+
+    The parameter table keeps the reference's names and ``state_dict`` order (``conv1.weight`` ... ``fc_v.2.bias``; the policy adds
+    ``net.`` / ``target_net.``) and the initial values replay its constructor (torch's default resets, in module order).  In the
+    flat buffer ``fc_v.0.weight`` follows ``fc.0.weight`` and ``fc_v.0.bias`` follows ``fc.0.bias``: the two first Linears are ONE
+    ``[2H, 3136]`` matrix, the trunk closes in one product, and the heads read the halves of its output (``NetSpec.dueling``)."""
+    A, H = int(act_dim), int(hidden_dim)
+    if H % 4:
+        raise NotImplementedError(f"atari-dqn: hidden_dim must be a multiple of 4 (the towers' first layers share one matrix), got {H}")
+    c, h, w = 4, 84, 84
+    b = _Builder(seed)
+    layers = [ObsScaleSpec("scale", (c, h, w), 1.0 / 255.0)]
+    for name, cout, k, stride in (("conv1", 32, 8, 4), ("conv2", 64, 4, 2), ("conv3", 64, 3, 1)):
+        oh, ow = _conv_out(h, k, stride), _conv_out(w, k, stride)
+        b.conv(name, c, cout, k, "conv_nhwc")
+        layers.append(ConvSpec(name, c, cout, k, stride, (h, w), (oh, ow), ACTS["relu"], first=False))
+        c, h, w = cout, oh, ow
+    flat = c * h * w
+    b.linear("fc.0", flat, H, "fc_from_chw", (c, h, w))
+    b.linear("fc.2", H, A)
+    b.linear("fc_v.0", flat, H, "fc_from_chw", (c, h, w))
+    b.linear("fc_v.2", H, 1)
+    layers.append(LinearSpec("fc.0", flat, 2 * H, ACTS["relu"]))   # ... and fc_v.0 right behind it
+    off = 0
+    placed = [n for n in b.params if not n.startswith("fc")] + ["fc.0.weight", "fc_v.0.weight", "fc.0.bias", "fc_v.0.bias",
+                                                                "fc.2.weight", "fc.2.bias", "fc_v.2.weight", "fc_v.2.bias"]
+    for name in placed:
+        b.params[name].offset = off
+        off += (b.params[name].numel + 3) // 4 * 4
+    assert b.params["fc_v.0.weight"].offset == b.params["fc.0.weight"].offset + H * flat
+    assert b.params["fc_v.0.bias"].offset == b.params["fc.0.bias"].offset + H
+    spec = NetSpec([EncoderSpec("obs", (4, 84, 84), layers, 2 * H)], [], None, None, LinearSpec("fc.2", H, A, 0),
+                   LinearSpec("fc_v.2", H, 1, 0), [A], H, 1, True, b.params, off, dueling=True)
     return spec, (b.values if b.init else None)

@@ -44,6 +44,17 @@ class PpoHparams(Structure):
                 ("mask_invert", c_int32)]
 
 
+class DqnHparams(Structure):
+    """``srl_dqn_hparams`` (include/srl_hip.h)."""
+    _fields_ = [("gamma", c_double), ("scalar_transform_eps", c_double), ("priority_interpolation_eta", c_double),
+                ("huber_delta", c_float), ("n", c_int32), ("apply_scalar_transform", c_int32), ("double_q", c_int32),
+                ("value_loss", c_int32), ("pad_", c_int32)]
+
+
+# TD-term slots (srl_hip.h: SRL_DQ_*)
+DQ_VLOSS, DQ_Q, DQ_Y, DQ_QINV, DQ_YINV, DQ_TD, DQ_TDMAX, DQ_MASK, DQ_COUNT = range(9)
+
+
 class GemmDesc(Structure):
     _fields_ = [("M", c_int64), ("N", c_int64), ("K", c_int64), ("A", c_void_p), ("lda", c_int64),
                 ("a_kmajor", c_int32), ("B", c_void_p), ("ldb", c_int64), ("b_kmajor", c_int32), ("C", c_void_p),
@@ -271,6 +282,11 @@ _SIGNATURES = {
     "srl_allreduce_stats_f64x3": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "srl_allreduce_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "srl_broadcast_params": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "srl_dqn_td_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 6 + [c_int, c_int, c_int,
+                                   POINTER(DqnHparams), c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "srl_epsilon_greedy_sample": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_long,
+                                          c_int, c_int, c_uint64, c_uint64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "srl_polyak_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -655,6 +671,59 @@ def categorical_sample(logits, avail, is_eval, head_dims, seed, offset, action_o
                                      len(head_dims), _i32_array(head_dims), int(seed), int(offset),
                                      _ptr(action_out, torch.int64, "action_out"), _ptr(logp, torch.float32, "logp"), int(row0)),
         "srl_categorical_sample")
+
+
+def dqn_td_fwd_bwd(adv, v, target_adv, target_v, action, reward, done, truncated, weight, T, B, hp: DqnHparams, d_adv, d_v, terms,
+                   priorities):
+    """``srl_dqn_td_fwd_bwd``: adv / target_adv / d_adv are [T*B, A] matrices whose rows may lie further apart than A (the pitch of
+    a wider buffer they are a view of); every other operand is dense with T*B (weight, priorities: B) entries."""
+    n, A = adv.shape
+    if n != T * B or target_adv.shape != adv.shape or d_adv.shape != adv.shape:
+        raise HipError(f"dqn_td_fwd_bwd: expected [{T * B}, A] head outputs, got {tuple(adv.shape)}, {tuple(target_adv.shape)}, "
+                       f"{tuple(d_adv.shape)}")
+    for name, t, cnt in (("v", v, n), ("target_v", target_v, n), ("action", action, n), ("reward", reward, n), ("done", done, n),
+                         ("truncated", truncated, n), ("d_v", d_v, n), ("priorities", priorities, B), ("terms", terms, DQ_COUNT)):
+        if t.numel() != cnt:
+            raise HipError(f"dqn_td_fwd_bwd: {name} holds {t.numel()} entries, expected {cnt}")
+    if weight is not None and weight.numel() != B:
+        raise HipError(f"dqn_td_fwd_bwd: weight holds {weight.numel()} entries, expected {B}")
+    f, u8 = torch.float32, torch.uint8
+    (pa, lda), (pt, ldt), (pd, ldd) = _rows_ptr(adv, "adv"), _rows_ptr(target_adv, "target_adv"), _rows_ptr(d_adv, "d_adv")
+    _check(
+        lib().srl_dqn_td_fwd_bwd(_stream(), pa, lda, _ptr(v, f, "v"), pt, ldt, _ptr(target_v, f, "target_v"),
+                                 _ptr(action, torch.int32, "action"), _ptr(reward, f, "reward"), _ptr(done, u8, "done"),
+                                 _ptr(truncated, u8, "truncated"), _ptr(weight, f, "weight"), int(T), int(B), int(A),
+                                 ctypes.byref(hp), pd, ldd, _ptr(d_v, f, "d_v"), _ptr(terms, torch.float64, "terms"),
+                                 _ptr(priorities, f, "priorities")), "srl_dqn_td_fwd_bwd")
+
+
+def epsilon_greedy_sample(adv, v, target_adv, target_v, epsilon, is_eval, double_q, seed, offset, action, value, target_value,
+                          row0=0):
+    """``srl_epsilon_greedy_sample``: adv / target_adv [n, A] with a row pitch, everything else dense with n entries."""
+    n, A = adv.shape
+    if target_adv.shape != adv.shape:
+        raise HipError(f"epsilon_greedy_sample: target_adv {tuple(target_adv.shape)} vs adv {tuple(adv.shape)}")
+    for name, t in (("v", v), ("target_v", target_v), ("epsilon", epsilon), ("action", action), ("value", value),
+                    ("target_value", target_value)) + ((("is_eval", is_eval),) if is_eval is not None else ()):
+        if t.numel() != n:
+            raise HipError(f"epsilon_greedy_sample: {name} holds {t.numel()} entries, expected {n}")
+    f = torch.float32
+    (pa, lda), (pt, ldt) = _rows_ptr(adv, "adv"), _rows_ptr(target_adv, "target_adv")
+    _check(
+        lib().srl_epsilon_greedy_sample(_stream(), pa, lda, _ptr(v, f, "v"), pt, ldt, _ptr(target_v, f, "target_v"),
+                                        _ptr(epsilon, f, "epsilon"), _ptr(is_eval, torch.uint8, "is_eval"), n, int(A),
+                                        int(bool(double_q)), int(seed), int(offset), int(row0),
+                                        _ptr(action, torch.int64, "action"), _ptr(value, f, "value"),
+                                        _ptr(target_value, f, "target_value")), "srl_epsilon_greedy_sample")
+
+
+def polyak_update(target, param, tau):
+    """target <- (1 - tau) target + tau param over two flat float32 buffers; tau = 1 is an exact copy."""
+    if target.numel() != param.numel():
+        raise HipError(f"polyak_update: {target.numel()} vs {param.numel()} entries")
+    _check(
+        lib().srl_polyak_update(_stream(), _ptr(target, torch.float32, "target"), _ptr(param, torch.float32, "param"),
+                                target.numel(), float(tau)), "srl_polyak_update")
 
 
 def categorical_log_softmax(logits, avail, head_dims, out):
