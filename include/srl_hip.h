@@ -206,6 +206,19 @@ int srl_gru_seq_fwd(void* stream, float* gi, float* gh, const float* w_hh, const
 int srl_gru_seq_bwd(void* stream, const float* dy, int64_t ld_dy, float* gates, float* gh, const float* w_hh,
                     const float* hin, const uint8_t* reset, int64_t N, int H, int C);
 
+/* One time step in one launch at the wide widths (added at ABI 22: additive, the version is unchanged; csrc/rnn_step.hip; H a
+ * multiple of 16, at least 128:
+ * srl_rnn_step_supported(kind, H), kind 0 GRU, 1 LSTM): what srl_gemm (W_hh h_in + b_hh) followed by srl_gru_cell_fwd /
+ * srl_lstm_cell_fwd does, on the same buffers and leaving the same saved values (GRU: gi -> gates, gh written in full; LSTM:
+ * pre = W_ih x + b_ih on entry -> activated gates), so srl_gru_cell_bwd / srl_lstm_cell_bwd follow unchanged.  N any value.
+ * hin_t (and cin_t) are read by every workgroup: they must not alias y_t, hin_next or cin_next.  All tensors 16-byte aligned.
+ * hin_next / cin_next (optional, both or neither for the LSTM) = the new state * (1 - reset_next). */
+int srl_rnn_step_supported(int kind, int H);
+int srl_gru_step_fwd(void* stream, float* gi_t, float* gh_t, const float* w_hh, const float* b_hh, const float* hin_t,
+                     const uint8_t* reset_next, int64_t N, int H, float* y_t, float* hin_next);
+int srl_lstm_step_fwd(void* stream, float* pre_t, const float* w_hh, const float* b_hh, const float* hin_t, const float* cin_t,
+                      const uint8_t* reset_next, int64_t N, int H, float* y_t, float* cnew_t, float* hin_next, float* cin_next);
+
 /* Rows of D floats between time-major [T*B] and chunk-major order: dst[(c, k*B + b)] = src[((k*C + c), b)]
  * (modules/utils.py:164-182 `to_chunk`: torch.cat(torch.split(x, C, dim=0), dim=1)); inverse != 0 undoes it. */
 int srl_chunk_rows(void* stream, const float* src, float* dst, int T, int B, int C, int D, int inverse);

@@ -9,12 +9,21 @@ The online and the target network are two executors over two parameter sets of o
 product.  ``analyze`` does not gather: it returns both networks' head outputs for every row, and the trainer's TD kernel
 (``csrc/dqn.hip``) forms Q, the greedy action and the gathers itself.  ``rollout`` samples with ``srl_epsilon_greedy_sample``.
 
+With ``num_rnn_layers > 0`` the agent is the recurrent one (R2D2): an auto-reset GRU / LSTM between the trunk and the towers
+(``algorithm/rnnpath.py``), chunks of ``chunk_len`` steps starting from the stored ``policy_state.hx``, and -- with
+``burn_in_steps`` -- a burn-in pass through the online network that gives both networks their initial state (``burn_in_plan``).
+
 DIFFERENCES: exploration draws come from a counter-based Philox stream keyed by ``(seed, call counter)`` instead of torch's
-generator.  ``num_rnn_layers > 0`` (R2D2) and ``dueling=False`` raise ``NotImplementedError`` at construction.
+generator.  The reference's recurrent towers read 512 columns whatever ``hidden_dim`` is (:70), so it runs only at
+``hidden_dim=512``, and so does this policy by default: another width with ``num_rnn_layers > 0`` raises.  The extra keyword
+``rnn_towers_read_hidden_dim=True`` is this project's extension: towers that read ``hidden_dim`` columns (the reference at 512),
+at any multiple of 4 -- it exists so that the small-width chunk kernels can be tested under this agent.
+``dueling=False``, ``rnn_type='gtrxl'``, ``rnn_include_last_action`` / ``rnn_include_last_reward`` and data parallelism raise
+``NotImplementedError``.
 """
 import dataclasses
 from collections import OrderedDict
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -22,7 +31,7 @@ import torch
 from srl_amd import hip
 from srl_amd.algorithm import netspec as ns
 from srl_amd.algorithm.actor_critic import to_device_leaf
-from srl_amd.algorithm.hipnet import HipNet
+from srl_amd.algorithm.hipnet import HipNet, RnnCtx
 from srl_amd.api import policy as policy_api
 from srl_amd.api.env_utils import DiscreteAction
 from srl_amd.namedarray import NamedArray
@@ -53,6 +62,30 @@ class DQNHeadOutputs:
     B: int
 
 
+BurnInPlan = NamedTuple("BurnInPlan", [("num_chunks", int), ("chunk", int), ("windows", list), ("state_rows", list)])
+
+
+def burn_in_plan(sample_rows: int, burn_in_steps: int, chunk_len: int) -> BurnInPlan:
+    """The index arithmetic of ``_dqn_analyze`` (:168-193) for a sample of ``sample_rows`` steps: the ``T = sample_rows -
+    burn_in_steps`` analysed steps are ``num_chunks = T // chunk_len`` chunks of ``chunk = T / num_chunks`` steps (chunk ``k`` is rows
+    ``[burn + k chunk, burn + (k + 1) chunk)`` of the sample; column ``k B + b`` of a recurrent pass).  ``state_rows[k]``: the row of
+    the sample whose stored ``policy_state.hx`` starts chunk ``k``'s first pass.  Without burn-in that is the chunk's first row and
+    ``windows`` is empty.  With burn-in, ``windows[k] = (k chunk_len, k chunk_len + burn)`` are the rows of the FULL sample the
+    online network replays first, from the state stored at ``k chunk_len``: the reference's literal indices (:183).  They end right
+    in front of chunk ``k`` only when ``chunk == chunk_len``; otherwise (44 analysed steps with ``chunk_len=40``: one chunk of 44;
+    10 with ``chunk_len=4``: two of 5) the later windows start ``k (chunk - chunk_len)`` rows early, as in the reference."""
+    burn, cl = int(burn_in_steps), int(chunk_len)
+    T = int(sample_rows) - burn
+    K = max(T, 0) // cl  # (:169-173: 44 steps with chunk_len=40 are one chunk of 44)
+    if K == 0 or T % K:
+        raise ValueError(f"atari-dqn: {sample_rows} steps less {burn} burn-in steps do not split into {K} equal chunks "
+                         f"(chunk_len={cl})")
+    C = T // K
+    if not burn:
+        return BurnInPlan(K, C, [], [k * C for k in range(K)])
+    return BurnInPlan(K, C, [(k * cl, k * cl + burn) for k in range(K)], [k * cl for k in range(K)])
+
+
 class AtariDQNPolicy(policy_api.Policy):
 
     def __init__(self,
@@ -67,17 +100,32 @@ class AtariDQNPolicy(policy_api.Policy):
                  rnn_include_last_action: bool = False,
                  rnn_include_last_reward: bool = False,
                  use_env_epsilon: bool = True,
-                 epsilon_scheduler=None):
+                 epsilon_scheduler=None,
+                 rnn_towers_read_hidden_dim: bool = False):
         super().__init__()
-        if num_rnn_layers > 0:
-            raise NotImplementedError("atari-dqn: num_rnn_layers > 0 (the recurrent R2D2 agent) is not implemented on the HIP path")
         if not dueling:
             raise NotImplementedError("atari-dqn: dueling=False is not implemented on the HIP path (the kernels form "
                                       "Q = v + adv - mean adv themselves)")
+        if num_rnn_layers > 0 and rnn_type == "gtrxl":
+            raise NotImplementedError("atari-dqn: rnn_type='gtrxl' is not implemented on the HIP path (only the GRU and LSTM "
+                                      "cells of AutoResetRNN are)")
+        if num_rnn_layers > 0 and rnn_type not in ("gru", "lstm"):
+            raise NotImplementedError(f"RNN type {rnn_type} has not been implemented.")  # autoreset_rnn.py:27
+        if num_rnn_layers > 0 and (rnn_include_last_action or rnn_include_last_reward):
+            raise NotImplementedError("atari-dqn: rnn_include_last_action / rnn_include_last_reward (extra input columns of the "
+                                      "recurrent layer) are not implemented on the HIP path")
+        if num_rnn_layers > 0 and int(hidden_dim) != 512 and not rnn_towers_read_hidden_dim:
+            raise NotImplementedError(f"atari-dqn: the reference's recurrent towers read 512 columns whatever hidden_dim is (:70), so "
+                                      f"its recurrent agent exists at hidden_dim=512 only (got {hidden_dim}); "
+                                      "rnn_towers_read_hidden_dim=True builds this project's extension, towers that read hidden_dim")
+        if num_rnn_layers > 0 and torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise NotImplementedError("atari-dqn: data-parallel training of the recurrent agent is not implemented (a process "
+                                      "group is initialised)")
         if not use_env_epsilon and epsilon_scheduler is None:
             raise ValueError("atari-dqn: use_env_epsilon=False needs an epsilon_scheduler (an object with `get(step)`)")
         np.random.seed(seed)  # atari_dqn_policy.py:134
-        self.spec, init = ns.build_atari_dqn_netspec(int(act_dim), hidden_dim, seed=seed)
+        self.spec, init = ns.build_atari_dqn_netspec(int(act_dim), hidden_dim, seed=seed, num_rnn_layers=int(num_rnn_layers),
+                                                     rnn_type=rnn_type)
         self._net = HipNet(self.spec, self.device)
         self._net.load_reference_state(init)
         # the target network: its own parameter state; it takes no gradient and keeps no tape
@@ -89,7 +137,8 @@ class AtariDQNPolicy(policy_api.Policy):
         self._chunk_len = int(chunk_len)
         self._use_env_epsilon = bool(use_env_epsilon)
         self._exploration = epsilon_scheduler
-        self._default_policy_state = DQNPolicyState(hx=None, epsilon=np.ones(1, dtype=np.float32))
+        hx = np.zeros((self.spec.num_rnn_layers, self.spec.rnn_state_width), dtype=np.float32) if num_rnn_layers > 0 else None  # :140
+        self._default_policy_state = DQNPolicyState(hx=hx, epsilon=np.ones(1, dtype=np.float32))
         self._version = -1
         self._seed = int(seed)
         self._rollout_calls = 0
@@ -163,23 +212,44 @@ class AtariDQNPolicy(policy_api.Policy):
     def _dqn_analyze(self, sample, burn_in_steps=0) -> DQNHeadOutputs:
         """Rows [burn_in_steps, Tb) of ``sample`` (leaves ``[Tb, B, ...]``) through both networks (:168-236).  Without a recurrent
         layer the reference's chunking only permutes independent rows, so they are evaluated in place; its shape requirement
-        (``modules/utils.py:176``) is kept."""
+        (``modules/utils.py:176``) is kept.  With one, the passes run in the reference's order -- burn-in through the online
+        network (no tape; ``burn_in_plan``), target (no tape), online (tape) -- and the burn-in's final state starts both others."""
         hip.require_gpu()
         burn = int(burn_in_steps)
         Tb, B = sample.on_reset.shape[0], sample.on_reset.shape[1]
         T = Tb - burn
-        chunks = max(T, 0) // self._chunk_len  # (:169-173: 44 steps with chunk_len=40 are one chunk of 44)
-        if chunks == 0 or T % chunks:
-            raise ValueError(f"atari-dqn: {Tb} steps less {burn} burn-in steps do not split into {chunks} equal chunks "
-                             f"(chunk_len={self._chunk_len})")
+        plan = burn_in_plan(Tb, burn, self._chunk_len)
         n = T * B
-        frames = to_device_leaf(sample.obs.obs, self.device, "obs")[burn:]
+        full = to_device_leaf(sample.obs.obs, self.device, "obs")
+        frames = full[burn:]
         obs = {"obs": frames.reshape(n, *frames.shape[2:])}
         action = to_device_leaf(sample.action.x, self.device, "index")[burn:].reshape(n)
-        tadv, tv = self._target.forward(obs, n, keep_tape=False)
-        adv, v = self._net.forward(obs, n, keep_tape=True)
+        ctx = None
+        if self.spec.num_rnn_layers:
+            ctx = self._recurrent_ctx(sample, full, plan, burn, Tb, B)
+        tadv, tv = self._target.forward(obs, n, keep_tape=False, rnn=ctx)
+        adv, v = self._net.forward(obs, n, keep_tape=True, rnn=ctx)
         self._analysis = n
         return DQNHeadOutputs(adv, v, tadv, tv, action, T, B)
+
+    def _recurrent_ctx(self, sample, full, plan: BurnInPlan, burn, Tb, B) -> RnnCtx:
+        """The time structure of the analysed rows and each chunk's initial state: the stored one, or what the burn-in pass leaves."""
+        L, SW, K, C = self.spec.num_rnn_layers, self.spec.rnn_state_width, plan.num_chunks, plan.chunk
+        ps = sample.policy_state
+        if ps is None or ps.hx is None:
+            raise ValueError("atari-dqn: the recurrent agent's sample carries no policy_state.hx")
+        hx = to_device_leaf(ps.hx, self.device, "real").reshape(Tb, B, L, SW)
+        on_reset = to_device_leaf(sample.on_reset, self.device, "flag").reshape(Tb, B)
+        stored = torch.stack([hx[r] for r in plan.state_rows]).reshape(K * B, L, SW).permute(1, 0, 2).contiguous()  # column k B + b
+        if plan.windows:
+            w_frames = torch.cat([full[a:b] for a, b in plan.windows], dim=0)   # [K burn, B, ...]: chunk k of the pass = window k
+            w_reset = torch.stack([on_reset[a:b] for a, b in plan.windows]).permute(1, 0, 2).reshape(burn, K * B).contiguous()
+            m = K * burn * B
+            self._net.forward({"obs": w_frames.reshape(m, *w_frames.shape[2:])}, m, keep_tape=False,
+                              rnn=RnnCtx(K * burn, B, burn, {"a:": stored}, w_reset))
+            stored = self._net.last_state["a:"].clone()
+        reset = on_reset[burn:].reshape(K, C, B).permute(1, 0, 2).reshape(C, K * B).contiguous()
+        return RnnCtx(Tb - burn, B, C, {"a:": stored}, reset)
 
     def backward_dqn(self, d_adv: torch.Tensor, d_v: torch.Tensor):
         """Back-propagate d loss / d (advantages, state values) of the last ``analyze`` into ``net.grad``."""
@@ -202,11 +272,22 @@ class AtariDQNPolicy(policy_api.Policy):
         is_eval = to_device_leaf(np.broadcast_to(is_eval, (n,)) if is_eval.size == 1 else is_eval, self.device, "flag")
         obs = {"obs": to_device_leaf(frames, self.device, "obs")}
         eps = to_device_leaf(eps_host, self.device, "real").reshape(n)
+        ctx = None
+        if self.spec.num_rnn_layers:   # [n, layers, SW] in and out; on_reset masks the INCOMING state (:250-252), for both networks
+            L, SW = self.spec.num_rnn_layers, self.spec.rnn_state_width
+            ps = requests.policy_state
+            if ps is None or ps.hx is None:
+                raise ValueError("atari-dqn: the recurrent agent's request carries no policy_state.hx")
+            h0 = to_device_leaf(np.asarray(ps.hx), self.device, "real").reshape(n, L, SW).permute(1, 0, 2).contiguous()
+            rs = np.asarray(requests.on_reset).reshape(-1)   # (a request built without one carries the default, one False)
+            reset = to_device_leaf(np.broadcast_to(rs, (n,)) if rs.size == 1 else rs, self.device, "flag").reshape(1, n)
+            ctx = RnnCtx(1, n, 1, {"a:": h0}, reset)
+        hx_out = None
         self._net.begin_serving()
         self._target.begin_serving()
         try:
-            adv, v = self._net.forward(obs, n, keep_tape=False)
-            tadv, tv = self._target.forward(obs, n, keep_tape=False)
+            adv, v = self._net.forward(obs, n, keep_tape=False, rnn=ctx)
+            tadv, tv = self._target.forward(obs, n, keep_tape=False, rnn=ctx)   # (the incoming state, not the online net's new one)
             action = torch.empty((n, 1), dtype=torch.int64, device=self.device)
             value = torch.empty((n, 1), dtype=torch.float32, device=self.device)
             target_value = torch.empty((n, 1), dtype=torch.float32, device=self.device)
@@ -214,11 +295,13 @@ class AtariDQNPolicy(policy_api.Policy):
                                       value, target_value)
             self._rollout_calls += 1
             out = [t.cpu().numpy() for t in (action, value, target_value)]
+            if ctx is not None:
+                hx_out = self._net.last_state["a:"].permute(1, 0, 2).cpu().numpy()
         finally:
             self._net.end_serving()
             self._target.end_serving()
         return policy_api.RolloutResult(action=DiscreteAction(out[0]),
-                                        policy_state=DQNPolicyState(hx=None, epsilon=eps_host),
+                                        policy_state=DQNPolicyState(hx=hx_out, epsilon=eps_host),
                                         analyzed_result=DQNRolloutAnalyzedResult(value=out[1], target_value=out[2]))
 
 

@@ -1464,7 +1464,11 @@ class HipNet:
                     if feat is None:
                         feat = self._buf(f"{tag}concat", n, width)
                     into = (feat.ptr + 4 * (r0 * width + col), width)   # the block writes its columns of the concatenation itself
-                outs.append(self._encoder_fwd(enc, self._enc_obs(enc, obs, r0, r1), r1 - r0, ptag, tape, lnheads=lnheads, into=into))
+                o = self._encoder_fwd(enc, self._enc_obs(enc, obs, r0, r1), r1 - r0, ptag, tape, lnheads=lnheads, into=into)
+                if o is not None and o.rows != r1 - r0:   # an encoder that closes in a convolution: Flatten, [rows*OH*OW, C] -> [rows, OH*OW*C]
+                    assert o.ld == o.cols and o.rows * o.cols == (r1 - r0) * enc.out_dim
+                    o = Buf(o.ptr, enc.out_dim, r1 - r0, enc.out_dim, o.mask)
+                outs.append(o)
                 tapes.append(tape)
                 col += enc.out_dim
             enc_tapes.append(tapes)
@@ -1482,6 +1486,9 @@ class HipNet:
                 col += o.cols
         bb_tape = []
         st = _Walk(None, n, tag, bb_tape, cur=feat, track=False)
+        closing = encoders[0].layers[-1] if len(encoders) == 1 and encoders[0].layers else None
+        if isinstance(closing, ns.ConvSpec):   # the backbone's first layer applies the closing convolution's derivative on the way back
+            st.cur_act = closing.act
         last_rnn = max((i for i, L in enumerate(backbone) if isinstance(L, ns.GruSpec)), default=-1)
         handlers = self.FWD_HANDLERS
         for li, L in enumerate(backbone):
@@ -1506,6 +1513,10 @@ class HipNet:
             col = 0
             for tape, wdt in zip(enc_tapes[pi], widths):
                 sub = Buf(g.ptr + 4 * (r0 * g.ld + col), g.ld, r1 - r0, wdt)
+                if tape and tape[-1].out_cols != wdt:   # the Flatten behind a closing convolution, undone
+                    oc = tape[-1].out_cols
+                    assert g.ld == wdt and wdt % oc == 0
+                    sub = Buf(sub.ptr, oc, (r1 - r0) * (wdt // oc), oc)
                 self._chain_bwd(tape, sub, tag, need_input_grad=False, dv=dv)
                 col += wdt
             if len(pieces) > 1:
@@ -1710,9 +1721,9 @@ class HipNet:
                 a_feat, c_feat = self._buf("a:dueling.adv_in", n, H), self._buf("a:dueling.v_in", n, H)
                 hip.copy2d(both.ptr, both.ld, a_feat.ptr, H, n, H)
                 hip.copy2d(both.ptr + 4 * H, both.ld, c_feat.ptr, H, n, H)
-                # the encoder ends in that Linear's ReLU (the other encoders end in a LayerNorm or a plain Linear, and the walk over
-                # an empty backbone reports no activation): the heads' data gradients apply its derivative
-                a_act = c_act = sp.obs_encoders[0].layers[-1].act
+                # the trunk ends in that Linear's ReLU, at the end of the backbone (the recurrent agent) or of the encoder (the walk
+                # over an empty backbone reports no activation): the heads' data gradients apply its derivative
+                a_act = c_act = (sp.actor_backbone or sp.obs_encoders[0].layers)[-1].act
         else:
             fc = self._fused_fwd("c:", sp.state_encoders, sp.critic_backbone, sp.critic_head if heads_in else None, obs, n,
                                  out=value_t if heads_in else None)

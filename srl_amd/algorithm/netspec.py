@@ -898,40 +898,73 @@ def build_dmlab_netspec(obs_shapes: Dict, action_dim: int, hidden_dim: int = 512
     return spec, (b.values if b.init else None)
 
 
-def build_atari_dqn_netspec(act_dim: int, hidden_dim: int = 512, seed: Optional[int] = None):
-    """``_AtariDQN`` with ``dueling=True`` and no recurrent layers (``q_learning/game_policies/atari_dqn_policy.py:29-101``): 4 x 84 x 84
-    frames ``/ 255``, ``Conv2d(4, 32, 8, 4) -> Conv2d(32, 64, 4, 2) -> Conv2d(64, 64, 3, 1)`` with ReLU behind each, Flatten, and two
-    towers ``fc`` = Linear(3136, H)-ReLU-Linear(H, A) (advantages) and ``fc_v`` = Linear(3136, H)-ReLU-Linear(H, 1) (state value).
+def build_atari_dqn_netspec(act_dim: int, hidden_dim: int = 512, seed: Optional[int] = None, num_rnn_layers: int = 0,
+                            rnn_type: str = "gru"):
+    """``_AtariDQN`` with ``dueling=True`` (``q_learning/game_policies/atari_dqn_policy.py:29-101``): 4 x 84 x 84 frames ``/ 255``,
+    ``Conv2d(4, 32, 8, 4) -> Conv2d(32, 64, 4, 2) -> Conv2d(64, 64, 3, 1)`` with ReLU behind each, Flatten, and two towers ``fc`` =
+    Linear(F, H)-ReLU-Linear(H, A) (advantages) and ``fc_v`` = Linear(F, H)-ReLU-Linear(H, 1) (state value).  Without a recurrent
+    layer F = 3136, the flattened trunk; with ``num_rnn_layers > 0`` (R2D2) ``AutoResetRNN(3136 -> H)`` of ``rnn_type`` (``gru`` /
+    ``lstm``) sits between the trunk and the towers, which then read its output.
 
-    The parameter table keeps the reference's names and ``state_dict`` order (``conv1.weight`` ... ``fc_v.2.bias``; the policy adds
-    ``net.`` / ``target_net.``) and the initial values replay its constructor (torch's default resets, in module order).  In the
-    flat buffer ``fc_v.0.weight`` follows ``fc.0.weight`` and ``fc_v.0.bias`` follows ``fc.0.bias``: the two first Linears are ONE
-    ``[2H, 3136]`` matrix, the trunk closes in one product, and the heads read the halves of its output (``NetSpec.dueling``)."""
-    A, H = int(act_dim), int(hidden_dim)
+    The parameter table keeps the reference's names and ``state_dict`` order (``conv1.weight`` ... ``conv3.bias``, the recurrent
+    ``rnn._AutoResetRNN__net.weight_ih_l0`` ... per layer, ``fc.0.weight`` ... ``fc_v.2.bias``; the policy adds ``net.`` /
+    ``target_net.``) and the initial values replay its constructor (torch's default resets, in module order).  In the flat buffer
+    ``fc_v.0.weight`` follows ``fc.0.weight`` and ``fc_v.0.bias`` follows ``fc.0.bias``: the two first Linears are ONE ``[2H, F]``
+    matrix, the trunk closes in one product, and the heads read the halves of its output (``NetSpec.dueling``).  Whatever reads
+    the flattened trunk (``fc.0`` / ``fc_v.0``, or ``weight_ih_l0``) has its columns stored in the trunk's NHWC order
+    (``fc_from_chw``).
+
+    DIFFERENCES: the reference's recurrent towers read 512 columns whatever ``hidden_dim`` is (:70), so it runs only at
+    ``hidden_dim = 512``; here they read ``hidden_dim`` columns, which is the reference at 512 and an extension (multiples of 4)
+    elsewhere."""
+    A, H, layers = int(act_dim), int(hidden_dim), int(num_rnn_layers)
     if H % 4:
         raise NotImplementedError(f"atari-dqn: hidden_dim must be a multiple of 4 (the towers' first layers share one matrix), got {H}")
+    if layers and rnn_type not in ("gru", "lstm"):
+        raise NotImplementedError(f"atari-dqn: rnn_type `{rnn_type}`: only the GRU and LSTM cells of AutoResetRNN are on the HIP path")
     c, h, w = 4, 84, 84
     b = _Builder(seed)
-    layers = [ObsScaleSpec("scale", (c, h, w), 1.0 / 255.0)]
+    layers_enc = [ObsScaleSpec("scale", (c, h, w), 1.0 / 255.0)]
     for name, cout, k, stride in (("conv1", 32, 8, 4), ("conv2", 64, 4, 2), ("conv3", 64, 3, 1)):
         oh, ow = _conv_out(h, k, stride), _conv_out(w, k, stride)
         b.conv(name, c, cout, k, "conv_nhwc")
-        layers.append(ConvSpec(name, c, cout, k, stride, (h, w), (oh, ow), ACTS["relu"], first=False))
+        layers_enc.append(ConvSpec(name, c, cout, k, stride, (h, w), (oh, ow), ACTS["relu"], first=False))
         c, h, w = cout, oh, ow
-    flat = c * h * w
-    b.linear("fc.0", flat, H, "fc_from_chw", (c, h, w))
+    flat = feat = c * h * w
+    backbone, width = [], 0
+    if layers:
+        rp, ng = "rnn._AutoResetRNN__net", 4 if rnn_type == "lstm" else 3
+        bound = 1.0 / math.sqrt(H)   # nn.GRU / nn.LSTM.reset_parameters
+        for l in range(layers):
+            if l == 0:
+                v = None
+                if b.init:
+                    v = torch.empty((ng * H, flat))
+                    torch.nn.init.uniform_(v, -bound, bound)
+                b._add(f"{rp}.weight_ih_l0", (ng * H, flat), v, "fc_from_chw", (c, h, w))
+            else:
+                b.uniform(f"{rp}.weight_ih_l{l}", (ng * H, H), bound)
+            b.uniform(f"{rp}.weight_hh_l{l}", (ng * H, H), bound)
+            b.uniform(f"{rp}.bias_ih_l{l}", (ng * H,), bound)
+            b.uniform(f"{rp}.bias_hh_l{l}", (ng * H,), bound)
+        backbone.append(GruSpec(rp, H, layers, rnn_type, in_dim=flat))
+        feat, width = H, (2 * H if rnn_type == "lstm" else H)
+    lay = ("fc_from_chw", (c, h, w)) if not layers else ("plain", None)
+    b.linear("fc.0", feat, H, *lay)
     b.linear("fc.2", H, A)
-    b.linear("fc_v.0", flat, H, "fc_from_chw", (c, h, w))
+    b.linear("fc_v.0", feat, H, *lay)
     b.linear("fc_v.2", H, 1)
-    layers.append(LinearSpec("fc.0", flat, 2 * H, ACTS["relu"]))   # ... and fc_v.0 right behind it
+    merged = LinearSpec("fc.0", feat, 2 * H, ACTS["relu"])   # ... and fc_v.0 right behind it
+    (backbone if layers else layers_enc).append(merged)
     off = 0
     placed = [n for n in b.params if not n.startswith("fc")] + ["fc.0.weight", "fc_v.0.weight", "fc.0.bias", "fc_v.0.bias",
                                                                 "fc.2.weight", "fc.2.bias", "fc_v.2.weight", "fc_v.2.bias"]
     for name in placed:
         b.params[name].offset = off
         off += (b.params[name].numel + 3) // 4 * 4
-    assert b.params["fc_v.0.weight"].offset == b.params["fc.0.weight"].offset + H * flat
+    assert b.params["fc_v.0.weight"].offset == b.params["fc.0.weight"].offset + H * feat
     assert b.params["fc_v.0.bias"].offset == b.params["fc.0.bias"].offset + H
-    spec = NetSpec([EncoderSpec("obs", (4, 84, 84), layers, 2 * H)], [], None, None, LinearSpec("fc.2", H, A, 0),
-                   LinearSpec("fc_v.2", H, 1, 0), [A], H, 1, True, b.params, off, dueling=True)
+    spec = NetSpec([EncoderSpec("obs", (4, 84, 84), layers_enc, flat if layers else 2 * H)], backbone, None, None,
+                   LinearSpec("fc.2", H, A, 0), LinearSpec("fc_v.2", H, 1, 0), [A], H, 1, True, b.params, off,
+                   num_rnn_layers=layers, rnn_state_width=width, dueling=True)
     return spec, (b.values if b.init else None)

@@ -4,7 +4,7 @@ Mirror of ``DeepQLearning`` (reference ``legacy/algorithm/q_learning/deep_q_lear
 defaults, the same statistics, ``TrainerStepResult.priorities`` for a prioritised replay buffer, checkpoints that carry both
 networks and the optimiser.  One step is
 
-    policy.analyze (both networks' forward passes) -> srl_dqn_td_fwd_bwd (gathers, transforms, n-step return, loss, gradient
+    policy.analyze (both networks' forward passes; the recurrent agent's burn-in pass in front of them) -> srl_dqn_td_fwd_bwd (gathers, transforms, n-step return, loss, gradient
     with respect to the head outputs, priorities, statistics: csrc/dqn.hip) -> net.backward -> global-norm clip folded into the
     optimiser step (FlatOptimizer) -> soft target update every step, or a hard one by ``hard_update_interval`` -> inc_version
 
@@ -13,6 +13,9 @@ and the host waits for the device once, at the end, for the statistics and the p
 DIFFERENCES: a sample is consumed by the call that receives it (the reference's GPU prefetcher hands ``step`` the PREVIOUS
 call's sample and returns an empty result for the first one, :91-96).  ``use_popart=True`` (the reference's ``atari-dqn`` policy has
 no ``denormalize_target_value`` either) and ``mixed_precision=True`` raise at construction; a process group is refused.
+``burn_in_steps`` is handed to ``policy.analyze`` and cut off every other leaf, as in the reference; with the recurrent ``atari-dqn``
+the burn-in rows run through the online network only, and the conv features of rows that are both burn-in and analysed rows are
+computed twice (not shared between the passes).
 """
 import numpy as np
 import torch

@@ -3,7 +3,8 @@ forward and backward, and the row order of a recurrent pass.
 
 The n = T*B rows of a pass are time-major; the layers want them chunk-major (step c of all T/C chunks side by side, N = (T/C)*B
 rows per step).  `forward` / `backward` are the layer loop, once for both cells; `CELLS` holds what differs, the time loop (one
-launch where csrc/rnn_seq.hip has the width, else W_hh h + a cell of csrc/gru.hip per step) included.
+launch where csrc/rnn_seq.hip has the width; else per step, one fused launch at the wide widths of csrc/rnn_step.hip, or W_hh h + a
+cell of csrc/gru.hip) included.
 """
 from collections import namedtuple
 from typing import NamedTuple, Optional
@@ -43,8 +44,13 @@ class _Lstm:
         pre, hin, cin, cnew, y = s
         if seq:
             return hip.lstm_seq_fwd(pre.ptr, w_hh, b_hh, hin.ptr, cin.ptr, r(0), N, H, C, y.ptr, cnew.ptr)
+        fused = hip.rnn_step_supported("lstm", H)
         for c in range(C):
             o4, o1, o1n, nxt = 4 * c * N * 4 * H, 4 * c * N * H, 4 * (c + 1) * N * H, c + 1 < C
+            if fused:   # the product and the cell in one launch
+                hip.lstm_step_fwd(pre.ptr + o4, w_hh, b_hh, hin.ptr + o1, cin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1,
+                                  cnew.ptr + o1, hin.ptr + o1n if nxt else None, cin.ptr + o1n if nxt else None)
+                continue
             hip.gemm(N, 4 * H, H, hin.ptr + o1, H, 0, w_hh, H, 0, pre.ptr + o4, 4 * H, bias=b_hh, accumulate=True)
             hip.lstm_cell_fwd(pre.ptr + o4, cin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1, cnew.ptr + o1,
                               hin.ptr + o1n if nxt else None, cin.ptr + o1n if nxt else None)
@@ -72,8 +78,13 @@ class _Gru:
         gi, gh, hin, y = s
         if seq:
             return hip.gru_seq_fwd(gi.ptr, gh.ptr, w_hh, b_hh, hin.ptr, r(0), N, H, C, y.ptr)
+        fused = hip.rnn_step_supported("gru", H)
         for c in range(C):
             o3, o1, nxt = 4 * c * N * 3 * H, 4 * c * N * H, c + 1 < C
+            if fused:   # the product and the cell in one launch
+                hip.gru_step_fwd(gi.ptr + o3, gh.ptr + o3, w_hh, b_hh, hin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1,
+                                 hin.ptr + 4 * (c + 1) * N * H if nxt else None)
+                continue
             hip.gemm(N, 3 * H, H, hin.ptr + o1, H, 0, w_hh, H, 0, gh.ptr + o3, 3 * H, bias=b_hh)
             hip.gru_cell_fwd(gi.ptr + o3, gh.ptr + o3, hin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1,
                              hin.ptr + 4 * (c + 1) * N * H if nxt else None)

@@ -183,6 +183,9 @@ _SIGNATURES = {
     "srl_lstm_seq_bwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 5 + [c_int64, c_int, c_int]),
     "srl_gru_seq_fwd": (c_int, [c_void_p] * 7 + [c_int64, c_int, c_int, c_void_p]),
     "srl_gru_seq_bwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 5 + [c_int64, c_int, c_int]),
+    "srl_rnn_step_supported": (c_int, [c_int, c_int]),
+    "srl_gru_step_fwd": (c_int, [c_void_p] * 7 + [c_int64, c_int, c_void_p, c_void_p]),
+    "srl_lstm_step_fwd": (c_int, [c_void_p] * 7 + [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "srl_gru_cell_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
     "srl_gru_cell_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
                                  c_void_p]),
@@ -545,6 +548,28 @@ def rnn_seq_supported(kind: str, H: int) -> bool:
     """Whether the time loop of a chunk runs inside one launch for this cell and width (``srl_rnn_seq_supported``; SRL_RNN_SEQ=0
     switches it off for an A/B)."""
     return os.environ.get("SRL_RNN_SEQ", "1")[:1] != "0" and bool(lib().srl_rnn_seq_supported(1 if kind == "lstm" else 0, int(H)))
+
+
+# the fused recurrent step where the library has the width; tests/test_gpu_rnn_step.py and scripts/rnn_step_bench.py clear it for
+# their reference side (a plain attribute, like `HipNet._enc_fused`: the set of environment switches is closed)
+RNN_STEP_FUSED = True
+
+
+def rnn_step_supported(kind: str, H: int) -> bool:
+    """Whether one time step (W_hh h + b_hh and the cell) runs as one launch for this cell and width (``srl_rnn_step_supported``:
+    the wide widths, csrc/rnn_step.hip; clearing the module attribute ``RNN_STEP_FUSED`` switches it off for an A/B: the GEMM and
+    the cell launch again)."""
+    return RNN_STEP_FUSED and bool(lib().srl_rnn_step_supported(1 if kind == "lstm" else 0, int(H)))
+
+
+def gru_step_fwd(gi_ptr, gh_ptr, w_hh, b_hh, hin_ptr, reset_next_ptr, N, H, y_ptr, hin_next_ptr):
+    _check(lib().srl_gru_step_fwd(_stream(), gi_ptr, gh_ptr, w_hh, b_hh, hin_ptr, reset_next_ptr, int(N), int(H), y_ptr, hin_next_ptr),
+           "srl_gru_step_fwd")
+
+
+def lstm_step_fwd(pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_next_ptr, N, H, y_ptr, cnew_ptr, hin_next_ptr, cin_next_ptr):
+    _check(lib().srl_lstm_step_fwd(_stream(), pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_next_ptr, int(N), int(H), y_ptr, cnew_ptr,
+                                   hin_next_ptr, cin_next_ptr), "srl_lstm_step_fwd")
 
 
 def lstm_seq_fwd(pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_ptr, N, H, C, y_ptr, cnew_ptr):
