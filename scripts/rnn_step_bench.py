@@ -1,6 +1,6 @@
 """The fused recurrent step (csrc/rnn_step.hip) against the two-launch path (srl_gemm + cell, `hip.RNN_STEP_FUSED` cleared), on one GPU.
 
-  * the forward time loop over C = 40 steps, as ``rnnpath`` drives it: GRU and LSTM at H = 512 with N = 128 rows per step (the
+  * ``rnnpath``'s forward time loop over C = 40 steps, each path named: GRU and LSTM at H = 512 with N = 128 rows per step (the
     recurrent atari-dqn agent at 64 environments, two chunks) and at H = 128 with N = 256 (the football / overcooked width);
     device events around 10 loops, 9 repetitions, the two ways alternating; microseconds per loop, median / min / max;
   * one ``q-learning`` update of the recurrent ``atari-dqn`` agent (GRU, hidden_dim 512, chunk_len 40, burn_in_steps 40, B = 64;
@@ -20,6 +20,7 @@ import torch
 
 import srl_amd
 from srl_amd import hip
+from srl_amd.algorithm.rnnpath import CELLS, bufs_of
 
 DEV = "cuda:0"
 srl_amd.register_all()
@@ -34,25 +35,12 @@ def loop_case(kind, H, N, C=40, reps=9, inner=10):
     pre0 = rn(C, N, G * H)
     pre, gh, hin, cin, y, cnew = pre0.clone(), rn(C, N, 3 * H), rn(C, N, H), rn(C, N, H), rn(C, N, H), rn(C, N, H)
     rs = (torch.rand(C, N, generator=g) < 0.1).to(torch.uint8).to(DEV)
-    P = lambda t, c: t[c].data_ptr()
     rp = lambda c: rs.data_ptr() + c * N
+    k = CELLS[kind]
+    s = bufs_of(kind, gi=pre, gh=gh, hin=hin, cin=cin, cnew=cnew, y=y)
 
-    def run(fused):
-        for c in range(C):
-            nxt = c + 1 < C
-            if kind == "lstm" and fused:
-                hip.lstm_step_fwd(P(pre, c), w.data_ptr(), b.data_ptr(), P(hin, c), P(cin, c), rp(c + 1) if nxt else None, N, H, P(y, c),
-                                  P(cnew, c), P(hin, c + 1) if nxt else None, P(cin, c + 1) if nxt else None)
-            elif kind == "lstm":
-                hip.gemm(N, 4 * H, H, P(hin, c), H, 0, w.data_ptr(), H, 0, P(pre, c), 4 * H, bias=b.data_ptr(), accumulate=True)
-                hip.lstm_cell_fwd(P(pre, c), P(cin, c), rp(c + 1) if nxt else None, N, H, P(y, c), P(cnew, c),
-                                  P(hin, c + 1) if nxt else None, P(cin, c + 1) if nxt else None)
-            elif fused:
-                hip.gru_step_fwd(P(pre, c), P(gh, c), w.data_ptr(), b.data_ptr(), P(hin, c), rp(c + 1) if nxt else None, N, H, P(y, c),
-                                 P(hin, c + 1) if nxt else None)
-            else:
-                hip.gemm(N, 3 * H, H, P(hin, c), H, 0, w.data_ptr(), H, 0, P(gh, c), 3 * H, bias=b.data_ptr())
-                hip.gru_cell_fwd(P(pre, c), P(gh, c), P(hin, c), rp(c + 1) if nxt else None, N, H, P(y, c), P(hin, c + 1) if nxt else None)
+    def run(fused):   # the product's forward time loop, the path named
+        k.fwd(s, w.data_ptr(), b.data_ptr(), rp, N, H, C, path="fused" if fused else "cell")
 
     # results agree (same inputs): y of both ways
     ys = {}

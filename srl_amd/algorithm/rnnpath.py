@@ -2,9 +2,8 @@
 forward and backward, and the row order of a recurrent pass.
 
 The n = T*B rows of a pass are time-major; the layers want them chunk-major (step c of all T/C chunks side by side, N = (T/C)*B
-rows per step).  `forward` / `backward` are the layer loop, once for both cells; `CELLS` holds what differs, the time loop (one
-launch where csrc/rnn_seq.hip has the width; else per step, one fused launch at the wide widths of csrc/rnn_step.hip, or W_hh h + a
-cell of csrc/gru.hip) included.
+rows per step).  `forward` / `backward` are the layer loop, once for both cells; `CELLS` holds what differs, the time loop of a
+chunk included: `CELLS[kind].fwd / .bwd` on raw device addresses, on the path `time_loop_path` chooses or the caller names.
 """
 from collections import namedtuple
 from typing import NamedTuple, Optional
@@ -34,76 +33,99 @@ RnnSaved = NamedTuple("RnnSaved", [("layers", list), ("ctx", RnnCtx), ("cm", boo
 # (W_ih x + b_ih; d gi after the backward's time loop), `hin` (the state each step starts from) and `y`.  `state`: per H columns
 # of the stored state, (where the masked state goes, where the time loop leaves it).  `d_hh`: what holds d(W_hh h + b_hh) after
 # the backward's time loop.  `carries`: the [N, H] buffers the per-step backward hands from step to step, two of each.
+#
+# `fwd` / `bwd` are THE time loop of a chunk (C steps of N rows, step c at byte offset 4 c N width H of every buffer): the layer
+# loop below, the kernel tests and scripts/rnn_step_bench.py all run these.  `s`: the cell's `Bufs` of raw device addresses;
+# `r(c)`: the address of step c's reset flags, or None; `path`: one of PATHS, by default `time_loop_path`'s.  The backward of
+# "fused" is "cell"'s (the fused step saves what the cell saves); it writes d h_in (d c_in) of step c to the addresses
+# `carry(c)` gives, which stay untouched until step c - 1 has read them.
+PATHS = ("seq", "fused", "cell")
+
+
+def time_loop_path(kind: str, H: int, named: Optional[str] = None) -> str:
+    """Where the path is chosen: the whole chunk in one launch (csrc/rnn_seq.hip) where the library has the width; else W_hh h and
+    the cell of a step in one launch (csrc/rnn_step.hip); else srl_gemm plus a cell of csrc/gru.hip per step.  ``named``: the
+    caller's choice instead (the tests' and the bench's reference sides)."""
+    assert named is None or named in PATHS, named
+    return named or ("seq" if hip.rnn_seq_supported(kind, H) else "fused" if hip.rnn_step_supported(kind, H) else "cell")
+
+
 class _Lstm:
     """`gi` becomes the pre-activations W_ih x + b_ih + W_hh h + b_hh, then the activated gates i|f|g|o, then their gradient."""
-    gates, carries, d_hh = 4, ("dh0", "dh1", "dc0", "dc1"), "gi"
+    kind, gates, carries, d_hh = "lstm", 4, ("dh0", "dc0", "dh1", "dc1"), "gi"
     Bufs, fields = namedtuple("LstmBufs", "gi hin cin cnew y"), (("gi", 4), ("hin", 1), ("cin", 1), ("cnew", 1), ("y", 1))
     state = (("hin", "y"), ("cin", "cnew"))   # cat(h, c) per row (autoreset_rnn.py:31-39); both halves are reset together
 
-    def fwd(self, seq, s, w_hh, b_hh, r, N, H, C):
+    def fwd(self, s, w_hh, b_hh, r, N, H, C, path=None):
+        path = time_loop_path(self.kind, H, path)
         pre, hin, cin, cnew, y = s
-        if seq:
-            return hip.lstm_seq_fwd(pre.ptr, w_hh, b_hh, hin.ptr, cin.ptr, r(0), N, H, C, y.ptr, cnew.ptr)
-        fused = hip.rnn_step_supported("lstm", H)
+        if path == "seq":
+            return hip.lstm_seq_fwd(pre, w_hh, b_hh, hin, cin, r(0), N, H, C, y, cnew)
         for c in range(C):
             o4, o1, o1n, nxt = 4 * c * N * 4 * H, 4 * c * N * H, 4 * (c + 1) * N * H, c + 1 < C
-            if fused:   # the product and the cell in one launch
-                hip.lstm_step_fwd(pre.ptr + o4, w_hh, b_hh, hin.ptr + o1, cin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1,
-                                  cnew.ptr + o1, hin.ptr + o1n if nxt else None, cin.ptr + o1n if nxt else None)
+            out = (r(c + 1) if nxt else None, N, H, y + o1, cnew + o1, hin + o1n if nxt else None, cin + o1n if nxt else None)
+            if path == "fused":   # the product and the cell in one launch
+                hip.lstm_step_fwd(pre + o4, w_hh, b_hh, hin + o1, cin + o1, *out)
                 continue
-            hip.gemm(N, 4 * H, H, hin.ptr + o1, H, 0, w_hh, H, 0, pre.ptr + o4, 4 * H, bias=b_hh, accumulate=True)
-            hip.lstm_cell_fwd(pre.ptr + o4, cin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1, cnew.ptr + o1,
-                              hin.ptr + o1n if nxt else None, cin.ptr + o1n if nxt else None)
+            hip.gemm(N, 4 * H, H, hin + o1, H, 0, w_hh, H, 0, pre + o4, 4 * H, bias=b_hh, accumulate=True)
+            hip.lstm_cell_fwd(pre + o4, cin + o1, *out)
 
-    def bwd(self, seq, carry, s, dout, w_hh, r, N, H, C):
+    def bwd(self, s, dy, ld_dy, w_hh, r, N, H, C, carry, path=None):
+        path = time_loop_path(self.kind, H, path)
+        assert path == "seq" or ld_dy == H, "the per-step cells read d y in rows of H"
         pre, _, cin, cnew, _ = s
-        if seq:
-            return hip.lstm_seq_bwd(dout.ptr, dout.ld, pre.ptr, w_hh, cin.ptr, cnew.ptr, r(0), N, H, C)
+        if path == "seq":
+            return hip.lstm_seq_bwd(dy, ld_dy, pre, w_hh, cin, cnew, r(0), N, H, C)
         ch = cc = None
         for c in range(C - 1, -1, -1):
-            o4, o1, dh, dc = 4 * c * N * 4 * H, 4 * c * N * H, carry[c & 1], carry[2 + (c & 1)]
-            hip.lstm_cell_bwd(dout.ptr + 4 * c * N * dout.ld, ch, cc, r(c + 1) if c + 1 < C else None, pre.ptr + o4,
-                              cin.ptr + o1, cnew.ptr + o1, N, H, dc.ptr)
-            hip.gemm(N, H, 4 * H, pre.ptr + o4, 4 * H, 0, w_hh, H, 1, dh.ptr, H)  # d h_in(c) = d pre . W_hh
-            ch, cc = dh.ptr, dc.ptr
+            o4, o1, (dh, dc) = 4 * c * N * 4 * H, 4 * c * N * H, carry(c)
+            hip.lstm_cell_bwd(dy + 4 * c * N * ld_dy, ch, cc, r(c + 1) if c + 1 < C else None, pre + o4, cin + o1, cnew + o1, N, H, dc)
+            hip.gemm(N, H, 4 * H, pre + o4, 4 * H, 0, w_hh, H, 1, dh, H)  # d h_in(c) = d pre . W_hh
+            ch, cc = dh, dc
 
 
 class _Gru:
     """`gh` = W_hh h + b_hh stays apart from `gi` (b_hn sits inside r * (.)); both become their gradients."""
-    gates, carries, d_hh = 3, ("dh0", "dh1"), "gh"
+    kind, gates, carries, d_hh = "gru", 3, ("dh0", "dh1"), "gh"
     Bufs, fields = namedtuple("GruBufs", "gi gh hin y"), (("gi", 3), ("gh", 3), ("hin", 1), ("y", 1))
     state = (("hin", "y"),)
 
-    def fwd(self, seq, s, w_hh, b_hh, r, N, H, C):
+    def fwd(self, s, w_hh, b_hh, r, N, H, C, path=None):
+        path = time_loop_path(self.kind, H, path)
         gi, gh, hin, y = s
-        if seq:
-            return hip.gru_seq_fwd(gi.ptr, gh.ptr, w_hh, b_hh, hin.ptr, r(0), N, H, C, y.ptr)
-        fused = hip.rnn_step_supported("gru", H)
+        if path == "seq":
+            return hip.gru_seq_fwd(gi, gh, w_hh, b_hh, hin, r(0), N, H, C, y)
         for c in range(C):
             o3, o1, nxt = 4 * c * N * 3 * H, 4 * c * N * H, c + 1 < C
-            if fused:   # the product and the cell in one launch
-                hip.gru_step_fwd(gi.ptr + o3, gh.ptr + o3, w_hh, b_hh, hin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1,
-                                 hin.ptr + 4 * (c + 1) * N * H if nxt else None)
+            out = (r(c + 1) if nxt else None, N, H, y + o1, hin + 4 * (c + 1) * N * H if nxt else None)
+            if path == "fused":   # the product and the cell in one launch
+                hip.gru_step_fwd(gi + o3, gh + o3, w_hh, b_hh, hin + o1, *out)
                 continue
-            hip.gemm(N, 3 * H, H, hin.ptr + o1, H, 0, w_hh, H, 0, gh.ptr + o3, 3 * H, bias=b_hh)
-            hip.gru_cell_fwd(gi.ptr + o3, gh.ptr + o3, hin.ptr + o1, r(c + 1) if nxt else None, N, H, y.ptr + o1,
-                             hin.ptr + 4 * (c + 1) * N * H if nxt else None)
+            hip.gemm(N, 3 * H, H, hin + o1, H, 0, w_hh, H, 0, gh + o3, 3 * H, bias=b_hh)
+            hip.gru_cell_fwd(gi + o3, gh + o3, hin + o1, *out)
 
-    def bwd(self, seq, carry, s, dout, w_hh, r, N, H, C):
+    def bwd(self, s, dy, ld_dy, w_hh, r, N, H, C, carry, path=None):
+        path = time_loop_path(self.kind, H, path)
+        assert path == "seq" or ld_dy == H, "the per-step cells read d y in rows of H"
         gi, gh, hin, _ = s
-        if seq:
-            return hip.gru_seq_bwd(dout.ptr, dout.ld, gi.ptr, gh.ptr, w_hh, hin.ptr, r(0), N, H, C)
+        if path == "seq":
+            return hip.gru_seq_bwd(dy, ld_dy, gi, gh, w_hh, hin, r(0), N, H, C)
         prev = None
         for c in range(C - 1, -1, -1):
-            o3, o1, cur = 4 * c * N * 3 * H, 4 * c * N * H, carry[c & 1]
-            hip.gru_cell_bwd(dout.ptr + 4 * c * N * dout.ld, prev, r(c + 1) if c + 1 < C else None, gi.ptr + o3, gh.ptr + o3,
-                             hin.ptr + o1, N, H, cur.ptr)
+            o3, o1, (cur,) = 4 * c * N * 3 * H, 4 * c * N * H, carry(c)
+            hip.gru_cell_bwd(dy + 4 * c * N * ld_dy, prev, r(c + 1) if c + 1 < C else None, gi + o3, gh + o3, hin + o1, N, H, cur)
             # d h_in(c) = dh*z + d gh . W_hh: the carry of step c-1 (masked there by on_reset[c])
-            hip.gemm(N, H, 3 * H, gh.ptr + o3, 3 * H, 0, w_hh, H, 1, cur.ptr, H, accumulate=True)
-            prev = cur.ptr
+            hip.gemm(N, H, 3 * H, gh + o3, 3 * H, 0, w_hh, H, 1, cur, H, accumulate=True)
+            prev = cur
 
 
 CELLS = {"lstm": _Lstm(), "gru": _Gru()}
+
+
+def bufs_of(kind: str, **tensors):
+    """The cell's `Bufs` of the addresses of the torch tensors named by field (other names are ignored): for the callers of the
+    time loop outside `HipNet`."""
+    return CELLS[kind].Bufs(*[tensors[f].data_ptr() for f in CELLS[kind].Bufs._fields])
 
 
 def _encoders(spec):
@@ -169,7 +191,7 @@ def forward(net, G, x, tag: str, ctx: RnnCtx, cm: bool):
                 hip.copy2d(src, SW, s.y.ptr, H, N, H)
                 src = s.y.ptr
             hip.gru_mask_state(src, r(0), N, H, getattr(s, first).ptr)
-        k.fwd(hip.rnn_seq_supported(G.kind, H), s, w_hh, b_hh, r, N, H, C)   # the time loop: in one launch, or step by step
+        k.fwd(k.Bufs(*[b.ptr for b in s]), w_hh, b_hh, r, N, H, C)   # the time loop: in one launch, or step by step
         for j, (_, final) in enumerate(k.state):
             hip.copy2d(getattr(s, final).ptr + end, H, last[l].data_ptr() + 4 * j * H, SW, N, H)
         saved.append((inp, s))
@@ -187,10 +209,8 @@ def backward(net, G, saved: RnnSaved, dy, in_act: int, need_dx: bool, tag: str):
     for l in range(G.layers - 1, -1, -1):
         inp, s = saved.layers[l]
         w_ih, w_hh = net._p(f"{G.prefix}.weight_ih_l{l}"), net._p(f"{G.prefix}.weight_hh_l{l}")
-        carry = [net._buf(f"{name}.{b}", N, H) for b in k.carries]
-        seq = hip.rnn_seq_supported(G.kind, H)
-        assert seq or dout.ld == H, "the per-step cells read d y in rows of H"
-        k.bwd(seq, carry, s, dout, w_hh, r, N, H, ctx.C)
+        carry, per = [net._buf(f"{name}.{b}", N, H).ptr for b in k.carries], len(k.carries) // 2   # two alternating sets
+        k.bwd(k.Bufs(*[b.ptr for b in s]), dout.ptr, dout.ld, w_hh, r, N, H, ctx.C, lambda c: carry[per * (c & 1):][:per])
         # parameter gradients over all steps at once (the bias gradients, column sums, come out of the same kernels)
         net._wgrad(k.gates * H, H, n, getattr(s, k.d_hh), s.hin.ptr, H, net._g(f"{G.prefix}.weight_hh_l{l}"),
                    net._g(f"{G.prefix}.bias_hh_l{l}"))

@@ -1,16 +1,17 @@
 // GRU cell kernels for the recurrent backbone (reference legacy/algorithm/modules/autoreset_rnn.py:42-66 wrapping
 // torch.nn.GRU; recurrent_backbone.py:61-66).  The matrix products (W_ih x for all steps at once, W_hh h per step,
 // and the three gradient GEMMs) run on srl_gemm; these kernels do what sits between them, one time step at a time:
-//   forward   r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r*gh_n), h = (1-z)*n + z*h_in
-//             and the auto-reset of the NEXT step's input state, h_in' = h * (1 - on_reset')
-//   backward  the same cell differentiated by hand, leaving d gi / d gh in place of the saved gates.
+//   forward   the cell (csrc/rnn_cell.h: gru_fwd / lstm_fwd with the libm gates, spelled out here) and the auto-reset of the
+//             NEXT step's input state, h_in' = h * (1 - on_reset')
+//   backward  the same cell differentiated by hand (gru_bwd / lstm_bwd), leaving d gi / d gh in place of the saved gates.
 // Layout: every per-step block is [N, 3H] (gates r|z|n, torch order) or [N, H], rows = environment columns of
 // the chunked batch; the time loop lives on the host (it is inherently serial), so each launch is fully parallel.
+#include "rnn_cell.h"
 #include "srl_common.h"
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+using rnn_cell::LibmGates;
 
 __global__ __launch_bounds__(256) void gru_mask_state_kernel(const float* h, const uint8_t* reset, long N, int H,
                                                              float* out) {
@@ -28,9 +29,10 @@ __global__ __launch_bounds__(256) void gru_cell_fwd_kernel(float* gi, float* gh,
     const int j = (int)(i - row * H);
     float* gi_r = gi + row * 3 * H;
     const float* gh_r = gh + row * 3 * H;
-    const float r = sigmoidf_(gi_r[j] + gh_r[j]);
-    const float z = sigmoidf_(gi_r[H + j] + gh_r[H + j]);
-    const float n = tanhf(gi_r[2 * H + j] + r * gh_r[2 * H + j]);
+    // rnn_cell::gru_fwd, spelled out: hin is read after the gates (rnn_cell.h says why that is kept)
+    const float r = LibmGates::sigm(gi_r[j] + gh_r[j]);
+    const float z = LibmGates::sigm(gi_r[H + j] + gh_r[H + j]);
+    const float n = LibmGates::tanh(gi_r[2 * H + j] + r * gh_r[2 * H + j]);
     const float h = (1.0f - z) * n + z * hin[i];
     gi_r[j] = r, gi_r[H + j] = z, gi_r[2 * H + j] = n;  // saved for the backward pass (gh keeps its n part)
     y[i] = h;
@@ -48,20 +50,15 @@ __global__ __launch_bounds__(256) void gru_cell_bwd_kernel(const float* dy, cons
     float* q = gh + row * 3 * H;
     float dh = dy ? dy[i] : 0.f;
     if (carry && !(reset_next && reset_next[row])) dh += carry[i];  // d h_in(t+1) reaches h(t) unless t+1 was reset
-    const float r = g[j], z = g[H + j], n = g[2 * H + j], ghn = q[2 * H + j];
-    const float dn = dh * (1.0f - z);
-    const float dz = dh * (hin[i] - n);
-    const float dpn = dn * (1.0f - n * n);
-    const float dpr = dpn * ghn * r * (1.0f - r);
-    const float dpz = dz * z * (1.0f - z);
-    g[j] = dpr, g[H + j] = dpz, g[2 * H + j] = dpn;      // d gi
-    q[j] = dpr, q[H + j] = dpz, q[2 * H + j] = dpn * r;  // d gh
-    dh_direct[i] = dh * z;                                // the part of d h_in that does not go through W_hh
+    const auto b = rnn_cell::gru_bwd(dh, g[j], g[H + j], g[2 * H + j], q[2 * H + j], hin[i]);
+    g[j] = b.d_r, g[H + j] = b.d_z, g[2 * H + j] = b.d_n;     // d gi
+    q[j] = b.d_r, q[H + j] = b.d_z, q[2 * H + j] = b.d_gh_n;  // d gh
+    dh_direct[i] = b.direct;                                  // the part of d h_in that does not go through W_hh
   }
 }
 
 // LSTM (torch.nn.LSTM gate order i|f|g|o).  pre = W_ih x + b_ih + W_hh h_in + b_hh (both GEMMs accumulate into one
-// block).  c' = s(f)*c_in + s(i)*tanh(g), h = s(o)*tanh(c').  pre is overwritten with the activated gates.
+// block).  pre is overwritten with the activated gates.
 __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(float* pre, const float* cin, const uint8_t* reset_next,
                                                             long N, int H, float* y, float* cnew, float* hin_next,
                                                             float* cin_next) {
@@ -69,9 +66,10 @@ __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(float* pre, const fl
     const long row = i / H;
     const int j = (int)(i - row * H);
     float* p = pre + row * 4 * H;
-    const float gi = sigmoidf_(p[j]), gf = sigmoidf_(p[H + j]), gg = tanhf(p[2 * H + j]), go = sigmoidf_(p[3 * H + j]);
+    // rnn_cell::lstm_fwd, spelled out: cin is read after the gates (rnn_cell.h says why that is kept)
+    const float gi = LibmGates::sigm(p[j]), gf = LibmGates::sigm(p[H + j]), gg = LibmGates::tanh(p[2 * H + j]), go = LibmGates::sigm(p[3 * H + j]);
     const float c2 = gf * cin[i] + gi * gg;
-    const float h = go * tanhf(c2);
+    const float h = go * LibmGates::tanh(c2);
     p[j] = gi, p[H + j] = gf, p[2 * H + j] = gg, p[3 * H + j] = go;
     y[i] = h;
     cnew[i] = c2;
@@ -94,14 +92,9 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* dy, con
     float dh = dy ? dy[i] : 0.f;
     float dc = 0.f;
     if (carry_h && !cut) { dh += carry_h[i]; dc = carry_c[i]; }
-    const float gi = g[j], gf = g[H + j], gg = g[2 * H + j], go = g[3 * H + j];
-    const float tc = tanhf(cnew[i]);
-    dc += dh * go * (1.0f - tc * tc);
-    g[j] = dc * gg * gi * (1.0f - gi);
-    g[H + j] = dc * cin[i] * gf * (1.0f - gf);
-    g[2 * H + j] = dc * gi * (1.0f - gg * gg);
-    g[3 * H + j] = dh * tc * go * (1.0f - go);
-    dc_in[i] = dc * gf;
+    const auto b = rnn_cell::lstm_bwd<LibmGates>(dh, dc, g[j], g[H + j], g[2 * H + j], g[3 * H + j], cin[i], cnew[i]);
+    g[j] = b.d_i, g[H + j] = b.d_f, g[2 * H + j] = b.d_g, g[3 * H + j] = b.d_o;
+    dc_in[i] = b.dc_in;
   }
 }
 

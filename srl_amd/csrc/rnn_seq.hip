@@ -13,6 +13,7 @@
 // parameter-gradient products over all steps stay on srl_gemm before / after these kernels, and either path can run the other's
 // backward.  (A scalar-FMA version of this loop -- 16 rows per workgroup, W_hh in LDS -- was LDS-bound at 815 us per launch on
 // 30 720 rows x 10 steps where the per-step path takes ~200: the matrix cores are what makes the fusion pay.)
+#include "rnn_cell.h"
 #include "srl_common.h"
 
 #include "../../include/srl_hip.h"
@@ -21,19 +22,15 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// The gates on the hardware's exp2 / reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each) instead of libm's expf / tanhf and an IEEE
-// division: a step's 5 transcendentals per unit were ~4 800 vector instructions per 32 rows, as long as the step's 256 MFMAs, and
-// with one wavefront per SIMD the two add up.  |error| <= ~2e-7 absolute on values in [-1, 1] (tanh near 0 through 1 - 2 / (1 +
-// e^2x): absolute, not relative); SRL_RNN_FASTMATH=0 at build time restores libm.
+// The gates run on the hardware's exp2 / reciprocal (rnn_cell::FastGates, where the error bound is given); SRL_RNN_FASTMATH=0 at
+// build time restores libm.
 #ifndef SRL_RNN_FASTMATH
 #define SRL_RNN_FASTMATH 1
 #endif
 #if SRL_RNN_FASTMATH
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x)); }
-__device__ __forceinline__ float tanh_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177792681f * x)); }
+using Gates = rnn_cell::FastGates;
 #else
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float tanh_(float x) { return tanhf(x); }
+using Gates = rnn_cell::LibmGates;
 #endif
 __device__ __forceinline__ int ch_of(int e, int hb) { return (e & 3) + 8 * (e >> 2) + 4 * hb; }
 
@@ -139,11 +136,10 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_kernel(SeqArgs a) {
         if (KIND) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const float gi = sigm(p[0][e] + acc[0][e]), gf = sigm(p[1][e] + acc[1][e]);
-            const float gg = tanh_(p[2][e] + acc[2][e]), go = sigm(p[3][e] + acc[3][e]);
-            c2[e] = gf * cs[ub][e] + gi * gg;
-            yv[e] = go * tanh_(c2[e]);
-            p[0][e] = gi; p[1][e] = gf; p[2][e] = gg; p[3][e] = go;
+            const auto o = rnn_cell::lstm_fwd<Gates>(p[0][e] + acc[0][e], p[1][e] + acc[1][e], p[2][e] + acc[2][e], p[3][e] + acc[3][e],
+                                                     cs[ub][e]);
+            c2[e] = o.c; yv[e] = o.h;
+            p[0][e] = o.i; p[1][e] = o.f; p[2][e] = o.g; p[3][e] = o.o;
           }
           blk_store(a.cnew + base * H, 32 * ub, hb, ok, c2);
 #pragma unroll
@@ -153,10 +149,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_kernel(SeqArgs a) {
           float q[3][16];
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const float rr = sigm(p[0][e] + acc[0][e]), z = sigm(p[1][e] + acc[1][e]);
-            const float n = tanh_(p[2][e] + rr * acc[2][e]);
-            yv[e] = (1.0f - z) * n + z * h[ub][e];
-            p[0][e] = rr; p[1][e] = z; p[2][e] = n;
+            const auto o = rnn_cell::gru_fwd<Gates>(p[0][e], p[1][e], p[2][e], acc[0][e], acc[1][e], acc[2][e], h[ub][e]);
+            yv[e] = o.h;
+            p[0][e] = o.r; p[1][e] = o.z; p[2][e] = o.n;
             q[0][e] = acc[0][e]; q[1][e] = acc[1][e]; q[2][e] = acc[2][e];
           }
 #pragma unroll
@@ -212,14 +207,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_kernel(SeqArgs a) {
           for (int e = 0; e < 16; ++e) {
             float dh = dyv[e], dc = 0.f;
             if (keep) { dh += ch[ub][e]; dc = cc[ub][e]; }
-            const float gi = g[0][e], gf = g[1][e], gc = g[2][e], go = g[3][e];
-            const float tc = tanh_(cn[e]);
-            dc += dh * go * (1.0f - tc * tc);
-            g[0][e] = dc * gc * gi * (1.0f - gi);
-            g[1][e] = dc * ci[e] * gf * (1.0f - gf);
-            g[2][e] = dc * gi * (1.0f - gc * gc);
-            g[3][e] = dh * tc * go * (1.0f - go);
-            cc[ub][e] = dc * gf;
+            const auto b = rnn_cell::lstm_bwd<Gates>(dh, dc, g[0][e], g[1][e], g[2][e], g[3][e], ci[e], cn[e]);
+            g[0][e] = b.d_i; g[1][e] = b.d_f; g[2][e] = b.d_g; g[3][e] = b.d_o;
+            cc[ub][e] = b.dc_in;
           }
 #pragma unroll
           for (int gg = 0; gg < 4; ++gg) {
@@ -236,15 +226,10 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_kernel(SeqArgs a) {
           for (int e = 0; e < 16; ++e) {
             float dh = dyv[e];
             if (keep) dh += ch[ub][e];
-            const float rr = g[0][e], z = g[1][e], n = g[2][e];
-            const float dn = dh * (1.0f - z);
-            const float dz = dh * (hi[e] - n);
-            const float dpn = dn * (1.0f - n * n);
-            const float dpr = dpn * qn[e] * rr * (1.0f - rr);
-            const float dpz = dz * z * (1.0f - z);
-            g[0][e] = dpr; g[1][e] = dpz; g[2][e] = dpn;
-            q[0][e] = dpr; q[1][e] = dpz; q[2][e] = dpn * rr;
-            direct[ub][e] = dh * z;
+            const auto b = rnn_cell::gru_bwd(dh, g[0][e], g[1][e], g[2][e], qn[e], hi[e]);
+            g[0][e] = b.d_r; g[1][e] = b.d_z; g[2][e] = b.d_n;
+            q[0][e] = b.d_r; q[1][e] = b.d_z; q[2][e] = b.d_gh_n;
+            direct[ub][e] = b.direct;
           }
 #pragma unroll
           for (int gg = 0; gg < 3; ++gg) {

@@ -10,19 +10,20 @@
 // four values are contiguous in every [N, H] buffer.  The reduction over k is split between the wavefronts in blocks of 16
 // (block c goes to wavefront c % 4; within a block lane group q = l >> 4 takes k = 16 c + 4 q + j in MFMA j, for both operands,
 // so each lane loads 16 bytes of a row at a time); the four partial sums meet in LDS in a fixed order, the first wavefront(s)
-// add b_hh, apply the cell exactly as csrc/gru.hip does (libm expf / tanhf) and write y, the masked next state and the saved
+// add b_hh, apply the cell csrc/gru.hip applies (csrc/rnn_cell.h, libm gates) and write y, the masked next state and the saved
 // gates -- gi / pre and gh come out as the two-launch path leaves them, so the per-step backward runs unchanged.
 //
 // No workgroup reads what another writes in the same launch (hin_t / cin_t are read-only here and must not alias hin_next /
 // cin_next; gi, gh, pre are read and written only at the workgroup's own units and columns); there is no grid-wide barrier,
 // no cooperative launch and no flag in memory; every store is an ordinary vector store.
+#include "rnn_cell.h"
 #include "srl_common.h"
 
 namespace {
 
 using f4 = __attribute__((ext_vector_type(4))) float;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+using rnn_cell::LibmGates;
 __device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
 __device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
 
@@ -117,10 +118,8 @@ __global__ __launch_bounds__(256) void rnn_step_kernel(StepArgs a) {
     f4 r, z, nn, h;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      r[e] = sigmoidf_(ir[e] + s[0][e]);
-      z[e] = sigmoidf_(iz[e] + s[1][e]);
-      nn[e] = tanhf(in[e] + r[e] * s[2][e]);
-      h[e] = (1.0f - z[e]) * nn[e] + z[e] * hp[e];
+      const auto o = rnn_cell::gru_fwd<LibmGates>(ir[e], iz[e], in[e], s[0][e], s[1][e], s[2][e], hp[e]);
+      r[e] = o.r, z[e] = o.z, nn[e] = o.n, h[e] = o.h;
     }
     st4(gi, r), st4(gi + H, z), st4(gi + 2 * H, nn);       // saved for the backward pass
     st4(gh, s[0]), st4(gh + H, s[1]), st4(gh + 2 * H, s[2]);
@@ -133,12 +132,8 @@ __global__ __launch_bounds__(256) void rnn_step_kernel(StepArgs a) {
     f4 gi, gf, gg, go, c2, h;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      gi[e] = sigmoidf_(pi[e] + s[0][e]);
-      gf[e] = sigmoidf_(pf[e] + s[1][e]);
-      gg[e] = tanhf(pg[e] + s[2][e]);
-      go[e] = sigmoidf_(po[e] + s[3][e]);
-      c2[e] = gf[e] * cp[e] + gi[e] * gg[e];
-      h[e] = go[e] * tanhf(c2[e]);
+      const auto o = rnn_cell::lstm_fwd<LibmGates>(pi[e] + s[0][e], pf[e] + s[1][e], pg[e] + s[2][e], po[e] + s[3][e], cp[e]);
+      gi[e] = o.i, gf[e] = o.f, gg[e] = o.g, go[e] = o.o, c2[e] = o.c, h[e] = o.h;
     }
     st4(p, gi), st4(p + H, gf), st4(p + 2 * H, gg), st4(p + 3 * H, go);
     st4(a.y + n * H + u, h);

@@ -14,6 +14,7 @@ import torch
 from oracle import gae as ogae
 from oracle import ppo as oppo
 from srl_amd import hip
+from srl_amd.algorithm.rnnpath import CELLS, bufs_of
 from srl_amd.runtime import synthetic
 
 pytestmark = pytest.mark.gpu
@@ -1332,51 +1333,18 @@ def test_rnn_time_loop_in_one_launch_matches_the_per_step_path(kind, H, N, C):
         hip.gru_mask_state(c0.data_ptr(), rp(0), N, H, cin.data_ptr())
         return pre, gh, hin, cin, torch.zeros(C, N, H, device=DEV), torch.zeros(C, N, H, device=DEV)
 
-    def step_path():
+    def run(path):   # the product's time loop (rnnpath), the path named
         pre, gh, hin, cin, y, cnew = buffers()
-        for c in range(C):
-            nxt = c + 1 < C
-            if kind == "lstm":
-                hip.gemm(N, 4 * H, H, hin[c].data_ptr(), H, 0, w_hh.data_ptr(), H, 0, pre[c].data_ptr(), 4 * H, bias=b_hh.data_ptr(), accumulate=True)
-                hip.lstm_cell_fwd(pre[c].data_ptr(), cin[c].data_ptr(), rp(c + 1) if nxt else None, N, H, y[c].data_ptr(), cnew[c].data_ptr(),
-                                  hin[c + 1].data_ptr() if nxt else None, cin[c + 1].data_ptr() if nxt else None)
-            else:
-                hip.gemm(N, 3 * H, H, hin[c].data_ptr(), H, 0, w_hh.data_ptr(), H, 0, gh[c].data_ptr(), 3 * H, bias=b_hh.data_ptr())
-                hip.gru_cell_fwd(pre[c].data_ptr(), gh[c].data_ptr(), hin[c].data_ptr(), rp(c + 1) if nxt else None, N, H, y[c].data_ptr(),
-                                 hin[c + 1].data_ptr() if nxt else None)
+        k = CELLS[kind]
+        s = bufs_of(kind, gi=pre, gh=gh, hin=hin, cin=cin, cnew=cnew, y=y)
+        k.fwd(s, w_hh.data_ptr(), b_hh.data_ptr(), rp, N, H, C, path=path)
         fwd = [t.clone() for t in (pre, gh, hin, cin, y, cnew)]
-        dh = [torch.zeros(N, H, device=DEV) for _ in range(2)]
-        dc = [torch.zeros(N, H, device=DEV) for _ in range(2)]
-        ch = cc = None
-        for c in range(C - 1, -1, -1):
-            nxt = c + 1 < C
-            if kind == "lstm":
-                hip.lstm_cell_bwd(dy[c].data_ptr(), ch, cc, rp(c + 1) if nxt else None, pre[c].data_ptr(), cin[c].data_ptr(), cnew[c].data_ptr(),
-                                  N, H, dc[c & 1].data_ptr())
-                hip.gemm(N, H, 4 * H, pre[c].data_ptr(), 4 * H, 0, w_hh.data_ptr(), H, 1, dh[c & 1].data_ptr(), H)
-                ch, cc = dh[c & 1].data_ptr(), dc[c & 1].data_ptr()
-            else:
-                hip.gru_cell_bwd(dy[c].data_ptr(), ch, rp(c + 1) if nxt else None, pre[c].data_ptr(), gh[c].data_ptr(), hin[c].data_ptr(), N, H,
-                                 dh[c & 1].data_ptr())
-                hip.gemm(N, H, 3 * H, gh[c].data_ptr(), 3 * H, 0, w_hh.data_ptr(), H, 1, dh[c & 1].data_ptr(), H, accumulate=True)
-                ch = dh[c & 1].data_ptr()
-        return fwd, [pre.clone(), gh.clone()]
-
-    def seq_path():
-        pre, gh, hin, cin, y, cnew = buffers()
-        if kind == "lstm":
-            hip.lstm_seq_fwd(pre.data_ptr(), w_hh.data_ptr(), b_hh.data_ptr(), hin.data_ptr(), cin.data_ptr(), rp(0), N, H, C, y.data_ptr(), cnew.data_ptr())
-        else:
-            hip.gru_seq_fwd(pre.data_ptr(), gh.data_ptr(), w_hh.data_ptr(), b_hh.data_ptr(), hin.data_ptr(), rp(0), N, H, C, y.data_ptr())
-        fwd = [t.clone() for t in (pre, gh, hin, cin, y, cnew)]
-        if kind == "lstm":
-            hip.lstm_seq_bwd(dy.data_ptr(), H, pre.data_ptr(), w_hh.data_ptr(), cin.data_ptr(), cnew.data_ptr(), rp(0), N, H, C)
-        else:
-            hip.gru_seq_bwd(dy.data_ptr(), H, pre.data_ptr(), gh.data_ptr(), w_hh.data_ptr(), hin.data_ptr(), rp(0), N, H, C)
+        carry = [torch.zeros(N, H, device=DEV) for _ in range(4)]   # d h_in, d c_in: two alternating sets
+        k.bwd(s, dy.data_ptr(), H, w_hh.data_ptr(), rp, N, H, C, lambda c: [t.data_ptr() for t in carry[2 * (c & 1):][:len(k.state)]], path=path)
         return fwd, [pre.clone(), gh.clone()]
 
     assert hip.rnn_seq_supported(kind, H) and not hip.rnn_seq_supported(kind, 48)
-    (f1, b1), (f2, b2) = step_path(), seq_path()
+    (f1, b1), (f2, b2) = run("cell"), run("seq")
     names = ("gates", "gh", "hin", "cin", "y", "cnew")
     for name, u, v in zip(names, f1, f2):
         if kind == "gru" and name in ("cin", "cnew"):

@@ -1,7 +1,7 @@
 """The recurrent kernels, entry point by entry point, against a float64 restatement of the auto-reset LSTM / GRU (tests/rnn_ref.py).
 
-Two paths carry a chunk of C steps over N rows, and both are driven here the way `rnnpath.forward / backward` drives them, on the
-same buffers (`pre` / `gi` = W_ih x + b_ih, `hin[0]` / `cin[0]` masked by srl_gru_mask_state, `reset[c]` for c in [0, C)):
+Two paths carry a chunk of C steps over N rows, and both are driven here by the time loop `rnnpath.forward / backward` runs
+(`rnnpath.CELLS[kind].fwd / .bwd`, the path named), on the same buffers (`pre` / `gi` = W_ih x + b_ih, `hin[0]` / `cin[0]` masked by srl_gru_mask_state, `reset[c]` for c in [0, C)):
   seq   srl_{lstm,gru}_seq_{fwd,bwd} (csrc/rnn_seq.hip): the whole time loop in one launch, H in {32, 64}, gates on the hardware's
         exp2 / rcp (SRL_RNN_FASTMATH);
   step  srl_gemm (W_hh h) + srl_{lstm,gru}_cell_{fwd,bwd} (csrc/gru.hip) per step: every other width, and H in {32, 64} with
@@ -28,6 +28,7 @@ import torch
 
 from rnn_ref import FAULTS, check_vs_float64, chunk
 from srl_amd import hip
+from srl_amd.algorithm.rnnpath import CELLS, bufs_of
 
 pytestmark = pytest.mark.gpu
 
@@ -112,8 +113,8 @@ def references(kind, inputs):
 
 
 def run_kernels(kind, path, inputs):
-    """The buffers `HipNet` hands the kernels, the forward and backward of one chunk, and what the kernels leave in them.  Output
-    buffers start as NaN: an element a kernel fails to write shows."""
+    """The buffers `HipNet` hands the kernels, its forward and backward time loop of one chunk, and what the kernels leave in them.
+    Output buffers start as NaN: an element a kernel fails to write shows."""
     pre_x, w_hh, b_hh, h0, c0, reset, dy = inputs
     C, N, GH = pre_x.shape
     H = w_hh.shape[1]
@@ -131,41 +132,13 @@ def run_kernels(kind, path, inputs):
         hip.gru_mask_state(c0d.data_ptr(), rp(0), N, H, cin.data_ptr())
     seq = hip.rnn_seq_supported(kind, H)
     assert seq == (path == "seq")
-    if seq and kind == "lstm":
-        hip.lstm_seq_fwd(pre.data_ptr(), w.data_ptr(), b.data_ptr(), hin.data_ptr(), cin.data_ptr(), rp(0), N, H, C, y.data_ptr(),
-                         cnew.data_ptr())
-    elif seq:
-        hip.gru_seq_fwd(pre.data_ptr(), gh.data_ptr(), w.data_ptr(), b.data_ptr(), hin.data_ptr(), rp(0), N, H, C, y.data_ptr())
-    for c in range(0 if seq else C):
-        nxt = c + 1 < C
-        if kind == "lstm":
-            hip.gemm(N, 4 * H, H, P(hin, c), H, 0, w.data_ptr(), H, 0, P(pre, c), 4 * H, bias=b.data_ptr(), accumulate=True)
-            hip.lstm_cell_fwd(P(pre, c), P(cin, c), rp(c + 1) if nxt else None, N, H, P(y, c), P(cnew, c),
-                              P(hin, c + 1) if nxt else None, P(cin, c + 1) if nxt else None)
-        else:
-            hip.gemm(N, 3 * H, H, P(hin, c), H, 0, w.data_ptr(), H, 0, P(gh, c), 3 * H, bias=b.data_ptr())
-            hip.gru_cell_fwd(P(pre, c), P(gh, c), P(hin, c), rp(c + 1) if nxt else None, N, H, P(y, c),
-                             P(hin, c + 1) if nxt else None)
+    k, named = CELLS[kind], "seq" if seq else "cell"   # "cell": csrc/gru.hip's cells at H = 128 too (the fused step: test_gpu_rnn_step.py)
+    s = bufs_of(kind, gi=pre, gh=gh, hin=hin, cin=cin, cnew=cnew, y=y)
+    k.fwd(s, w.data_ptr(), b.data_ptr(), rp, N, H, C, path=named)
     out = dict(gates=pre.clone(), hin=hin.clone(), y=y.clone())
     out.update(dict(cin=cin.clone(), cnew=cnew.clone()) if kind == "lstm" else dict(gh=gh.clone()))
-    d_hin, d_cin = nan(C, N, H), nan(C, N, H)
-    if seq and kind == "lstm":
-        hip.lstm_seq_bwd(dyd.data_ptr(), ld, pre.data_ptr(), w.data_ptr(), cin.data_ptr(), cnew.data_ptr(), rp(0), N, H, C)
-    elif seq:
-        hip.gru_seq_bwd(dyd.data_ptr(), ld, pre.data_ptr(), gh.data_ptr(), w.data_ptr(), hin.data_ptr(), rp(0), N, H, C)
-    else:
-        assert ld == H, "the cells read dy in rows of H"
-    ch = cc = None
-    for c in range(-1 if seq else C - 1, -1, -1):
-        nxt = c + 1 < C
-        if kind == "lstm":
-            hip.lstm_cell_bwd(P(dyd, c), ch, cc, rp(c + 1) if nxt else None, P(pre, c), P(cin, c), P(cnew, c), N, H, P(d_cin, c))
-            hip.gemm(N, H, 4 * H, P(pre, c), 4 * H, 0, w.data_ptr(), H, 1, P(d_hin, c), H)
-            ch, cc = P(d_hin, c), P(d_cin, c)
-        else:
-            hip.gru_cell_bwd(P(dyd, c), ch, rp(c + 1) if nxt else None, P(pre, c), P(gh, c), P(hin, c), N, H, P(d_hin, c))
-            hip.gemm(N, H, 3 * H, P(gh, c), 3 * H, 0, w.data_ptr(), H, 1, P(d_hin, c), H, accumulate=True)
-            ch = P(d_hin, c)
+    d_hin, d_cin = nan(C, N, H), nan(C, N, H)   # one carry per step, so that every step's is compared
+    k.bwd(s, dyd.data_ptr(), ld, w.data_ptr(), rp, N, H, C, lambda c: (P(d_hin, c), P(d_cin, c))[:len(k.state)], path=named)
     out["d_pre"] = pre
     if kind == "gru":
         out["d_gh"] = gh

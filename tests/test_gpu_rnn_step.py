@@ -1,5 +1,5 @@
 """The fused recurrent step (csrc/rnn_step.hip: W_hh h + b_hh and the cell in one launch, H a multiple of 16 from 128 up) against the
-float64 restatement of the auto-reset LSTM / GRU (tests/rnn_ref.py::chunk), driven as ``rnnpath`` drives it: the fused forward step
+float64 restatement of the auto-reset LSTM / GRU (tests/rnn_ref.py::chunk), driven by ``rnnpath``'s own time loop: the fused forward step
 by step, then the EXISTING per-step backward (srl_{gru,lstm}_cell_bwd + srl_gemm) on what the forward saved.
 
 Every buffer the kernels write is compared element by element: the activated gates, GRU's gh, hin[1:], cin[1:], y, cnew; d pre /
@@ -13,6 +13,7 @@ import torch
 
 from rnn_ref import chunk, check_vs_float64
 from srl_amd import hip
+from srl_amd.algorithm.rnnpath import CELLS, bufs_of
 
 DEV = "cuda:0"
 A_F32, B_ABS = 4.0, 1e-7   # tests/test_gpu_rnn.py BOUNDS["step"]
@@ -58,39 +59,17 @@ def run_kernels(kind, inputs, fused=True):
     if kind == "lstm":
         hip.gru_mask_state(c0d.data_ptr(), rp(0), N, H, cin.data_ptr())
     assert hip.rnn_step_supported(kind, H) and not hip.rnn_seq_supported(kind, H)
-    for c in range(C):
-        nxt = c + 1 < C
-        if kind == "lstm" and fused:
-            hip.lstm_step_fwd(P(pre, c), w.data_ptr(), b.data_ptr(), P(hin, c), P(cin, c), rp(c + 1) if nxt else None, N, H, P(y, c),
-                              P(cnew, c), P(hin, c + 1) if nxt else None, P(cin, c + 1) if nxt else None)
-        elif kind == "lstm":
-            hip.gemm(N, 4 * H, H, P(hin, c), H, 0, w.data_ptr(), H, 0, P(pre, c), 4 * H, bias=b.data_ptr(), accumulate=True)
-            hip.lstm_cell_fwd(P(pre, c), P(cin, c), rp(c + 1) if nxt else None, N, H, P(y, c), P(cnew, c),
-                              P(hin, c + 1) if nxt else None, P(cin, c + 1) if nxt else None)
-        elif fused:
-            hip.gru_step_fwd(P(pre, c), P(gh, c), w.data_ptr(), b.data_ptr(), P(hin, c), rp(c + 1) if nxt else None, N, H, P(y, c),
-                             P(hin, c + 1) if nxt else None)
-        else:
-            hip.gemm(N, 3 * H, H, P(hin, c), H, 0, w.data_ptr(), H, 0, P(gh, c), 3 * H, bias=b.data_ptr())
-            hip.gru_cell_fwd(P(pre, c), P(gh, c), P(hin, c), rp(c + 1) if nxt else None, N, H, P(y, c), P(hin, c + 1) if nxt else None)
+    k, named = CELLS[kind], "fused" if fused else "cell"
+    s = bufs_of(kind, gi=pre, gh=gh, hin=hin, cin=cin, cnew=cnew, y=y)
+    k.fwd(s, w.data_ptr(), b.data_ptr(), rp, N, H, C, path=named)
     out = dict(gates=pre.clone(), hin=hin.clone(), y=y.clone())
     out.update(dict(cin=cin.clone(), cnew=cnew.clone()) if kind == "lstm" else dict(gh=gh.clone()))
     if ld != H:   # the per-step cells read d y in rows of H: a view into a wider buffer is made dense first
         dense = nan(C, N, H)
         hip.copy2d(dyd.data_ptr(), ld, dense.data_ptr(), H, C * N, H)
         dyd = dense
-    d_hin, d_cin = nan(C, N, H), nan(C, N, H)
-    ch = cc = None
-    for c in range(C - 1, -1, -1):
-        nxt = c + 1 < C
-        if kind == "lstm":
-            hip.lstm_cell_bwd(P(dyd, c), ch, cc, rp(c + 1) if nxt else None, P(pre, c), P(cin, c), P(cnew, c), N, H, P(d_cin, c))
-            hip.gemm(N, H, 4 * H, P(pre, c), 4 * H, 0, w.data_ptr(), H, 1, P(d_hin, c), H)
-            ch, cc = P(d_hin, c), P(d_cin, c)
-        else:
-            hip.gru_cell_bwd(P(dyd, c), ch, rp(c + 1) if nxt else None, P(pre, c), P(gh, c), P(hin, c), N, H, P(d_hin, c))
-            hip.gemm(N, H, 3 * H, P(gh, c), 3 * H, 0, w.data_ptr(), H, 1, P(d_hin, c), H, accumulate=True)
-            ch = P(d_hin, c)
+    d_hin, d_cin = nan(C, N, H), nan(C, N, H)   # one carry per step, so that every step's is compared
+    k.bwd(s, dyd.data_ptr(), H, w.data_ptr(), rp, N, H, C, lambda c: (P(d_hin, c), P(d_cin, c))[:len(k.state)], path=named)
     out["d_pre"], out["d_hin"] = pre, d_hin
     out.update(dict(d_cin=d_cin) if kind == "lstm" else dict(d_gh=gh))
     torch.cuda.synchronize()
