@@ -7,7 +7,8 @@ constructor keywords and defaults, the same ``state_dict`` names (``net.conv1.we
 The online and the target network are two executors over two parameter sets of one ``NetSpec``
 (``netspec.build_atari_dqn_netspec``); the convolution trunk runs once per pass per network, both towers' first Linear being one
 product.  ``analyze`` does not gather: it returns both networks' head outputs for every row, and the trainer's TD kernel
-(``csrc/dqn.hip``) forms Q, the greedy action and the gathers itself.  ``rollout`` samples with ``srl_epsilon_greedy_sample``.
+(``csrc/dqn.hip``) forms Q, the greedy action and the gathers itself.  ``rollout`` samples with ``srl_epsilon_greedy_sample``
+(``csrc/dqn.hip`` too; its Philox draw is ``csrc/action_dist.h``'s, the one the action heads' samplers use).
 
 With ``num_rnn_layers > 0`` the agent is the recurrent one (R2D2): an auto-reset GRU / LSTM between the trunk and the towers
 (``algorithm/rnnpath.py``), chunks of ``chunk_len`` steps starting from the stored ``policy_state.hx``, and -- with

@@ -4,28 +4,10 @@
 // sampler), one thread per batch column walking time for the n-step return; float64 registers where the reference computes in
 // float64, float32 roundings where it rounds.  (Both passes of the TD step in the column walk took 390 us at 64 x 44 rows of 18
 // actions -- one wavefront reading 38 floats per row, 44 rows in sequence; the row pass now runs 2816 threads wide.)
-#include "srl_common.h"
+// The value loss and the sampler's Philox draw are action_dist.h's.
+#include "action_dist.h"
 
 namespace {
-
-// nn.MSELoss / nn.HuberLoss(delta) / nn.SmoothL1Loss(beta = delta), reduction='none' (modules/utils.py:242-265): l and dl/dq
-__device__ __forceinline__ void vloss(int kind, float delta, float q, float y, float& l, float& dl) {
-  const float d = q - y;
-  if (kind == 0) {
-    l = d * d;
-    dl = 2.0f * d;
-    return;
-  }
-  const float a = fabsf(d);
-  const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  if (kind == 1) {
-    if (a <= delta) { l = 0.5f * d * d; dl = d; }
-    else { l = delta * (a - 0.5f * delta); dl = delta * sgn; }
-  } else {
-    if (a < delta) { l = 0.5f * d * d / delta; dl = d / delta; }
-    else { l = a - 0.5f * delta; dl = sgn; }
-  }
-}
 
 __device__ __forceinline__ double sign_of(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); }
 
@@ -182,20 +164,6 @@ __global__ __launch_bounds__(kTdThreads) void dqn_td_kernel(TdArgs p) {
   }
 }
 
-// ---- Philox4x32-10 (Salmon et al. 2011), as in ppo_loss.hip --------------------------------------
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-    const uint32_t hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += W0;
-    key.y += W1;
-  }
-  return ctr;
-}
-
 __global__ __launch_bounds__(256) void epsilon_greedy_kernel(const float* adv, long ld_adv, const float* v, const float* tadv,
                                                              long ld_tadv, const float* tv, const float* epsilon,
                                                              const uint8_t* is_eval, long n, int A, int double_q, uint64_t seed,
@@ -212,10 +180,8 @@ __global__ __launch_bounds__(256) void epsilon_greedy_kernel(const float* adv, l
   q_argmax(tr, tvi, tmean, A, tqmax);
   int pick = greedy;
   if (!(is_eval && is_eval[i])) {
-    const uint64_t ctr_row = (uint64_t)(row0 + i);
-    const uint4 rnd = philox4x32_10(make_uint4((uint32_t)ctr_row, (uint32_t)(ctr_row >> 32), 0u, (uint32_t)offset),
-                                    make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-    const float u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
+    const uint4 rnd = philox_draw((uint64_t)(row0 + i), 0u, offset, seed);  // the row's number in the caller's whole batch
+    const float u = u24(rnd.x);
     // floor((x1 >> 8) 2^-24 A) in integers: never A
     if (!(u > epsilon[i])) pick = (int)(((uint64_t)(rnd.y >> 8) * (uint64_t)A) >> 24);
   }

@@ -3,11 +3,10 @@
 //   log_prob(x) = -(x - mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi),   entropy = 1/2 + log sqrt(2 pi) + log sigma
 // summed over the action dimensions; log sigma is either one vector shared by all rows (`fixed`,
 // `separate_learnable`: ld_ls = 0) or one row per sample from a second head (`shared_learnable`: ld_ls = its pitch).
-#include "srl_common.h"
+// The per-dimension log-probability and entropy are action_dist.h's, as is the Philox draw of the sampler.
+#include "action_dist.h"
 
 namespace {
-
-constexpr float kHalfLog2Pi = 0.91893853320467274178f;  // log sqrt(2 pi)
 
 __global__ __launch_bounds__(256) void gaussian_fwd_kernel(const float* mean, int ld_mean, const float* log_std,
                                                            int ld_ls, const float* action, long n, int A, float* logp,
@@ -19,8 +18,8 @@ __global__ __launch_bounds__(256) void gaussian_fwd_kernel(const float* mean, in
     const float ls = log_std[i * ld_ls + j];
     const float sd = expf(ls);
     const float d = action[i * A + j] - mean[i * ld_mean + j];
-    lp += -(d * d) / (2.f * sd * sd) - logf(sd) - kHalfLog2Pi;  // torch/distributions/normal.py log_prob
-    en += 0.5f + kHalfLog2Pi + logf(sd);                          // ... entropy
+    lp += normal_log_prob(d, sd);
+    en += normal_entropy(sd);
   }
   logp[i] = lp;
   ent[i] = en;
@@ -42,20 +41,7 @@ __global__ __launch_bounds__(256) void gaussian_bwd_kernel(const float* mean, in
   }
 }
 
-// Box-Muller on Philox4x32-10 counters (defined in ppo_loss.hip's translation unit as well; duplicated here as static)
-__device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
-__device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = mulhi32(0xD2511F53u, c.x);
-    const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = mulhi32(0xCD9E8D57u, c.z);
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-
+// Box-Muller on one Philox draw per (row, action dimension)
 __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float* mean, int ld_mean, const float* log_std,
                                                               int ld_ls, const uint8_t* is_eval, long n, int A,
                                                               uint64_t seed, uint64_t offset, float* action,
@@ -70,15 +56,14 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float* mean,
     const float sd = expf(log_std[i * ld_ls + j]);
     float x = mu;  // evaluation: the mean (actor_critic_policy.py:504)
     if (!greedy) {
-      const uint4 rnd = philox(make_uint4((uint32_t)ctr_row, (uint32_t)(ctr_row >> 32), (uint32_t)j, (uint32_t)offset),
-                               make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+      const uint4 rnd = philox_draw(ctr_row, (uint32_t)j, offset, seed);
       const float u1 = ((float)(rnd.x >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-      const float u2 = (float)(rnd.y >> 8) * (1.0f / 16777216.0f);
+      const float u2 = u24(rnd.y);
       x = mu + sd * sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
     }
     const float d = x - mu;
     action[i * A + j] = x;
-    lp += -(d * d) / (2.f * sd * sd) - logf(sd) - kHalfLog2Pi;
+    lp += normal_log_prob(d, sd);
   }
   logp[i] = lp;
 }

@@ -1,84 +1,67 @@
-// Phasic Policy Gradient, auxiliary phase (phasic_policy_gradient.py:140-153, 262-280): the action distributions a cache entry
-// keeps, and the joint loss  L = aux_value_loss + beta_clone * policy_distance + value_head_weight * value_head_loss  with its
-// gradient with respect to the network's outputs, in one pass over the rows.
+// Phasic Policy Gradient, auxiliary phase (phasic_policy_gradient.py:140-153, 262-280): the joint loss  L = aux_value_loss + beta_clone * policy_distance + value_head_weight * value_head_loss  with its
+// gradient with respect to the network's outputs, in one pass over the rows, for categorical heads (the distributions a cache entry
+// keeps are categorical.hip's srl_categorical_log_softmax rows) and for Normal heads.
 //   policy_distance  = sum over heads of  sum_rows KL(old_h || new_h) (1 - done) / sum_rows (1 - done)      (:140-144)
 //   *_value_loss     = 1/2 sum (v - target)^2 (1 - done) / sum_rows (1 - done)                               (:146-147)
 // HBM-bound row work (a few dozen floats per row): one thread per row, no matrix cores.
-#include "srl_common.h"
+#include "action_dist.h"
 
 namespace {
 
-struct Heads {
-  int n_heads;
-  int dims[SRL_MAX_HEADS];
-};
-
-constexpr float kMaskedLogit = -1e10f;  // actor_critic_policy.py:136
-
-int make_heads(int n_heads, const int32_t* dims, Heads& h, int& atot) {
-  if (n_heads < 1 || n_heads > SRL_MAX_HEADS || !dims) return -1;
-  h.n_heads = n_heads;
-  atot = 0;
-  for (int k = 0; k < n_heads; ++k) {
-    if (dims[k] < 1) return -1;
-    h.dims[k] = dims[k];
-    atot += dims[k];
-  }
-  return 0;
-}
-
-__device__ __forceinline__ float masked_logit(const float* row, const uint8_t* av, int j) {
-  return (av && av[j] == 0) ? kMaskedLogit : row[j];
-}
-
-// out[i, head segment] = masked logits - logsumexp: what torch.distributions.Categorical(logits=...) keeps as `.logits`
-__global__ __launch_bounds__(256) void categorical_log_softmax_kernel(const float* logits, int ld, const uint8_t* avail, long n, Heads h,
-                                                                      int atot, float* out, int ldo) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float* row = logits + i * ld;
-  const uint8_t* av = avail ? avail + i * atot : nullptr;
-  float* o = out + i * ldo;
-  int s = 0;
-  for (int k = 0; k < h.n_heads; ++k) {
-    const int d = h.dims[k];
-    float mx = -INFINITY;
-    for (int j = 0; j < d; ++j) mx = fmaxf(mx, masked_logit(row, av, s + j));
-    float se = 0.f;
-    for (int j = 0; j < d; ++j) se += expf(masked_logit(row, av, s + j) - mx);
-    const float lse = mx + logf(se);
-    for (int j = 0; j < d; ++j) o[s + j] = masked_logit(row, av, s + j) - lse;
-    s += d;
-  }
-}
-
-struct AuxArgs {
-  const float* logq_old;  // [n, atot] normalised log-probabilities of the distributions kept by the cache entry
-  const float* logits;    // [n, atot] raw logits of the current policy
-  const uint8_t* avail;   // [n, atot] or null
+// What both kinds of head share: the two value terms, the row weights and the three sums
+struct AuxCommon {
   const float* aux;       // [n, vd]
   const float* pred;      // [n, vd]
   const float* target;    // [n, vd]
   const uint8_t* done;    // [n] (the cache entry's info_mask, :264)
   const double* count;    // sum over rows of (1 - done)
   long n;
-  int ld_old, ld, vd, atot;
+  int vd;
   float beta_clone, value_head_weight;
-  float* d_logits;        // [n, atot] (pitch ldd)
-  int ldd;
   float* d_aux;           // [n, vd]
   float* d_pred;          // [n, vd]
   double* terms;          // [3]: auxiliary value loss, value head loss, policy distance (each already divided by count)
+};
+
+// The value terms of row i (weight w = und / count, und = 1 - done): d_aux, d_pred and the row's share of acc[0], acc[1]
+__device__ __forceinline__ void aux_value_terms(const AuxCommon& c, long i, float und, float w, double (&acc)[3]) {
+  for (int ch = 0; ch < c.vd; ++ch) {
+    const long e = i * c.vd + ch;
+    const float da = c.aux[e] - c.target[e], dp = c.pred[e] - c.target[e];
+    c.d_aux[e] = da * w;
+    c.d_pred[e] = c.value_head_weight * dp * w;
+    acc[0] += 0.5 * (double)(da * da * und);
+    acc[1] += 0.5 * (double)(dp * dp * und);
+  }
+}
+
+// The workgroup's three sums, divided by the count, into terms (`red`: 4 * 3 doubles of LDS)
+__device__ __forceinline__ void aux_reduce(const AuxCommon& c, double cnt, double (&acc)[3], double* red) {
+  block_sum<3, 256>(acc, red);
+  if (threadIdx.x == 0 && cnt > 0.0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) atomicAdd(&c.terms[i], acc[i] / cnt);
+  }
+}
+
+struct AuxArgs {
+  AuxCommon c;
+  const float* logq_old;  // [n, atot] normalised log-probabilities of the distributions kept by the cache entry
+  const float* logits;    // [n, atot] raw logits of the current policy
+  const uint8_t* avail;   // [n, atot] or null
+  int ld_old, ld, atot;
+  float* d_logits;        // [n, atot] (pitch ldd)
+  int ldd;
   Heads h;
 };
 
 __global__ __launch_bounds__(256) void ppg_aux_loss_kernel(AuxArgs a) {
   __shared__ double red[4 * 3];
   double acc[3] = {0.0, 0.0, 0.0};
-  const double cnt = *a.count;
+  const double cnt = *a.c.count;
   const float inv = cnt > 0.0 ? (float)(1.0 / cnt) : 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
-    const float und = 1.f - (float)a.done[i];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.c.n; i += (long)gridDim.x * 256) {
+    const float und = 1.f - (float)a.c.done[i];
     const float w = und * inv;
     const float* row = a.logits + i * a.ld;
     const float* old = a.logq_old + i * a.ld_old;
@@ -88,11 +71,7 @@ __global__ __launch_bounds__(256) void ppg_aux_loss_kernel(AuxArgs a) {
     float kl = 0.f;
     for (int k = 0; k < a.h.n_heads; ++k) {
       const int d = a.h.dims[k];
-      float mx = -INFINITY;
-      for (int j = 0; j < d; ++j) mx = fmaxf(mx, masked_logit(row, av, s + j));
-      float se = 0.f;
-      for (int j = 0; j < d; ++j) se += expf(masked_logit(row, av, s + j) - mx);
-      const float lse = mx + logf(se);
+      const float lse = head_norm(row, av, s, d).lse;
       for (int j = 0; j < d; ++j) {
         const float lq = masked_logit(row, av, s + j) - lse, lp = old[s + j];
         const float p = expf(lp), q = expf(lq);
@@ -102,46 +81,26 @@ __global__ __launch_bounds__(256) void ppg_aux_loss_kernel(AuxArgs a) {
         if (p == 0.f) t = 0.f;
         kl += t;
         // d KL / d z_j = q_j - p_j (sum p = 1); logits overwritten with the mask constant receive no gradient (:135-136)
-        drow[s + j] = (av && av[s + j] == 0) ? 0.f : a.beta_clone * w * (q - p);
+        drow[s + j] = (av && av[s + j] == 0) ? 0.f : a.c.beta_clone * w * (q - p);
       }
       s += d;
     }
     acc[2] += (double)(kl * und);
-    for (int c = 0; c < a.vd; ++c) {
-      const long e = i * a.vd + c;
-      const float da = a.aux[e] - a.target[e], dp = a.pred[e] - a.target[e];
-      a.d_aux[e] = da * w;
-      a.d_pred[e] = a.value_head_weight * dp * w;
-      acc[0] += 0.5 * (double)(da * da * und);
-      acc[1] += 0.5 * (double)(dp * dp * und);
-    }
+    aux_value_terms(a.c, i, und, w, acc);
   }
-  block_sum<3, 256>(acc, red);
-  if (threadIdx.x == 0 && cnt > 0.0) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) atomicAdd(&a.terms[i], acc[i] / cnt);
-  }
+  aux_reduce(a.c, cnt, acc, red);
 }
 
 struct GaussAuxArgs {
+  AuxCommon c;
   const float* mean_old;     // [n, A] (pitch ld_old): the means kept by the cache entry
   const float* log_std_old;  // [A] (pitch 0) or [n, A] rows (pitch ld_ls_old): log sigma kept by the cache entry
   const float* mean;         // [n, A] (pitch ld): the current policy's means
   const float* log_std;      // [A] (pitch 0) or [n, A] rows (pitch ld_ls): the current policy's log sigma
-  const float* aux;          // [n, vd]
-  const float* pred;         // [n, vd]
-  const float* target;       // [n, vd]
-  const uint8_t* done;       // [n]
-  const double* count;       // sum over rows of (1 - done)
-  long n;
-  int ld_old, ld_ls_old, ld, ld_ls, vd, A;
-  float beta_clone, value_head_weight;
+  int ld_old, ld_ls_old, ld, ld_ls, A;
   float* d_mean;             // [n, A] (pitch ldd)
   int ldd;
   float* d_log_std;          // [n, A] or null (`fixed`: log sigma takes no gradient)
-  float* d_aux;              // [n, vd]
-  float* d_pred;             // [n, vd]
-  double* terms;             // [3], as in AuxArgs
 };
 
 // Normal heads: KL(N(m0, s0) || N(m1, s1)) per action dimension as torch.distributions.kl._kl_normal_normal,
@@ -150,12 +109,12 @@ struct GaussAuxArgs {
 __global__ __launch_bounds__(256) void ppg_aux_loss_gaussian_kernel(GaussAuxArgs a) {
   __shared__ double red[4 * 3];
   double acc[3] = {0.0, 0.0, 0.0};
-  const double cnt = *a.count;
+  const double cnt = *a.c.count;
   const float inv = cnt > 0.0 ? (float)(1.0 / cnt) : 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
-    const float und = 1.f - (float)a.done[i];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.c.n; i += (long)gridDim.x * 256) {
+    const float und = 1.f - (float)a.c.done[i];
     const float w = und * inv;
-    const float gw = a.beta_clone * w;
+    const float gw = a.c.beta_clone * w;
     const float* m0 = a.mean_old + i * a.ld_old;
     const float* l0 = a.log_std_old + i * a.ld_ls_old;
     const float* m1 = a.mean + i * a.ld;
@@ -174,36 +133,12 @@ __global__ __launch_bounds__(256) void ppg_aux_loss_gaussian_kernel(GaussAuxArgs
       if (dl) dl[j] = gw * (1.f - r - t);   // d KL / d ls1
     }
     acc[2] += (double)(kl * und);
-    for (int c = 0; c < a.vd; ++c) {
-      const long e = i * a.vd + c;
-      const float da = a.aux[e] - a.target[e], dp = a.pred[e] - a.target[e];
-      a.d_aux[e] = da * w;
-      a.d_pred[e] = a.value_head_weight * dp * w;
-      acc[0] += 0.5 * (double)(da * da * und);
-      acc[1] += 0.5 * (double)(dp * dp * und);
-    }
+    aux_value_terms(a.c, i, und, w, acc);
   }
-  block_sum<3, 256>(acc, red);
-  if (threadIdx.x == 0 && cnt > 0.0) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) atomicAdd(&a.terms[i], acc[i] / cnt);
-  }
+  aux_reduce(a.c, cnt, acc, red);
 }
 
 }  // namespace
-
-extern "C" int srl_categorical_log_softmax(void* stream, const float* logits, int ld_logits, const uint8_t* avail, long n, int n_heads,
-                                           const int32_t* host_head_dims, float* out, int ld_out) {
-  Heads h;
-  int atot;
-  SRL_CHECK_ARG(make_heads(n_heads, host_head_dims, h, atot) == 0, "bad head dims");
-  SRL_CHECK_ARG(logits && out && ld_logits >= atot && ld_out >= atot && n >= 0, "null tensor / ld");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(categorical_log_softmax_kernel, dim3((unsigned)srl_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, logits,
-                     ld_logits, avail, n, h, atot, out, ld_out);
-  SRL_LAUNCH_CHECK();
-  return 0;
-}
 
 extern "C" int srl_ppg_aux_loss_fwd_bwd(void* stream, const float* logq_old, int ld_old, const float* logits, int ld_logits,
                                         const uint8_t* avail, long n, int n_heads, const int32_t* host_head_dims, const float* aux_value,
@@ -218,9 +153,9 @@ extern "C" int srl_ppg_aux_loss_fwd_bwd(void* stream, const float* logq_old, int
   hipStream_t st = (hipStream_t)stream;
   SRL_HIP_TRY(hipMemsetAsync(terms, 0, 3 * sizeof(double), st));
   if (n == 0) return 0;
-  a.logq_old = logq_old; a.logits = logits; a.avail = avail; a.aux = aux_value; a.pred = pred_value; a.target = target; a.done = done;
-  a.count = undone_count; a.n = n; a.ld_old = ld_old; a.ld = ld_logits; a.vd = value_dim; a.beta_clone = beta_clone;
-  a.value_head_weight = value_head_weight; a.d_logits = d_logits; a.ldd = ld_dlogits; a.d_aux = d_aux; a.d_pred = d_pred; a.terms = terms;
+  a.c = AuxCommon{aux_value, pred_value, target, done, undone_count, n, value_dim, beta_clone, value_head_weight, d_aux, d_pred, terms};
+  a.logq_old = logq_old; a.logits = logits; a.avail = avail; a.ld_old = ld_old; a.ld = ld_logits; a.d_logits = d_logits;
+  a.ldd = ld_dlogits;
   const unsigned grid = (unsigned)(srl_ceil_div(n, 256) < 2048 ? srl_ceil_div(n, 256) : 2048);
   hipLaunchKernelGGL(ppg_aux_loss_kernel, dim3(grid), dim3(256), 0, st, a);
   SRL_LAUNCH_CHECK();
@@ -244,10 +179,10 @@ extern "C" int srl_ppg_aux_loss_gaussian_fwd_bwd(void* stream, const float* mean
                     d_aux && d_pred,
                 "null tensor");
   GaussAuxArgs a{};
-  a.mean_old = mean_old; a.log_std_old = log_std_old; a.mean = mean; a.log_std = log_std; a.aux = aux_value; a.pred = pred_value;
-  a.target = target; a.done = done; a.count = undone_count; a.n = n; a.ld_old = ld_mean_old; a.ld_ls_old = ld_log_std_old;
-  a.ld = ld_mean; a.ld_ls = ld_log_std; a.vd = value_dim; a.A = A; a.beta_clone = beta_clone; a.value_head_weight = value_head_weight;
-  a.d_mean = d_mean; a.ldd = ld_dmean; a.d_log_std = d_log_std; a.d_aux = d_aux; a.d_pred = d_pred; a.terms = terms;
+  a.c = AuxCommon{aux_value, pred_value, target, done, undone_count, n, value_dim, beta_clone, value_head_weight, d_aux, d_pred, terms};
+  a.mean_old = mean_old; a.log_std_old = log_std_old; a.mean = mean; a.log_std = log_std; a.ld_old = ld_mean_old;
+  a.ld_ls_old = ld_log_std_old; a.ld = ld_mean; a.ld_ls = ld_log_std; a.A = A; a.d_mean = d_mean; a.ldd = ld_dmean;
+  a.d_log_std = d_log_std;
   // at most 512 workgroups (the categorical kernel's limit is 2048): every workgroup ends with three float64 atomics into the one
   // 24-byte `terms`, and those -- not the rows' bytes -- set the time of a large call (524 288 rows x 6: 90 us per call with 2048
   // workgroups, 60 with 1024, 40 with 512, 38 with 256, 53 with 128; measured)

@@ -1,6 +1,7 @@
 """Plain restatements of the discrete-action heads, their Philox sampler, the PPO loss and the masked normalisation, on the CPU
-(torch with autograd / numpy), buffer by buffer as the HIP kernels see them (csrc/ppo_loss.hip, csrc/gae.hip: `srl_categorical_fwd /
-_bwd / _sample`, `srl_ppo_loss_fwd_bwd`, `srl_masked_stats / _normalize`).  No GPU and no project code.
+(torch with autograd / numpy), buffer by buffer as the HIP kernels see them (csrc/categorical.hip: `srl_categorical_fwd / _bwd /
+_sample`; csrc/ppo_loss.hip: `srl_ppo_loss_fwd_bwd`; csrc/gae.hip: `srl_masked_stats / _normalize`; the head normalisation, the
+Philox draw and the value loss are stated once on the device, in csrc/action_dist.h).  No GPU and no project code.
 
 Run in float64 they are the reference the kernels are held to (tests/test_gpu_loss_kernels.py); run in float32 they measure how far
 an honest float32 evaluation of the same arithmetic lands from float64, which sets the tolerance.  tests/test_loss_reference.py
@@ -58,7 +59,8 @@ def categorical(logits, action, avail, dims, d_logp=None, d_ent=None, dtype=torc
               float32, the arithmetic of the reference project and of the kernels: every masked logit is -1e10, where float32 is
               spaced 1024 apart, so logsumexp = fl(-1e10 + log d) = -1e10, every normalised logit is -1e10 - (-1e10) = 0 exactly,
               the log-prob is 0 and the entropy -sum p 0 = 0.  float32 torch.distributions.Categorical gives these zeros
-              (tests/test_loss_reference.py asserts it) and csrc/ppo_loss.hip computes lse = mx + logf(se) the same way, so a dead
+              (tests/test_loss_reference.py asserts it) and csrc/action_dist.h's head_norm, the one normalisation every categorical
+              kernel calls, computes lse = mx + logf(se) the same way, so a dead
               head's share is pinned to exactly 0 and logp / ent are held to the live heads' sum at the live heads' scale.
       scales  logp, ent [n], d_logits [n, sum(dims)]: the error scales (module docstring) of the live heads (0 where every head is
               dead); d_logits has scale 0, and must be exactly 0, at unavailable actions and in dead heads.  With z the masked

@@ -1,4 +1,5 @@
-"""The deep Q-learning kernels (csrc/dqn.hip) against the float64 restatements of tests/dqn_ref.py.
+"""The deep Q-learning kernels (csrc/dqn.hip; the value loss and the sampler's Philox draw are csrc/action_dist.h's, shared with
+the PPO loss and the action heads) against the float64 restatements of tests/dqn_ref.py.
 
 TD step: every element of d_adv, d_v, the priorities and the statistics obeys the project's rule (dqn_cases.assert_within: three times
 the float32 reference's own error plus 2e-6 of the tensor's largest element), in every case of dqn_cases.TD_CASES and every variant

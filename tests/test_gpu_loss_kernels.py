@@ -1,5 +1,6 @@
 """The discrete-action heads, their Philox sampler, the PPO loss and the masked normalisation -- the kernels every update of every
-discrete-action configuration passes through (csrc/ppo_loss.hip, csrc/gae.hip) -- each called through the raw C entry points, so
+discrete-action configuration passes through (csrc/categorical.hip, csrc/ppo_loss.hip, csrc/gae.hip; the head arithmetic, the
+Philox draw and the value loss they share: csrc/action_dist.h) -- each called through the raw C entry points, so
 that pitches can differ from widths, and compared with the float64 restatements of tests/loss_ref.py at the sizes where such
 kernels go wrong: one row, one row past a workgroup, past the grid caps (512 workgroups of the loss, 2048 of the normalisation),
 SRL_MAX_HEADS heads, a head of one action, heads with one or no available action, column windows of wider matrices.  Outputs are
@@ -167,6 +168,50 @@ def test_categorical_sample_follows_the_host_sampler(case):
         tail_a, tail_l = _sample_device(c, "window", seed, 5, row0=R.TAIL, start=R.TAIL)
         assert np.array_equal(tail_a, act[R.TAIL:]), "a batch streamed in pieces samples what it would in one call"
         assert np.array_equal(tail_l.view(np.uint32), lp[R.TAIL:].view(np.uint32))
+
+
+SHARED_WALK_CASES = [(257, (2, 3, 1, 5, 2, 4, 3, 2), "dead", 2.0),  # a row past a workgroup, SRL_MAX_HEADS heads, dead and single-action heads
+                     (257, (18,), "random", 8.0)]                   # probabilities underflow
+
+
+@pytest.mark.parametrize("case", SHARED_WALK_CASES, ids=_case_id)
+def test_entry_points_share_one_head_walk(case):
+    """The categorical entry points normalise a head by one definition (csrc/action_dist.h), seen from outside, in the "window"
+    layout, bitwise on the float32 patterns: (a) the rows of srl_categorical_log_softmax, gathered at the case's actions and added
+    over the heads in float32 in head order from 0, are srl_categorical_fwd's log-probability; (b) the log-probability
+    srl_categorical_sample returns is srl_categorical_fwd's log-probability of the actions it returned."""
+    c = R.cat_case(*case)
+    n, dims = c["n"], c["dims"]
+    A, H = sum(dims), len(dims)
+    keep, lg_ptr, ld = _logits_on_device(c, "window")
+    avail = dev(c["avail"])
+    st, hd, L = hip._stream(), hip._i32_array(dims), hip.lib()
+
+    def fwd_logp(action):
+        act = dev(action, torch.int32)
+        logp, ent = torch.full((n,), NAN, device=DEV), torch.full((n,), NAN, device=DEV)
+        hip._check(L.srl_categorical_fwd(st, lg_ptr, ld, act.data_ptr(), avail.data_ptr(), n, H, hd, logp.data_ptr(), ent.data_ptr()),
+                   "srl_categorical_fwd")
+        return logp.cpu().numpy()
+
+    wide = torch.full((n, A + GRAD_PAD), NAN, device=DEV)
+    hip._check(L.srl_categorical_log_softmax(st, lg_ptr, ld, avail.data_ptr(), n, H, hd, wide.data_ptr() + 4 * GRAD_OFF, A + GRAD_PAD),
+               "srl_categorical_log_softmax")
+    rows = wide.cpu().numpy()[:, GRAD_OFF:GRAD_OFF + A]
+    assert rows.dtype == np.float32 and np.isfinite(rows).all()
+    gathered = np.zeros(n, np.float32)
+    for k, s, d in R._heads(dims):
+        gathered = gathered + rows[np.arange(n), s + c["action"][:, k]]  # float32 + float32, rounded once like the kernel's
+    assert gathered.dtype == np.float32
+    logp = fwd_logp(c["action"])
+    diff = np.abs(gathered.astype(np.float64) - logp)
+    print(f"\n(a) log-softmax rows gathered against fwd: max difference {diff.max():.3e}")
+    assert np.array_equal(gathered.view(np.uint32), logp.view(np.uint32)), ("a", float(diff.max()))
+    act, lp = _sample_device(c, "window", R.SAMPLE_SEED, 5)
+    again = fwd_logp(act)
+    diff = np.abs(lp.astype(np.float64) - again)
+    print(f"(b) the sampler's log-probability against fwd at its picks: max difference {diff.max():.3e}")
+    assert np.array_equal(lp.view(np.uint32), again.view(np.uint32)), ("b", float(diff.max()))
 
 
 def test_categorical_argument_errors():
