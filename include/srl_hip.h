@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SRL_HIP_ABI_VERSION 22
+#define SRL_HIP_ABI_VERSION 23
 
 int srl_abi_version(void);
 const char* srl_last_error(void);
@@ -507,13 +507,8 @@ int srl_obs_ln_stats(void* stream, const void* obs, int is_u8, int64_t n, int D,
 int srl_im2col_obs_ln(void* stream, const void* obs, int is_u8, const float* mean, const float* rstd,
                       const float* gamma, const float* beta, int64_t n, int C, int H, int W, int KH, int KW,
                       int stride, float* P);
-/* im2col for later convolutions on NHWC float32 activations: P [n*OH*OW, KH*KW*C], k = (kh, kw, c). */
-int srl_im2col_nhwc(void* stream, const float* x, int64_t n, int H, int W, int C, int KH, int KW, int stride,
-                    float* P);
-/* Gather form of col2im: dX[n,h,w,c] = sum of the dP entries that patch (h,w,c) went to;
- * optionally * act'(y) with y = forward activation of the same shape as dX (dact 1 relu, 2 tanh). */
-int srl_col2im_nhwc(void* stream, const float* dP, int64_t n, int H, int W, int C, int KH, int KW, int stride,
-                    const float* y, int dact, float* dX);
+/* (Later convolutions of the explicit path take the patch matrix of their channels-last activation from srl_im2col_ndhwc /
+ * srl_col2im_ndhwc with D = 1, below.) */
 /* Backward of srl_im2col_obs_ln w.r.t. the LayerNorm affine parameters:
  * dgamma[c,h,w] += sum_n dXn * xhat, dbeta[c,h,w] += sum_n dXn, dXn = col2im(dP) (never materialised). */
 int srl_obs_ln_affine_bwd(void* stream, const float* dP, const void* obs, int is_u8, const float* mean,
@@ -870,28 +865,28 @@ int srl_adam_step(void* stream, float* p, const float* g, float* m, float* v, in
 /* `Convolution` encoder pieces beyond unpadded convolutions (legacy/algorithm/modules/cnn.py:99-118; policies/utils.py:53):
  * srl_obs_ln_nhwc(_bwd): the whole-observation LayerNorm as an explicit pass, planar uint8 / float32 observation
  *   [n,C,H,W] -> channels-last float32 [n,H,W,C] (gamma / beta [C,H,W]); backward accumulates dgamma, dbeta from
- *   dy [n,H,W,C].  srl_pad_nhwc / srl_crop_nhwc: zero padding of an NHWC activation and its adjoint (nn.Conv2d(padding=p,
- *   padding_mode='zeros')).  srl_maxpool2_nhwc_fwd / _bwd: MaxPool2d(2) (`use_maxpool`: in front of every layer but the
- *   last); the backward routes to the first maximum of a window (torch's rule) and multiplies by act'(x) of the
- *   activation that produced x (dact 0 none, 1 relu, 2 tanh). */
+ *   dy [n,H,W,C]. */
 int srl_obs_ln_nhwc(void* stream, const void* obs, int is_u8, const float* mean, const float* rstd, const float* gamma,
                     const float* beta, int64_t n, int C, int H, int W, float* y);
 int srl_obs_ln_nhwc_bwd(void* stream, const float* dy, const void* obs, int is_u8, const float* mean, const float* rstd,
                         int64_t n, int C, int H, int W, float* dgamma, float* dbeta);
-int srl_pad_nhwc(void* stream, const float* x, int64_t n, int H, int W, int C, int pad, float* y);
-int srl_crop_nhwc(void* stream, const float* yp, int64_t n, int H, int W, int C, int pad, float* x);
-int srl_maxpool2_nhwc_fwd(void* stream, const float* x, int64_t n, int H, int W, int C, float* y);
-int srl_maxpool2_nhwc_bwd(void* stream, const float* dy, const float* x, int64_t n, int H, int W, int C, int dact, float* dx);
 
-/* The same encoder pieces for observations with one or three spatial dimensions (modules/cnn.py:60-71: nn.Conv1d /
- * nn.Conv3d with MaxPool1d / MaxPool3d by the observation's rank; modules_test.py:385-401), on channels-last volumes
- * [n, D, H, W, C] (Conv1d: D = H = 1).  srl_pad_ndhwc: border of (pd, ph, pw <= 8) voxels per side filled per
- * nn.ConvNd's `padding_mode` (mode 0 zeros, 1 reflect, 2 replicate, 3 circular; torch's preconditions: reflect pad <
- * extent, circular pad <= extent); srl_crop_ndhwc: its adjoint (mode 0: the crop; else every interior voxel also collects
- * the border voxels that were filled from it).  srl_maxpool_ndhwc_fwd / _bwd: windows of (wd, wh, ww) voxels, each 1 or 2, stride = window, floor; the
- * backward as srl_maxpool2_nhwc_bwd.  srl_im2col_ndhwc: patch matrix P[(s,od,oh,ow)][(kd,kh,kw,c)] for a dense GEMM
- * against weights laid out [Cout][KD][KH][KW][Cin]; srl_col2im_ndhwc: its adjoint (sums the taps that reach a voxel,
- * optionally times act'(y), y = the forward activation of that voxel, dact as above). */
+/* The other encoder pieces, for observations of every rank (modules/cnn.py:60-71: nn.Conv1d / Conv2d / Conv3d with the
+ * matching MaxPool by the observation's rank; modules_test.py:385-401), on channels-last float32 volumes [n, D, H, W, C]:
+ * an NHWC image is D = 1, a sequence D = H = 1 (until ABI 22 the image had entry points of its own, srl_*_nhwc).
+ * srl_pad_ndhwc: border of (pd, ph, pw <= 8) voxels per side filled per nn.ConvNd's `padding_mode` (mode 0 zeros --
+ * nn.Conv2d(padding=p, padding_mode='zeros') is pads (0, p, p) -- 1 reflect, 2 replicate, 3 circular; torch's
+ * preconditions: reflect pad < extent, circular pad <= extent); srl_crop_ndhwc: its adjoint (mode 0: the crop; else every
+ * interior voxel also collects the border voxels that were filled from it).
+ * srl_maxpool_ndhwc_fwd / _bwd: windows of (wd, wh, ww) voxels, each 1 or 2, stride = window, floor (MaxPool2d(2),
+ * `use_maxpool`: in front of every layer but the last, is the window (1, 2, 2)).  The maximum starts from the window's
+ * first voxel: a window that is NaN throughout gives NaN.  The backward routes to the first maximum of a window in
+ * (d, h, w) scan order (torch's rule) and multiplies by act'(x) of the activation that produced x (dact 0 none, 1 relu,
+ * 2 tanh); voxels no window covers get 0.
+ * srl_im2col_ndhwc: patch matrix P[(s,od,oh,ow)][(kd,kh,kw,c)] ([n*OD*OH*OW, KD*KH*KW*C]) for a dense GEMM against
+ * weights laid out [Cout][KD][KH][KW][Cin]; srl_col2im_ndhwc: the gather form of its adjoint (dX[s,d,h,w,c] = sum of
+ * the dP entries the voxel went to, taps in ascending (kd, kh, kw) order, optionally times act'(y), y = the forward
+ * activation of that voxel, dact as above).  Both move float4s along c when C is a multiple of 4. */
 int srl_pad_ndhwc(void* stream, const float* x, int64_t n, int D, int H, int W, int C, int pd, int ph, int pw, int mode,
                   float* y);
 int srl_crop_ndhwc(void* stream, const float* yp, int64_t n, int D, int H, int W, int C, int pd, int ph, int pw, int mode,

@@ -11,7 +11,7 @@ Linear (+act)     ``srl_gemm`` X W^T + b, act in epilogue    ``srl_gemm`` dZ^T X
 LayerNorm         ``srl_layernorm_fwd``                      ``srl_layernorm_bwd`` (act' of the producer fused)
 first Conv2d      ``srl_obs_ln_stats`` + ``srl_im2col_obs_ln``  GEMMs + ``srl_obs_ln_affine_bwd``
                   (uint8 -> LN -> patches) + ``srl_gemm``
-later Conv2d      ``srl_im2col_nhwc`` + ``srl_gemm``             GEMMs + ``srl_col2im_nhwc`` (act' fused)
+later Conv2d      ``srl_im2col_ndhwc`` (D = 1) + ``srl_gemm``   GEMMs + ``srl_col2im_ndhwc`` (act' fused)
 entity attention  ``srl_entity_attn_fwd`` (several leaves)   ``srl_entity_attn_bwd`` (walks forward again, no tape)
 instruction LSTM  ``srl_instr_lstm_fwd`` (token ids)         ``srl_instr_lstm_bwd`` (walks forward again, no tape)
 ================  =========================================  ==========================================
@@ -78,7 +78,12 @@ class ConvSaved(NamedTuple):
 
 LnHeadsSaved = NamedTuple("LnHeadsSaved", [("mean", torch.Tensor), ("rstd", torch.Tensor), ("heads", list)])
 ObsLnSaved = NamedTuple("ObsLnSaved", [("is_u8", bool), ("mean", torch.Tensor), ("rstd", torch.Tensor), ("n", int)])
-ConvNdSaved = NamedTuple("ConvNdSaved", [("P", Buf), ("n", int), ("sp", tuple)])   # sp: the (padded) input volume
+def _padded_vol(L) -> tuple:
+    """(D, H, W, C) of a convolution's input with its border (ConvSpec: D = 1)."""
+    return (*(d + 2 * p for d, p in zip(L.in_vol, L.pads)), L.cin)
+
+
+ConvNdSaved = NamedTuple("ConvNdSaved", [("P", Buf), ("n", int), ("vol", tuple)])   # vol: the (padded) input volume (D, H, W, C)
 
 
 class FusedChain(NamedTuple):
@@ -985,49 +990,29 @@ class HipNet:
     @_fwd(ns.PoolSpec, emits=("pool",))
     def _fwd_pool(self, st, L):
         cur, n = st.cur, st.n
-        (h, w), (ph, pw) = L.in_hw, L.out_hw
-        assert cur.ld == L.c and cur.rows == n * h * w
-        y = self._buf(f"{st.tag}{L.prefix}.y", n * ph * pw, L.c)
-        hip.maxpool2_nhwc_fwd(cur.ptr, n, h, w, L.c, y.ptr)
-        st.tape.append(Rec("pool", L, cur, n, st.cur_act, L.c))
-        st.advance(y)  # the activation's derivative is applied by the pooling backward at the winner
-
-    @_fwd(ns.PoolNdSpec, emits=("poolnd",))
-    def _fwd_poolnd(self, st, L):
-        cur, n = st.cur, st.n
         assert cur.ld == L.c and cur.rows == n * math.prod(L.in_sp)
         y = self._buf(f"{st.tag}{L.prefix}.y", n * math.prod(L.out_sp), L.c)
         hip.maxpool_ndhwc_fwd(cur.ptr, n, (*L.in_sp, L.c), L.win, y.ptr)
-        st.tape.append(Rec("poolnd", L, cur, n, st.cur_act, L.c))
-        st.advance(y)
+        st.tape.append(Rec("pool", L, cur, n, st.cur_act, L.c))
+        st.advance(y)  # the activation's derivative is applied by the pooling backward at the winner
 
     @_fwd(ns.ConvNdSpec, emits=("convnd",))
     def _fwd_convnd(self, st, L):
-        cur, n, tag = st.cur, st.n, st.tag
-        sp = L.in_sp
-        assert cur.ld == L.cin and cur.rows == n * math.prod(sp)
-        if any(L.pads):
-            sp = tuple(d + 2 * p for d, p in zip(sp, L.pads))
-            xp = self._buf(f"{tag}{L.prefix}.xp", n * math.prod(sp), L.cin)
-            hip.pad_ndhwc(cur.ptr, n, (*L.in_sp, L.cin), L.pads, xp.ptr, L.pad_mode)
-            cur = xp
+        n, tag = st.n, st.tag
+        x, vol = self._pad(tag, L, st.cur, n)
         m, kdim = n * math.prod(L.out_sp), L.cin * math.prod(L.kern)
         P = self._buf(f"{tag}{L.prefix}.P", m, kdim)
-        hip.im2col_ndhwc(cur.ptr, n, (*sp, L.cin), L.kern, L.stride, P.ptr)
         y = self._buf(f"{tag}{L.prefix}.y", m, L.cout)
-        hip.gemm(m, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
-                 bias=self._p(f"{L.prefix}.bias"), act=L.act)
-        st.tape.append(Rec("convnd", L, cur, ConvNdSaved(P, n, sp), st.cur_act, L.cout))
+        self._patch_conv_fwd(L, x, P, y, n, vol)
+        st.tape.append(Rec("convnd", L, x, ConvNdSaved(P, n, vol), st.cur_act, L.cout))
         st.advance(y, L.act)
 
     @_fwd(ns.ConvSpec, emits=("conv", "h2cnn"))
     def _fwd_conv(self, st, L):
         n, tag = st.n, st.tag
         m, kdim = n * L.out_hw[0] * L.out_hw[1], L.cin * L.k * L.k
-        h, w = L.in_hw
-        x = st.cur
-        if L.pad:  # zero-padded copy: the implicit-GEMM gather needs no bounds logic
-            x, h, w = self._conv_pad_fwd(st, L)
+        # (a padded copy: the implicit-GEMM gather needs no bounds logic)
+        x, (_, h, w, _) = self._pad(tag, L, st.cur, n)
         desc = hip.conv_desc(n, h, w, L.cin, L.k, L.k, L.stride, L.cout, L.act)
         # implicit GEMM (no patch matrix) whenever the geometry allows; explicit im2col otherwise
         implicit = not self.force_explicit_conv and hip.conv2d_supported(desc, L.first)
@@ -1053,23 +1038,70 @@ class HipNet:
             assert x.ld == L.cin and x.rows == n * h * w
             if implicit:
                 y_range = self._conv_later_fwd(st, L, desc, x, y, kdim)
-        if not implicit:
-            self._conv_explicit_fwd(L, first, x, y, P, n, h, w, kdim)
+        if not implicit:  # the fallback
+            self._patch_conv_fwd(L, x, P, y, n, (1, h, w, L.cin), first)
         st.tape.append(Rec("conv", L, x, ConvSaved(P, first, n, desc, st.cur_range), st.cur_act, L.cout))
         st.advance(y, L.act, y_range)
 
-    def _conv_pad_fwd(self, st, L):
-        """The padded copy of `st.cur` and its extent."""
-        cur, n = st.cur, st.n
-        h, w = L.in_hw
-        assert not L.first and cur.ld == L.cin and cur.rows == n * h * w
-        h, w = h + 2 * L.pad, w + 2 * L.pad
-        xp = self._buf(f"{st.tag}{L.prefix}.xp", n * h * w, L.cin)
-        if L.pad_mode:  # reflect / replicate / circular borders: the general kernel (D = 1)
-            hip.pad_ndhwc(cur.ptr, n, (1, L.in_hw[0], L.in_hw[1], L.cin), (0, L.pad, L.pad), xp.ptr, L.pad_mode)
+    # One pad / crop pair and one patch-matrix convolution for ConvSpec (an image: the volume with D = 1) and ConvNdSpec.
+    def _pad(self, tag, L, cur, n):
+        """The layer's input with its border (`L.pads` voxels per side, filled per `L.pad_mode`) and that volume
+        (D, H, W, C); `cur` itself where the layer has no padding."""
+        vol = L.in_vol
+        if not any(L.pads):
+            return cur, vol
+        assert cur.ld == L.cin and cur.rows == n * math.prod(vol[:3])
+        pvol = _padded_vol(L)
+        xp = self._buf(f"{tag}{L.prefix}.xp", n * math.prod(pvol[:3]), L.cin)
+        hip.pad_ndhwc(cur.ptr, n, vol, L.pads, xp.ptr, L.pad_mode)
+        return xp, pvol
+
+    def _crop(self, tag, L, dx: Buf, n) -> Buf:
+        """The adjoint of `_pad`: the gradient of the layer's input from that of its padded copy (zero padding: drop the border)."""
+        if not any(L.pads):
+            return dx
+        vol = L.in_vol
+        out = self._buf(f"{tag}{L.prefix}.dxc", n * math.prod(vol[:3]), L.cin)
+        hip.crop_ndhwc(dx.ptr, n, vol, L.pads, out.ptr, L.pad_mode)
+        return out
+
+    def _patch_conv_fwd(self, L, x, P: Buf, y: Buf, n, vol, first=None):
+        """A convolution as patch matrix + dense GEMM (bias and activation in its epilogue): the patches of the channels-last
+        volume `x` of extent `vol` (padded), or, for the layer that reads the observation (`first`), of the layer-normed
+        planar observation."""
+        kdim = P.cols
+        if first is not None:
+            ln = first.lnspec
+            hip.im2col_obs_ln(first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(),
+                              self._p(f"{ln.prefix}.weight"), self._p(f"{ln.prefix}.bias"), n, ln.shape[0], vol[1], vol[2],
+                              L.k, L.k, L.stride, P.ptr)
         else:
-            hip.pad_nhwc(cur.ptr, n, L.in_hw[0], L.in_hw[1], L.cin, L.pad, xp.ptr)
-        return xp, h, w
+            assert x.ld == L.cin and x.rows == n * math.prod(vol[:3])
+            hip.im2col_ndhwc(x.ptr, n, vol, L.kern, L.stride, P.ptr)
+        hip.gemm(P.rows, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
+                 bias=self._p(f"{L.prefix}.bias"), act=L.act)
+
+    def _patch_conv_bwd(self, rec, g, tag, P: Buf, n, vol, need_dx, first=None) -> Optional[Buf]:
+        """Backward of `_patch_conv_fwd`: weight and bias gradients, then the gradient of the (padded) input volume `vol` with the
+        derivative of the activation that produced it, cropped to the layer's input; the first layer ends in the observation
+        LayerNorm's gradients instead."""
+        L, x, in_act = rec.layer, rec.x, rec.in_act
+        m, kdim = g.rows, P.cols
+        self._wgrad(L.cout, kdim, m, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
+        hip.colsum(g.ptr, g.ld, m, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
+        if not (need_dx or first is not None):  # the chain's first record on a written-out observation: nobody takes dx
+            return None
+        # dP = dZ W, written over the patch matrix (its last reader was the weight gradient above)
+        hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)
+        if first is not None:
+            ln = first.lnspec
+            c, h, w = ln.shape
+            hip.obs_ln_affine_bwd(P.ptr, first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(), n, c, h, w,
+                                  L.k, L.k, L.stride, self._g(f"{ln.prefix}.weight"), self._g(f"{ln.prefix}.bias"))
+            return None
+        dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(vol[:3]), L.cin)
+        hip.col2im_ndhwc(P.ptr, n, vol, L.kern, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
+        return self._crop(tag, L, dx, n)
 
     def _conv_first_source(self, st, L, desc, implicit, h, w) -> "FirstConv":
         """Where the first convolution reads the observation and its whole-image LayerNorm statistics: the ring's rows in place,
@@ -1147,18 +1179,6 @@ class HipNet:
                             presplit=pre is not None, family=fam)
         return y_range
 
-    def _conv_explicit_fwd(self, L, first, x: Buf, y: Buf, P: Buf, n, h, w, kdim):
-        """The fallback: patch matrix (of the layer-normed observation for the first layer) + dense GEMM."""
-        if first is not None:
-            ln = first.lnspec
-            hip.im2col_obs_ln(first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(),
-                              self._p(f"{ln.prefix}.weight"), self._p(f"{ln.prefix}.bias"), n, ln.shape[0], h, w,
-                              L.k, L.k, L.stride, P.ptr)
-        else:
-            hip.im2col_nhwc(x.ptr, n, h, w, L.cin, L.k, L.k, L.stride, P.ptr)
-        hip.gemm(P.rows, L.cout, kdim, P.ptr, kdim, 0, self._p(f"{L.prefix}.weight"), kdim, 0, y.ptr, y.ld,
-                 bias=self._p(f"{L.prefix}.bias"), act=L.act)
-
     # ------------------------------------------------------------------ one backward handler per record kind
     # A handler `(self, rec, g, g_range, need_dx, tag, below, dv)` takes the gradient `g` w.r.t. the record's pre-activation output
     # (`g_range`: device float bounding max |g| when its producer tracked it) and returns the gradient for the record below and
@@ -1184,7 +1204,7 @@ class HipNet:
         return g
 
     def _notify_ready(self, rec):
-        if self.grad_ready_hook is None or rec.kind in ("pool", "poolnd"):
+        if self.grad_ready_hook is None or rec.kind == "pool":
             return
         done = [rec.layer.prefix]
         if rec.kind == "conv" and rec.saved.first is not None:
@@ -1271,48 +1291,31 @@ class HipNet:
                             self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"))
         return None, None
 
-    @_bwd("poolnd")
-    def _bwd_poolnd(self, rec, g, g_range, need_dx, tag, below, dv):
+    @_bwd("pool")
+    def _bwd_pool(self, rec, g, g_range, need_dx, tag, below, dv):
         L, n = rec.layer, rec.saved
+        assert g.ld == L.c and g.rows == n * math.prod(L.out_sp)
         dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(L.in_sp), L.c)
         hip.maxpool_ndhwc_bwd(g.ptr, rec.x.ptr, n, (*L.in_sp, L.c), L.win, rec.in_act, dx.ptr)
         return dx, None
 
-    @_bwd("pool")
-    def _bwd_pool(self, rec, g, g_range, need_dx, tag, below, dv):
-        L, n = rec.layer, rec.saved
-        (h, w), (ph, pw) = L.in_hw, L.out_hw
-        assert g.ld == L.c and g.rows == n * ph * pw
-        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.c)
-        hip.maxpool2_nhwc_bwd(g.ptr, rec.x.ptr, n, h, w, L.c, rec.in_act, dx.ptr)
-        return dx, None
-
     @_bwd("convnd")
     def _bwd_convnd(self, rec, g, g_range, need_dx, tag, below, dv):
-        L, x, in_act = rec.layer, rec.x, rec.in_act
-        P, n, sp = rec.saved
-        m, kdim = g.rows, L.cin * math.prod(L.kern)
-        assert g.ld == L.cout and m == n * math.prod(L.out_sp)
-        self._wgrad(L.cout, kdim, m, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
-        hip.colsum(g.ptr, g.ld, m, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
-        hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)  # dP over P
-        dx = self._buf(f"{tag}{L.prefix}.dx", n * math.prod(sp), L.cin)
-        hip.col2im_ndhwc(P.ptr, n, (*sp, L.cin), L.kern, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
-        if any(L.pads):
-            dxc = self._buf(f"{tag}{L.prefix}.dxc", n * math.prod(L.in_sp), L.cin)
-            hip.crop_ndhwc(dx.ptr, n, (*L.in_sp, L.cin), L.pads, dxc.ptr, L.pad_mode)
-            dx = dxc
-        return dx, None
+        L = rec.layer
+        P, n, vol = rec.saved
+        assert g.ld == L.cout and g.rows == n * math.prod(L.out_sp)
+        return self._patch_conv_bwd(rec, g, tag, P, n, vol, True), None
 
     @_bwd("conv")
     def _bwd_conv(self, rec, g, g_range, need_dx, tag, below, dv):
         """Four variants, as the forward pass chose: first layer on the observation (one launch), small direct kernels, implicit
-        matrix-core kernels, explicit patch matrix.  The last three are a weight-gradient half and a data-gradient half."""
+        matrix-core kernels, explicit patch matrix (`_patch_conv_bwd`).  The middle two are a weight-gradient half and a data-gradient
+        half."""
         L, s = rec.layer, rec.saved
         assert s.P is not None or g.ld == L.cout
         if s.P is not None:
-            wgrad, dgrad = self._conv_explicit_wgrad, self._conv_explicit_dgrad
-        elif L.first:
+            return self._patch_conv_bwd(rec, g, tag, s.P, s.n, _padded_vol(L), need_dx, s.first), None
+        if L.first:
             return self._conv_first_bwd(rec, g)
         elif self._conv_small(L, s.desc):
             wgrad, dgrad = self._conv_small_wgrad, self._conv_small_dgrad
@@ -1389,43 +1392,7 @@ class HipNet:
         hip.conv2d_nhwc_dgrad(desc, g.ptr, pre or wtp, x.ptr if in_act and x_mask is None else None, in_act,
                               dx.ptr, dz_absmax=g_range if two else None, w_absmax=wr,
                               dx_absmax=dx_range, x_mask=x_mask, presplit=pre is not None, family=fam)
-        return self._crop(L, dx, n, tag), dx_range
-
-    def _conv_explicit_wgrad(self, rec, g, g_range):
-        L, P = rec.layer, rec.saved.P
-        kdim = L.cin * L.k * L.k
-        self._wgrad(L.cout, kdim, g.rows, g, P.ptr, kdim, self._g(f"{L.prefix}.weight"))
-        hip.colsum(g.ptr, g.ld, g.rows, L.cout, self._g(f"{L.prefix}.bias"), accumulate=True)
-        return g_range
-
-    def _conv_explicit_dgrad(self, rec, g, g_range, tag):
-        L, x, in_act = rec.layer, rec.x, rec.in_act
-        P, first, n = rec.saved.P, rec.saved.first, rec.saved.n
-        m, kdim = g.rows, L.cin * L.k * L.k
-        # dP = dZ W, written over the patch matrix (its last reader was the weight gradient above)
-        hip.gemm(m, kdim, L.cout, g.ptr, g.ld, 0, self._p(f"{L.prefix}.weight"), kdim, 1, P.ptr, kdim)
-        if L.first:
-            ln = first.lnspec
-            c, h, w = ln.shape
-            hip.obs_ln_affine_bwd(P.ptr, first.src.data_ptr(), first.is_u8, first.mean.data_ptr(), first.rstd.data_ptr(), n, c, h, w,
-                                  L.k, L.k, L.stride, self._g(f"{ln.prefix}.weight"), self._g(f"{ln.prefix}.bias"))
-            return None, None
-        h, w = L.in_hw[0] + 2 * L.pad, L.in_hw[1] + 2 * L.pad
-        dx = self._buf(f"{tag}{L.prefix}.dx", n * h * w, L.cin)
-        hip.col2im_nhwc(P.ptr, n, h, w, L.cin, L.k, L.k, L.stride, x.ptr if in_act else None, in_act, dx.ptr)
-        return self._crop(L, dx, n, tag), None
-
-    def _crop(self, L, dx: Buf, n: int, tag: str) -> Buf:
-        """Gradient of a zero-padded input: drop the border."""
-        if not L.pad:
-            return dx
-        h, w = L.in_hw
-        out = self._buf(f"{tag}{L.prefix}.dxc", n * h * w, L.cin)
-        if L.pad_mode:
-            hip.crop_ndhwc(dx.ptr, n, (1, h, w, L.cin), (0, L.pad, L.pad), out.ptr, L.pad_mode)
-        else:
-            hip.crop_nhwc(dx.ptr, n, h, w, L.cin, L.pad, out.ptr)
-        return out
+        return self._crop(tag, L, dx, n), dx_range
 
     def _lnheads_ok(self, encoders, backbone, heads, n) -> bool:
         """The encoder's closing LayerNorm and the heads right behind it (no backbone layers between) as one launch."""

@@ -135,14 +135,18 @@ class ConvSpec:
     pad: int = 0  # padding on every side (in_hw is the unpadded input)
     pad_mode: int = 0  # nn.Conv2d's padding_mode: 0 zeros, 1 reflect, 2 replicate, 3 circular
 
+    # the image as the D = 1 volume of the pad / crop / patch-matrix kernels (ConvNdSpec's fields of the same names)
+    @property
+    def in_vol(self):
+        return (1, *self.in_hw, self.cin)
 
-@dataclasses.dataclass
-class PoolSpec:
-    """nn.MaxPool2d(2) between convolutions (modules/cnn.py:61-62): floor(H/2) x floor(W/2) windows, no parameters."""
-    prefix: str
-    c: int
-    in_hw: Tuple[int, int]
-    out_hw: Tuple[int, int]
+    @property
+    def pads(self):
+        return (0, self.pad, self.pad)
+
+    @property
+    def kern(self):
+        return (1, self.k, self.k)
 
 
 @dataclasses.dataclass
@@ -161,10 +165,15 @@ class ConvNdSpec:
     act: int
     pad_mode: int = 0
 
+    @property
+    def in_vol(self):
+        return (*self.in_sp, self.cin)
+
 
 @dataclasses.dataclass
-class PoolNdSpec:
-    """nn.MaxPool1d(2) / nn.MaxPool3d(2) between those convolutions."""
+class PoolSpec:
+    """nn.MaxPool1d(2) / MaxPool2d(2) / MaxPool3d(2) between convolutions (modules/cnn.py:61-62): floor windows, no
+    parameters.  Volumes as in ConvNdSpec: three entries with leading 1s (an image: (1, h, w), window (1, 2, 2))."""
     prefix: str
     c: int
     in_sp: Tuple[int, int, int]
@@ -399,6 +408,38 @@ def _pad_mode(padding, padding_mode, extents) -> int:
     return PAD_MODES[padding_mode] if padding else 0
 
 
+def _default_cnn(c: int):
+    """modules/cnn.py:96-98: the stack of an encoder whose `cnn_layers` entry is missing."""
+    return [(c, 5, 1, 0, "zeros"), (c * 2, 3, 1, 0, "zeros"), (c, 3, 1, 0, "zeros")]
+
+
+def _pool_before(layers: list, prefix: str, c: int, sp: Tuple[int, int, int], nd: int) -> Tuple[int, int, int]:
+    """The pooling layer that sits BEFORE a convolution (modules/cnn.py:61-63): MaxPool{nd}d(2) over the last `nd` axes
+    of the volume `sp`; returns the pooled volume."""
+    lead = 3 - nd
+    win = (1,) * lead + (2,) * nd
+    out = tuple(d // w for d, w in zip(sp, win))
+    if min(out) <= 0:
+        raise ValueError(f"CNN Dimension error, got {out[lead:]} after max-pooling")
+    layers.append(PoolSpec(prefix, c, sp, out, win))
+    return out
+
+
+def _fc_tail(b: "_Builder", layers: list, fb: str, chw: Tuple[int, int, int], hidden: int):
+    """nn.Flatten -> (Linear, ReLU, LayerNorm)* behind the last convolution, widths halving down to 8 * hidden
+    (modules/cnn.py:86-91); `chw`: that convolution's output as the first Linear's columns see it."""
+    sizes = [int(math.prod(chw))]
+    while sizes[-1] > hidden * 8:
+        sizes.append(sizes[-1] // 2)
+    sizes.append(hidden)
+    for j in range(len(sizes) - 1):
+        first_fc = j == 0
+        b.linear(f"{fb}.{3 * j}", sizes[j], sizes[j + 1], "fc_from_chw" if first_fc else "plain", chw if first_fc else None)
+        b.layernorm(f"{fb}.{3 * j + 2}", sizes[j + 1])
+        layers.append(LinearSpec(f"{fb}.{3 * j}", sizes[j], sizes[j + 1], 1))  # utils.mlp default ReLU
+        layers.append(LayerNormSpec(f"{fb}.{3 * j + 2}", sizes[j + 1]))
+
+
 def _build_encoders(b: _Builder, root: str, dims: Dict, hidden: int, act: int, act_name: str, cnn_layers: Dict,
                     use_maxpool: Optional[Dict] = None):
     encs = []
@@ -423,8 +464,8 @@ def _build_encoders(b: _Builder, root: str, dims: Dict, hidden: int, act: int, a
         cb = f"{base}.1._Convolution__model"
         c, h, w = shape
         cfg = cnn_layers.get(key)
-        if cfg is None:  # modules/cnn.py:96-98 default stack
-            cfg = [(c, 5, 1, 0, "zeros"), (c * 2, 3, 1, 0, "zeros"), (c, 3, 1, 0, "zeros")]
+        if cfg is None:
+            cfg = _default_cnn(c)
         # a strided first convolution whose stride divides kernel and image is run on the space-to-depth'd
         # observation (contiguous patch rows); its weight and the LayerNorm tables then live in that layout
         k0, s0 = cfg[0][1], cfg[0][2]
@@ -446,12 +487,8 @@ def _build_encoders(b: _Builder, root: str, dims: Dict, hidden: int, act: int, a
         gain = torch.nn.init.calculate_gain(act_name)
         idx = 0  # position in the reference's nn.Sequential (modules/cnn.py:57-72)
         for i, (cout, k, stride, padding, padding_mode) in enumerate(cfg):
-            if pool and i != len(cfg) - 1:  # the pooling layer sits BEFORE convolution i (modules/cnn.py:61-63)
-                ph, pw = h // 2, w // 2
-                if ph <= 0 or pw <= 0:
-                    raise ValueError(f"CNN Dimension error, got {(ph, pw)} after max-pooling")
-                layers.append(PoolSpec(f"{cb}.{idx}", c, (h, w), (ph, pw)))
-                h, w = ph, pw
+            if pool and i != len(cfg) - 1:
+                _, h, w = _pool_before(layers, f"{cb}.{idx}", c, (1, h, w), 2)
                 idx += 1
             mode = _pad_mode(padding, padding_mode, (h, w))
             oh, ow = _conv_out(h + 2 * padding, k, stride), _conv_out(w + 2 * padding, k, stride)
@@ -466,18 +503,7 @@ def _build_encoders(b: _Builder, root: str, dims: Dict, hidden: int, act: int, a
             layers.append(ConvSpec(name, c, cout, k, stride, (h, w), (oh, ow), act, first=first,
                                    s2d=s2d if first else 0, pad=int(padding), pad_mode=mode))
             c, h, w = cout, oh, ow
-        sizes = [c * h * w]
-        while sizes[-1] > hidden * 8:  # modules/cnn.py:86-91
-            sizes.append(sizes[-1] // 2)
-        sizes.append(hidden)
-        fb = f"{cb}.{idx + 1}"  # nn.Flatten takes index idx
-        for j in range(len(sizes) - 1):
-            first_fc = j == 0
-            b.linear(f"{fb}.{3 * j}", sizes[j], sizes[j + 1], "fc_from_chw" if first_fc else "plain",
-                     (c, h, w) if first_fc else None)
-            b.layernorm(f"{fb}.{3 * j + 2}", sizes[j + 1])
-            layers.append(LinearSpec(f"{fb}.{3 * j}", sizes[j], sizes[j + 1], 1))  # utils.mlp default ReLU
-            layers.append(LayerNormSpec(f"{fb}.{3 * j + 2}", sizes[j + 1]))
+        _fc_tail(b, layers, f"{cb}.{idx + 1}", (c, h, w), hidden)  # nn.Flatten takes index idx
         encs.append(EncoderSpec(key, shape, layers, hidden))
     return encs
 
@@ -490,20 +516,15 @@ def _build_nd_encoder(b: _Builder, key: str, base: str, shape, hidden: int, act:
     sp = (1,) * (3 - nd) + tuple(shape[1:])
     lead = 3 - nd
     cb = f"{base}.1._Convolution__model"
-    if cfg is None:  # modules/cnn.py:96-98 default stack
-        cfg = [(c, 5, 1, 0, "zeros"), (c * 2, 3, 1, 0, "zeros"), (c, 3, 1, 0, "zeros")]
+    if cfg is None:
+        cfg = _default_cnn(c)
     b.layernorm(f"{base}.0", shape)
     layers = [ObsLayerNormSpec(f"{base}.0", (c, 1, int(math.prod(sp))), explicit=True)]
     gain = torch.nn.init.calculate_gain(act_name)
     idx = 0
     for i, (cout, k, stride, padding, padding_mode) in enumerate(cfg):
         if pool and i != len(cfg) - 1:
-            win = (1,) * lead + (2,) * nd
-            out = tuple(d // w for d, w in zip(sp, win))
-            if min(out) <= 0:
-                raise ValueError(f"CNN Dimension error, got {out[lead:]} after max-pooling")
-            layers.append(PoolNdSpec(f"{cb}.{idx}", c, sp, out, win))
-            sp = out
+            sp = _pool_before(layers, f"{cb}.{idx}", c, sp, nd)
             idx += 1
         mode = _pad_mode(padding, padding_mode, sp[lead:])
         kern = (1,) * lead + (k,) * nd
@@ -518,18 +539,7 @@ def _build_nd_encoder(b: _Builder, key: str, base: str, shape, hidden: int, act:
         b.zero(f"{name}.bias")
         layers.append(ConvNdSpec(name, c, cout, kern, stride, pads, sp, out, act, pad_mode=mode))
         c, sp = cout, out
-    vox = int(math.prod(sp))
-    sizes = [c * vox]
-    while sizes[-1] > hidden * 8:
-        sizes.append(sizes[-1] // 2)
-    sizes.append(hidden)
-    fb = f"{cb}.{idx + 1}"
-    for j in range(len(sizes) - 1):
-        first_fc = j == 0
-        b.linear(f"{fb}.{3 * j}", sizes[j], sizes[j + 1], "fc_from_chw" if first_fc else "plain", (c, 1, vox) if first_fc else None)
-        b.layernorm(f"{fb}.{3 * j + 2}", sizes[j + 1])
-        layers.append(LinearSpec(f"{fb}.{3 * j}", sizes[j], sizes[j + 1], 1))
-        layers.append(LayerNormSpec(f"{fb}.{3 * j + 2}", sizes[j + 1]))
+    _fc_tail(b, layers, f"{cb}.{idx + 1}", (c, 1, int(math.prod(sp))), hidden)
     return EncoderSpec(key, tuple(shape), layers, hidden)
 
 

@@ -590,7 +590,7 @@ def test_im2col_col2im_nhwc(H, C, k, s):
     OH = (H - k) // s + 1
     P = torch.empty((n * OH * OH, k * k * C), device=DEV)
     dx_ = dev(x)
-    hip.im2col_nhwc(dx_.data_ptr(), n, H, H, C, k, k, s, P.data_ptr())
+    hip.im2col_ndhwc(dx_.data_ptr(), n, (1, H, H, C), (1, k, k), s, P.data_ptr())
     xt = torch.from_numpy(x).permute(0, 3, 1, 2).double().requires_grad_(True)  # NCHW for unfold
     u = torch.nn.functional.unfold(xt, k, stride=s)  # [n, C*k*k, L] with (c,kh,kw) order
     u = u.reshape(n, C, k, k, OH * OH).permute(0, 4, 2, 3, 1).reshape(n * OH * OH, k * k * C)  # -> (kh,kw,c)
@@ -600,7 +600,7 @@ def test_im2col_col2im_nhwc(H, C, k, s):
     ymask = rng.standard_normal((n, H, H, C)).astype(np.float32)
     dX = torch.empty((n, H, H, C), device=DEV)
     ddP, dym = dev(dP), dev(ymask)  # keep the device copies alive across the asynchronous launch
-    hip.col2im_nhwc(ddP.data_ptr(), n, H, H, C, k, k, s, dym.data_ptr(), 1, dX.data_ptr())
+    hip.col2im_ndhwc(ddP.data_ptr(), n, (1, H, H, C), (1, k, k), s, dym.data_ptr(), 1, dX.data_ptr())
     torch.cuda.synchronize()
     ref = xt.grad.permute(0, 2, 3, 1).numpy() * (ymask > 0)
     assert rel_close(dX.cpu().numpy(), ref, 1e-5, scale=1.0)
@@ -919,6 +919,10 @@ def test_pad_crop_ndhwc(vol, pads, mode):
     dx_ = dev(x)
     hip.pad_ndhwc(dx_.data_ptr(), n, vol, pads, y.data_ptr(), hip.PAD_MODES[mode])
     assert np.array_equal(y.cpu().numpy(), yt.permute(0, 2, 3, 4, 1).detach().numpy().astype(np.float32))
+    if mode == "zeros":
+        back = torch.full((n, D, H, W, C), float("nan"), device=DEV)
+        hip.crop_ndhwc(y.data_ptr(), n, vol, pads, back.data_ptr(), hip.PAD_MODES[mode])
+        assert np.array_equal(back.cpu().numpy().view(np.uint32), x.view(np.uint32)), "crop(pad(x)) == x, bit for bit"
     dy = rng.standard_normal((n, *pv, C)).astype(np.float32)
     (yt * torch.from_numpy(dy).permute(0, 4, 1, 2, 3).double()).sum().backward()
     back = torch.full((n, D, H, W, C), float("nan"), device=DEV)
@@ -961,7 +965,7 @@ def test_maxpool_ndhwc_matches_torch(vol, win, dact):
 
 
 @pytest.mark.parametrize("vol,kern,s", [((1, 1, 40, 3), (1, 1, 5), 2), ((1, 9, 9, 4), (1, 3, 3), 1), ((6, 7, 5, 2), (2, 3, 2), 1),
-                                        ((7, 7, 7, 3), (3, 3, 3), 2)])
+                                        ((7, 7, 7, 3), (3, 3, 3), 2), ((3, 5, 4, 8), (2, 3, 2), 1)])
 def test_im2col_col2im_ndhwc(vol, kern, s):
     """The patch matrix reproduces torch's convolution of the matching rank through one GEMM, and col2im is its adjoint."""
     rng = np.random.default_rng(sum(vol) + s)

@@ -459,6 +459,7 @@ def test_accumulate_n_adds_left_to_right(k):
 
 
 # ------------------------------------------------------------------------------------------------ NHWC pad / crop / max-pool
+# (an image is the D = 1 case of the channels-last volume kernels)
 @pytest.mark.parametrize("pad", [1, 2])
 @pytest.mark.parametrize("H,W,C", [(7, 5, 1), (9, 11, 3), (5, 7, 32)])
 def test_pad_crop_nhwc(H, W, C, pad):
@@ -468,15 +469,15 @@ def test_pad_crop_nhwc(H, W, C, pad):
     ref = torch.nn.functional.pad(torch.from_numpy(x).permute(0, 3, 1, 2), (pad,) * 4).permute(0, 2, 3, 1).numpy()
     dx = dev(x)
     y = torch.full((n, H + 2 * pad, W + 2 * pad, C), float("nan"), device=DEV)
-    hip.pad_nhwc(dx.data_ptr(), n, H, W, C, pad, y.data_ptr())
+    hip.pad_ndhwc(dx.data_ptr(), n, (1, H, W, C), (0, pad, pad), y.data_ptr())
     assert np.array_equal(y.cpu().numpy(), ref)
     back = torch.full((n, H, W, C), float("nan"), device=DEV)
-    hip.crop_nhwc(y.data_ptr(), n, H, W, C, pad, back.data_ptr())
+    hip.crop_ndhwc(y.data_ptr(), n, (1, H, W, C), (0, pad, pad), back.data_ptr())
     assert np.array_equal(back.cpu().numpy(), x), "crop(pad(x)) == x"
     # crop is the adjoint of the zero padding: the interior of any padded gradient
     dy = rng.standard_normal((n, H + 2 * pad, W + 2 * pad, C)).astype(np.float32)
     ddy = dev(dy)
-    hip.crop_nhwc(ddy.data_ptr(), n, H, W, C, pad, back.data_ptr())
+    hip.crop_ndhwc(ddy.data_ptr(), n, (1, H, W, C), (0, pad, pad), back.data_ptr())
     assert np.array_equal(back.cpu().numpy(), dy[:, pad:-pad, pad:-pad])
 
 
@@ -499,7 +500,7 @@ def test_maxpool2_nhwc_matches_torch(H, W, C, dact):
     OH, OW = H // 2, W // 2
     dx = dev(x)
     y = torch.full((n, OH, OW, C), float("nan"), device=DEV)
-    hip.maxpool2_nhwc_fwd(dx.data_ptr(), n, H, W, C, y.data_ptr())
+    hip.maxpool_ndhwc_fwd(dx.data_ptr(), n, (1, H, W, C), (1, 2, 2), y.data_ptr())
     assert np.array_equal(y.cpu().numpy(), yt.detach().permute(0, 2, 3, 1).numpy())
     dy = rng.standard_normal((n, OH, OW, C)).astype(np.float32)
     dy[dy == 0] = 1.0
@@ -508,7 +509,7 @@ def test_maxpool2_nhwc_matches_torch(H, W, C, dact):
     assert (routed[0, :2 * OH:2, :2 * OW:2, 0] == dy[0, :, :, 0]).all(), "torch routes a tie to the first element"
     out = torch.full((n, H, W, C), float("nan"), device=DEV)
     ddy = dev(dy)
-    hip.maxpool2_nhwc_bwd(ddy.data_ptr(), dx.data_ptr(), n, H, W, C, dact, out.data_ptr())
+    hip.maxpool_ndhwc_bwd(ddy.data_ptr(), dx.data_ptr(), n, (1, H, W, C), (1, 2, 2), dact, out.data_ptr())
     got = out.cpu().numpy()
     if dact == 0:
         assert np.array_equal(got, routed)
