@@ -350,6 +350,48 @@ int srl_epsilon_greedy_sample(void* stream, const float* adv, int64_t ld_adv, co
 int srl_polyak_update(void* stream, float* target, const float* param, int64_t n, double tau);
 
 /* ------------------------------------------------------------------------------------------------
+ * Prioritised experience replay resident in HBM (added at ABI 23: additive, the version is unchanged).
+ *
+ * The state of the reference's PrioritizedReplayBuffer (base/buffer.py:280-465) on the device: a sum tree and a min tree, each
+ * float64[2 * capacity] with capacity a power of two, the root at index 1 and leaf i at capacity + i (base/segment_tree.py:34,75-82);
+ * empty leaves hold the neutral elements 0.0 and +inf; max_priority float32[1] and refused int32[1].  Every float64 product, sum and
+ * quotient below is rounded once (no FMA contraction), so a numpy float64 restatement is bit-exact up to the library's pow.
+ *
+ * srl_per_set: n pairs (slots[k], priorities[k]) -> both trees (SegmentTree.__setitem__, segment_tree.py:75-82, as
+ * update_priorities and put call it, buffer.py:391-393,452-458).  leaf = pow((double)priority, alpha) in both trees (alpha 1 and 0 give
+ * the priority and 1.0 exactly); every ancestor of a written leaf = its left child (+ | min) its right child, so inner nodes are
+ * the exact float64 sum / min of the device's own children.  A slot that occurs more than once takes its LAST accepted pair, as the
+ * reference's sequential loop leaves it (:452-456).  A pair is refused -- its leaf is left alone and refused[0] goes up by one, where
+ * the reference asserts (:453-454) -- when the priority is not finite or not > 0, or the slot is outside [0, n_slots).
+ * max_priority[0] = max(max_priority[0], accepted priorities) (:458); priorities may be max_priority itself (n = 1: a new sample
+ * enters with the running maximum, :352).  last: int32[capacity] of scratch, every entry -1 before the
+ * call and after it.  One launch of one workgroup; n may exceed its thread count and the capacity. */
+int srl_per_set(void* stream, double* sum_tree, double* min_tree, int64_t capacity, int64_t n_slots, const int32_t* slots,
+                const float* priorities, int64_t n, double alpha, int32_t* last, float* max_priority, int32_t* refused);
+
+/* srl_per_sample: B stratified draws and their importance weights in one launch (_sample_proportional and get, buffer.py:409-437).
+ * Draw i: one Philox4x32-10 block with the samplers' counter layout (row = i, stream word 0, offset, seed), u = (x0 >> 8) 2^-24,
+ *   mass = (u + i) * (total / B),  total = sum_tree[1]
+ * -- the ROOT, not the reference's sum(0, total_chunks - 1) (:411), whose half-open range leaves the newest filled slot out so that it
+ * is never drawn -- then find_prefixsum_idx (segment_tree.py:117-124): from the root, go left iff value[2 node] > mass, else subtract it
+ * and go right.  idx[i] = min(leaf reached, n_filled - 1): a mass that rounds up to the root would walk into an empty leaf.
+ *   weight[i] = (float)( pow(leaf / total * n_filled, -beta) / pow(min_tree[1] / total * n_filled, -beta) )          (:430-437)
+ * with leaf the sum tree's value at idx[i].  idx int32[B] comes out ascending (:417; the masses already are), weight float32[B]. */
+int srl_per_sample(void* stream, const double* sum_tree, const double* min_tree, int64_t capacity, int64_t n_filled, int64_t B,
+                   double beta, uint64_t seed, uint64_t offset, int32_t* idx, float* weight);
+
+/* srl_replay_gather: dst[t, b, :] = store[idx[b], t, :] for one leaf of the replay store [max_size, Tb, row_bytes] (the fancy index of
+ * _slicing, buffer.py:166-172,426-428, with idx read on the device); row_bytes a multiple of 4; 16-byte pieces when row_bytes and both
+ * bases allow, else 4-byte words.  An idx outside [0, max_size) leaves its rows of dst alone.  One read and one write of the batch. */
+int srl_replay_gather(void* stream, const void* store, int64_t max_size, const int32_t* idx, int64_t B, int64_t Tb, int64_t row_bytes,
+                      void* dst);
+
+/* out[k] = the float32 mean of vector k as numpy's ndarray.mean() rounds it (pairwise float32 sum, float32 quotient), widened to
+ * float64; 0.0 for a NULL or empty vector.  The statistics DeepQLearning.step logs of its priorities, sampling weights and
+ * epsilon (deep_q_learning.py:206-214), placed in the block the step reads back.  At most 2^21 elements each. */
+int srl_pairwise_means(void* stream, const float* a, int64_t na, const float* b, int64_t nb, const float* c, int64_t nc, double* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Phasic Policy Gradient, auxiliary phase (ABI 15).
  *
  * srl_categorical_log_softmax: out[i, head h] = masked logits - logsumexp over the head -- the `.logits` of the

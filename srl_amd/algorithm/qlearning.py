@@ -8,7 +8,11 @@ networks and the optimiser.  One step is
     with respect to the head outputs, priorities, statistics: csrc/dqn.hip) -> net.backward -> global-norm clip folded into the
     optimiser step (FlatOptimizer) -> soft target update every step, or a hard one by ``hard_update_interval`` -> inc_version
 
-and the host waits for the device once, at the end, for the statistics and the priorities.
+and the host waits for the device once, at the end, for the statistics and the priorities.  ``step(sample,
+device_priorities=True)`` serves a replay buffer resident in HBM (runtime/replay.py): ``TrainerStepResult.priorities`` stays a device
+tensor, ``sampling_weight`` and ``policy_state.epsilon`` may be device tensors, and the means the statistics report of the three
+(``srl_pairwise_means``: numpy's float32 mean, so both paths log the same numbers) travel in the block the step reads back anyway --
+still one wait.  (``info`` statistics of a sample whose leaves are device tensors are read back on their own.)
 
 DIFFERENCES: a sample is consumed by the call that receives it (the reference's GPU prefetcher hands ``step`` the PREVIOUS
 call's sample and returns an empty result for the first one, :91-96).  ``use_popart=True`` (the reference's ``atari-dqn`` policy has
@@ -91,7 +95,7 @@ class DeepQLearning(PytorchTrainer):
         raise NotImplementedError("q-learning: data-parallel training is not implemented")
 
     # ------------------------------------------------------------------ the step (:90-238)
-    def step(self, sample):
+    def step(self, sample, device_priorities=False):
         hip.require_gpu()
         if dist.is_initialized():
             raise NotImplementedError("q-learning: data-parallel training is not implemented (a process group is initialised)")
@@ -117,9 +121,11 @@ class DeepQLearning(PytorchTrainer):
         d_adv = ws.get("dqn.d_adv", out.adv.numel())[:out.adv.numel()].view_as(out.adv)
         d_v = ws.get("dqn.d_v", n)[:n]
         priorities = ws.get("dqn.priorities", B)[:B]
-        # one block for everything the host reads back: the TD terms, then the gradient norm (float32 in a float64 slot)
-        back = ws.get("dqn.terms", hip.DQ_COUNT + 1, torch.float64)[:hip.DQ_COUNT + 1]
-        terms, gn = back[:hip.DQ_COUNT], back[hip.DQ_COUNT:].view(torch.float32)[:1]
+        # one block for everything the host reads back: the TD terms, then the gradient norm (float32 in a float64 slot), then
+        # (device_priorities) the means of the new priorities, the sampling weights and epsilon
+        n_back = hip.DQ_COUNT + 1 + (3 if device_priorities else 0)
+        back = ws.get("dqn.terms", hip.DQ_COUNT + 4, torch.float64)[:n_back]
+        terms, gn = back[:hip.DQ_COUNT], back[hip.DQ_COUNT:hip.DQ_COUNT + 1].view(torch.float32)[:1]
         hip.dqn_td_fwd_bwd(out.adv, out.value.reshape(n), out.target_adv, out.target_value.reshape(n), out.action, reward, done,
                            truncated, weight, T, B, self._hp, d_adv, d_v, terms, priorities)
         policy.backward_dqn(d_adv, d_v)
@@ -141,20 +147,33 @@ class DeepQLearning(PytorchTrainer):
             self.hard_update_count += 1
         self.steps += 1
 
+        eps = getattr(sample.policy_state, "epsilon", None) if sample.policy_state is not None else None
+        if device_priorities:
+            on_device = lambda x: x.to(dev, torch.float32).contiguous() if isinstance(x, torch.Tensor) and x.is_cuda else None
+            hip.pairwise_means([priorities, on_device(host_weight), on_device(eps)], back[hip.DQ_COUNT + 1:])
         host = back.cpu()  # the step's first wait for the device
-        new_priorities = priorities.cpu().numpy().copy()
         t = host[:hip.DQ_COUNT].numpy()
-        grad_norm = float(host[hip.DQ_COUNT:].view(torch.float32)[0])
+        grad_norm = float(host[hip.DQ_COUNT:hip.DQ_COUNT + 1].view(torch.float32)[0])
         cnt = t[hip.DQ_MASK]
         self.total_timesteps += cnt
         mean = lambda slot: float(t[slot] / cnt) if cnt > 0 else float("nan")
-        eps = getattr(sample.policy_state, "epsilon", None) if sample.policy_state is not None else None
+        if device_priorities:
+            new_priorities = priorities.clone()  # the workspace's next step overwrites it
+            means = host[hip.DQ_COUNT + 1:].numpy()
+            of = lambda x, k: float(means[k]) if isinstance(x, torch.Tensor) and x.is_cuda else float(np.asarray(x).mean())
+            mean_priority = float(means[0])
+            mean_weight = of(host_weight, 1) if host_weight is not None else 0.0
+            mean_eps = of(eps, 2) if eps is not None else 0.0
+        else:
+            new_priorities = priorities.cpu().numpy().copy()
+            mean_priority = float(new_priorities.mean())
+            to_host = lambda x: x.cpu() if isinstance(x, torch.Tensor) else x
+            mean_weight = float(np.asarray(to_host(host_weight)).mean()) if host_weight is not None else 0.0
+            mean_eps = float(np.asarray(eps.cpu() if isinstance(eps, torch.Tensor) else eps).mean()) if eps is not None else 0.0
         stats = dict(value_loss=mean(hip.DQ_VLOSS), grad_norm=grad_norm, train_q_tot=mean(hip.DQ_QINV),
                      target_q_tot=mean(hip.DQ_YINV), normalized_train_q_tot=mean(hip.DQ_Q),
                      normalized_target_q_tot=mean(hip.DQ_Y), mean_td_err=mean(hip.DQ_TD), max_td_err=float(t[hip.DQ_TDMAX]),
-                     new_priorities=float(new_priorities.mean()),
-                     priority_weight=float(np.asarray(host_weight).mean()) if host_weight is not None else 0.0,
-                     epsilon=float(np.asarray(eps.cpu() if isinstance(eps, torch.Tensor) else eps).mean()) if eps is not None else 0.0,
+                     new_priorities=mean_priority, priority_weight=mean_weight, epsilon=mean_eps,
                      frames=int(self.frames), hard_update_count=self.hard_update_count,
                      total_timesteps=float(self.total_timesteps))
 

@@ -284,6 +284,12 @@ _SIGNATURES = {
     "srl_epsilon_greedy_sample": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_long,
                                           c_int, c_int, c_uint64, c_uint64, c_int64, c_void_p, c_void_p, c_void_p]),
     "srl_polyak_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double]),
+    "srl_per_set": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p,
+                            c_void_p]),
+    "srl_per_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint64, c_uint64, c_void_p,
+                               c_void_p]),
+    "srl_replay_gather": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "srl_pairwise_means": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -743,6 +749,53 @@ def polyak_update(target, param, tau):
     _check(
         lib().srl_polyak_update(_stream(), _ptr(target, torch.float32, "target"), _ptr(param, torch.float32, "param"),
                                 target.numel(), float(tau)), "srl_polyak_update")
+
+
+def per_set(sum_tree, min_tree, capacity, n_slots, slots, priorities, alpha, last, max_priority, refused):
+    """``srl_per_set``: the pairs (slots[k], priorities[k]) into both segment trees (views of float64 [2 * capacity]); ``last`` is
+    int32 [capacity] of scratch that holds -1 everywhere between calls."""
+    n = slots.numel()
+    if priorities.numel() != n:
+        raise HipError(f"per_set: {n} slots vs {priorities.numel()} priorities")
+    if sum_tree.numel() != 2 * capacity or min_tree.numel() != 2 * capacity or last.numel() != capacity:
+        raise HipError(f"per_set: trees of {sum_tree.numel()} / {min_tree.numel()} and scratch of {last.numel()} entries for capacity {capacity}")
+    f64, i32 = torch.float64, torch.int32
+    _check(
+        lib().srl_per_set(_stream(), _ptr(sum_tree, f64, "sum_tree"), _ptr(min_tree, f64, "min_tree"), int(capacity), int(n_slots),
+                          _ptr(slots, i32, "slots"), _ptr(priorities, torch.float32, "priorities"), n, float(alpha),
+                          _ptr(last, i32, "last"), _ptr(max_priority, torch.float32, "max_priority"), _ptr(refused, i32, "refused")),
+        "srl_per_set")
+
+
+def per_sample(sum_tree, min_tree, capacity, n_filled, beta, seed, offset, idx, weight):
+    """``srl_per_sample``: ``idx.numel()`` stratified draws (int32, ascending) and their importance weights (float32)."""
+    B = idx.numel()
+    if weight.numel() != B:
+        raise HipError(f"per_sample: {B} indices vs {weight.numel()} weights")
+    if sum_tree.numel() != 2 * capacity or min_tree.numel() != 2 * capacity:
+        raise HipError(f"per_sample: trees of {sum_tree.numel()} / {min_tree.numel()} entries for capacity {capacity}")
+    f64 = torch.float64
+    _check(
+        lib().srl_per_sample(_stream(), _ptr(sum_tree, f64, "sum_tree"), _ptr(min_tree, f64, "min_tree"), int(capacity), int(n_filled), B,
+                             float(beta), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(idx, torch.int32, "idx"),
+                             _ptr(weight, torch.float32, "weight")), "srl_per_sample")
+
+
+def replay_gather(store_ptr, max_size, idx: torch.Tensor, B, Tb, row_bytes, dst_ptr):
+    """dst[t, b, :] = store[idx[b], t, :] (``srl_replay_gather``); ``idx`` int32 [>= B] on the device."""
+    with _scope("replay_gather"):
+        _check(lib().srl_replay_gather(_stream(), store_ptr, int(max_size), _ptr(idx, torch.int32, "idx"), int(B), int(Tb),
+                                       int(row_bytes), dst_ptr), "srl_replay_gather")
+
+
+def pairwise_means(vectors, out):
+    """``srl_pairwise_means``: out[k] = numpy's float32 mean of vectors[k] (a float32 device tensor, or None -> 0.0), k < 3."""
+    if len(vectors) != 3 or out.numel() != 3:
+        raise HipError("pairwise_means: three vectors and three float64 results")
+    args = []
+    for k, v in enumerate(vectors):
+        args += [_ptr(v, torch.float32, f"vectors[{k}]"), 0 if v is None else v.numel()]
+    _check(lib().srl_pairwise_means(_stream(), *args, _ptr(out, torch.float64, "out")), "srl_pairwise_means")
 
 
 def categorical_log_softmax(logits, avail, head_dims, out):

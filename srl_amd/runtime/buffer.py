@@ -21,6 +21,7 @@ class ReplayEntry:
     receive_time: float
     sample: object
     reuses: int = 0
+    sampling_indices: object = None  # the slots a prioritised replay buffer drew (base/buffer.py:30); host or device
 
     def __lt__(self, other):
         return (self.reuses_left, self.receive_time) < (other.reuses_left, other.receive_time)
@@ -69,3 +70,17 @@ class PriorityQueueBuffer:
         if not self.full() and entry.reuses_left > 0:
             self._insert(entry)
         return entry
+
+
+def make_buffer(name, **buffer_args):
+    """The reference's factory (``base/buffer.py:533-541``) plus ``prioritized_replay_buffer_hip``, the buffer resident in HBM
+    (runtime/replay.py).  The reference's plain queue and its uniform replay buffer have no counterpart here."""
+    if name == "priority_queue":
+        return PriorityQueueBuffer(**buffer_args)
+    if name in ("prioritized_replay_buffer", "prioritized_replay_buffer_hip"):
+        from srl_amd.runtime import replay
+        cls = replay.PrioritizedReplayBuffer if name == "prioritized_replay_buffer" else replay.DevicePrioritizedReplayBuffer
+        return cls(**buffer_args)
+    if name in ("simple_queue", "simple_replay_buffer"):
+        raise NotImplementedError(f"buffer {name!r} is not implemented")
+    raise KeyError(f"unknown buffer {name!r}")
