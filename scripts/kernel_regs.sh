@@ -16,5 +16,6 @@ for line in sys.stdin:
         kv=t.split(':')
         if len(kv)==2: cur[kv[0].strip()]=kv[1].strip()
         if kv[0].strip().startswith('LDS Size'):
-            print(cur.get('name','?')[:60], '| vgpr',cur.get('VGPRs'),'agpr',cur.get('AGPRs'),'scratch',cur.get('ScratchSize [bytes/lane]'),'occ',cur.get('Occupancy [waves/SIMD]'),'lds',cur.get('LDS Size [bytes/block]'))
+            n=cur.get('name','?').split(' ')[0]   # (template kernels differ in their last arguments: keep the name's tail too)
+            print(n[:60]+('..'+n[-36:] if len(n)>96 else n[60:]), '| vgpr',cur.get('VGPRs'),'agpr',cur.get('AGPRs'),'scratch',cur.get('ScratchSize [bytes/lane]'),'occ',cur.get('Occupancy [waves/SIMD]'),'lds',cur.get('LDS Size [bytes/block]'))
 " | grep -E "$pat"

@@ -44,7 +44,7 @@ struct MArgs {
 __device__ __forceinline__ int mm_ch(int e, int hb) { return (e & 3) + 8 * (e >> 2) + 4 * hb; }
 // how many of a block's 16 k-pairs (register e of both half-lanes) hold channels below `dim`: registers 4g .. 4g + 3 carry channels
 // 8g .. 8g + 7, so a 4-wide input needs 4 of the 16 MFMAs of its block (the others multiply padding zeros)
-__device__ __forceinline__ int mm_ne(int dim, int blk) {
+constexpr __host__ __device__ __forceinline__ int mm_ne(int dim, int blk) {
   const int left = dim - 32 * blk;
   return left >= 32 ? 16 : (left <= 0 ? 0 : 4 * ((left + 7) >> 3));
 }

@@ -303,6 +303,15 @@ int fill(Args& a, const srl_mlp_layer* layers, int n) {
 #include "mlp_sig.h"
 #include "mlp_sigh.h"
 
+// A shape with kernels of its own (mlp_sig.h's list) runs them, on f16 pieces (LinF16, mlp_sigh.h) or float32 MFMAs (LinF32).
+// SRL_MLP_F16: the forward pass takes f16 pieces for every value but 0, the backward pass with bit 0 set and bit 1 clear.
+static bool shape_fwd(const Args& a, hipStream_t st) {
+  return sx_enabled() && (hx_mode() != 0 ? Sigs::fwd<LinF16>(a, st) : Sigs::fwd<LinF32>(a, st));
+}
+static bool shape_bwd(const Args& a, hipStream_t st) {
+  return sx_enabled() && ((hx_mode() & 1) && !(hx_mode() & 2) ? Sigs::bwd<LinF16>(a, st) : Sigs::bwd<LinF32>(a, st));
+}
+
 // rows from which the matrix-core chain (mlp_mfma.h) takes over from the FMA chain
 constexpr long kMfmaMinRows = 512;
 
@@ -352,7 +361,7 @@ extern "C" int srl_mlp_fwd(void* stream, const srl_mlp_layer* layers, int n, con
   a.x = x; a.ldx = ldx; a.rows = rows; a.tape = tape; a.tld = tape_ld; a.y = y; a.ldy = ldy;
   MArgs m;
   if (mfma_takes(a, rows, m)) {
-    if (hx_fwd(a, (hipStream_t)stream) || sx_fwd(a, (hipStream_t)stream)) {   // a shape with a kernel of its own (mlp_sigh.h / mlp_sig.h)
+    if (shape_fwd(a, (hipStream_t)stream)) {
       SRL_LAUNCH_CHECK();
       return 0;
     }
@@ -411,7 +420,7 @@ static int mlp_bwd_impl(void* stream, const srl_mlp_layer* layers, int n, const 
   a.dx = dx; a.lddx = lddx;
   MArgs m;
   if (mfma_takes(a, rows, m)) {
-    if (hx_bwd(a, (hipStream_t)stream) || sx_bwd(a, (hipStream_t)stream)) {
+    if (shape_bwd(a, (hipStream_t)stream)) {
       SRL_LAUNCH_CHECK();
       return 0;
     }

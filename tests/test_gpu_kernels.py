@@ -1397,8 +1397,11 @@ _SIG_CHAINS = {
 }
 
 
+# (the last two: the smallest ragged batches.  The kernels see the rows that the gate filter below keeps, 516 of 534 and 611 of 640:
+# from 512 rows on a chain is the matrix-core kernels', and neither count is a multiple of a workgroup's 128 rows.  Of 513 rows
+# the filter keeps 488, which is the FMA chain's and needs a tape)
 @pytest.mark.parametrize("rows,chain", [(4096, "c1-actor"), (5003, "c1-critic"), (131072, "c1-actor"), (6001, "smac-obs"),
-                                        (3001, "smac-state")])
+                                        (3001, "smac-state"), (534, "c1-critic"), (640, "smac-obs")])
 def test_mlp_chain_shape_kernels_match_the_generic_ones(rows, chain):
     """csrc/mlp_sig.h: the towers of BASELINE configs[0] (LayerNorm 4, 4 -> 64 ReLU, LayerNorm 64, 64 -> 64 ReLU, 64 -> 64 ReLU, 64 ->
     2 | 1) and the encoders of configs[3]'s multi-agent policy (LayerNorm 30 | 48, -> 64 ReLU, LayerNorm, 64 -> 64 ReLU, LayerNorm)
@@ -1573,6 +1576,83 @@ def test_mlp_chain_backward_with_input_gradient(rows, chain):
     assert rel_close(dxo.cpu().numpy(), x64.grad.numpy(), 2e-5, scale=float(x64.grad.abs().max()))
     for k, (g, p_) in enumerate(zip(dev_g, p64)):
         assert rel_close(g.cpu().numpy(), p_.grad.numpy(), 2e-5, scale=float(p_.grad.abs().max()) + 1e-6), k
+
+
+@pytest.mark.parametrize("chain", [[(0, 64, 64, 0), (1, 64, 9, 0)], [(0, 64, 64, 0), (1, 64, 1, 0)]], ids=["actor-tail", "critic-tail"])
+def test_mlp_tails_with_input_gradient_on_every_kernel_family(chain, tmp_path):
+    """srl_mlp_fwd / srl_mlp_bwd_dx on configs[3]'s tails (LayerNorm 64, 64 -> 9 | 1) through all three kernel families -- the shape
+    kernels on f16 pieces, the shape kernels on float32 MFMAs (SRL_MLP_F16=0) and the generic matrix-core chain (SRL_MLP_SIG=0), a
+    child process each -- against float64 autograd: y, dx and every parameter gradient.  513 and 640 rows: just past the row count
+    from which the matrix-core kernels take a chain, no multiple of the 128 rows of a workgroup's four tiles (whole tiles past the
+    end; at 513 a last tile of one row).  No ReLU in these chains: every row stays in."""
+    import subprocess, sys, json
+    t = torch
+    din, dout = chain[0][1], chain[-1][2]
+    cases = {}
+    def draw(rows, seed):
+        rng = np.random.default_rng(seed)
+        host = []
+        for kind, i, o, act in chain:
+            if kind == 0:
+                w, b = 1 + 0.1 * rng.standard_normal(i), 0.1 * rng.standard_normal(i)
+            else:
+                w, b = rng.standard_normal((o, i)) / np.sqrt(i), 0.1 * rng.standard_normal(o)
+            host += [w.astype(np.float32), b.astype(np.float32)]
+        return host, rng.standard_normal((rows, din)).astype(np.float32), rng.standard_normal((rows, dout)).astype(np.float32)
+
+    for rows in (513, 640):
+        # The head's bias gradient is dy's column sums and LayerNorm's dbeta is W^T times them, and the tolerance is relative to the
+        # gradient's own largest element.  The sums of standard normals have standard deviation sqrt(rows), and a draw can cancel far
+        # below that (seed 513, one column: 0.17 = 0.007 sqrt(rows)); the f16 pieces' error does not cancel with them: 2^-21 of
+        # |w| |dz| per term, ~ 2^-21 sqrt(rows) over the rows.  So: the first seed from `rows` on whose largest column sum reaches
+        # half a standard deviation, where the pieces' share is <= 2 * 2^-21 ~ 1e-6 of the gradient -- decided by the data alone.
+        seed = rows
+        while np.abs(draw(rows, seed)[2].astype(np.float64).sum(0)).max() < 0.5 * np.sqrt(rows):
+            seed += 1
+        host, x, dy = draw(rows, seed)
+        np.savez(tmp_path / f"in{rows}.npz", x=x, dy=dy, **{f"p{k}": p for k, p in enumerate(host)})
+        p64 = [t.from_numpy(p).double().requires_grad_(True) for p in host]
+        x64 = t.from_numpy(x).double().requires_grad_(True)
+        h = x64
+        for li, (kind, i, o, act) in enumerate(chain):
+            w, b = p64[2 * li], p64[2 * li + 1]
+            h = t.nn.functional.layer_norm(h, (i,), w, b, 1e-5) if kind == 0 else h @ w.t() + b
+        h.backward(t.from_numpy(dy).double())
+        cases[rows] = (h.detach().numpy(), x64.grad.numpy(), [p.grad.numpy() for p in p64])
+    code = r'''
+import sys, json, numpy as np, torch
+from srl_amd import hip
+chain, td = json.loads(sys.argv[1]), sys.argv[2]
+din, dout = chain[0][1], chain[-1][2]
+for rows in (513, 640):
+    z = np.load(f"{td}/in{rows}.npz")
+    par = [torch.from_numpy(z[f"p{k}"]).cuda() for k in range(2 * len(chain))]
+    grads = [torch.zeros_like(p) for p in par]
+    desc = [(kind, i, o, act, par[2 * li].data_ptr(), par[2 * li + 1].data_ptr(), grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr())
+            for li, (kind, i, o, act) in enumerate(chain)]
+    arr = hip.mlp_layers(desc)
+    assert hip.mlp_tape_floats_at(arr, rows) == 0
+    x, dy = torch.from_numpy(z["x"]).cuda(), torch.from_numpy(z["dy"]).cuda()
+    y = torch.full((rows, dout), float("nan"), device="cuda")
+    dx = torch.full((rows, din), float("nan"), device="cuda")
+    hip.mlp_fwd(arr, x.data_ptr(), din, rows, 0, 0, y.data_ptr(), dout)
+    hip.mlp_bwd_dx(arr, x.data_ptr(), din, rows, dy.data_ptr(), dout, dx.data_ptr(), din)
+    torch.cuda.synchronize()
+    np.savez(f"{td}/out{rows}_{sys.argv[3]}.npz", y=y.cpu().numpy(), dx=dx.cpu().numpy(), **{f"g{k}": g.cpu().numpy() for k, g in enumerate(grads)})
+'''
+    for tag, sig, f16 in (("f16", "1", "1"), ("f32", "1", "0"), ("generic", "0", "1")):
+        env = dict(os.environ, SRL_MLP_SIG=sig, SRL_MLP_F16=f16, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        r = subprocess.run([sys.executable, "-c", code, json.dumps(chain), str(tmp_path), tag], env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        for rows, (y64, dx64, g64) in cases.items():
+            got = np.load(tmp_path / f"out{rows}_{tag}.npz")
+            err = lambda a, b: float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+            print(tag, rows, "y", err(got["y"], y64), "dx", err(got["dx"], dx64), "grads", [err(got[f"g{k}"], g) for k, g in enumerate(g64)])
+            assert rel_close(got["y"], y64, 1e-5, scale=float(np.abs(y64).max())), (tag, rows)
+            assert rel_close(got["dx"], dx64, 2e-5, scale=float(np.abs(dx64).max())), (tag, rows)
+            for k, g in enumerate(g64):
+                assert rel_close(got[f"g{k}"], g, 2e-5, scale=float(np.abs(g).max()) + 1e-6), (tag, rows, k)
 
 
 @pytest.mark.parametrize("cin,cout,k", [(4, 8, 3), (8, 4, 3), (4, 4, 3), (8, 8, 3), (4, 4, 5), (4, 8, 5)])
