@@ -968,7 +968,12 @@ int srl_rmsprop_step(void* stream, float* p, const float* g, float* square_avg, 
  * The descriptor is passed by value to the kernel: no allocation, no copy, no synchronisation -- capturable.
  * srl_entity_attn_supported: 1 when D is 16, 32 or 64, 1 <= nkeys <= 3, 1 <= E <= 64, 1 <= S <= 128 and 1 <= f_k <= 64
  * (one row's intermediates then fit the 160 KiB of LDS; parameters and gradient sums are staged there too when room is
- * left, else read from / added to global memory), else 0.  The pointers are not looked at. */
+ * left, else read from / added to global memory), else 0.  The pointers are not looked at.
+ * srl_entity_attn_plan: host-only, no launch: the plan srl_entity_attn_fwd (bwd == 0) / _bwd (bwd != 0) would run `rows` rows
+ *   on, from the code the launches themselves use.  out [6]: out[0] R (rows per tile), out[1] stage_p (parameters staged in
+ *   LDS), out[2] stage_g (gradient sums kept in LDS over the workgroup's tiles), out[3] LDS bytes of a workgroup, out[4]
+ *   workgroups launched, out[5] tiles; workgroup w takes the tiles w, w + out[4], ...  Returns 0, or the error
+ *   srl_entity_attn_fwd would give for the shape.  The pointers of the descriptor are not looked at. */
 #define SRL_EATTN_MAX_KEYS 3
 enum {                      /* parameter slots of srl_entity_attn::p / ::g (k = entity leaf 0..2) */
   SRL_EATTN_LN_SELF_W = 0,  /* [S] */
@@ -1003,6 +1008,7 @@ typedef struct srl_entity_attn {
 int srl_entity_attn_supported(const srl_entity_attn* d);
 int srl_entity_attn_fwd(void* stream, const srl_entity_attn* d, int64_t rows, float* out, int64_t ldo);
 int srl_entity_attn_bwd(void* stream, const srl_entity_attn* d, int64_t rows, const float* d_out, int64_t lddo);
+int srl_entity_attn_plan(const srl_entity_attn* d, int bwd, int64_t rows, int32_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Language encoder of the DMLab agent (csrc/instr_lstm.hip; ABI 20): DMLabActorCritic.forward's instruction branch
@@ -1023,7 +1029,11 @@ int srl_entity_attn_bwd(void* stream, const srl_entity_attn* d, int64_t rows, co
  *   narrows the grid).  No input gradient is formed (the inputs are token ids).
  * The descriptor is passed by value to the kernel: no allocation, no copy, no synchronisation -- capturable.
  * srl_instr_lstm_supported: 1 when 1 <= V <= 65536, 1 <= Ed <= 32, H is 32 or 64 and 1 <= L <= 64 (W_ih | W_hh, staged once per
- * workgroup, and one 32-row tile's operands then fit the 160 KiB of LDS), else 0.  The pointers are not looked at. */
+ * workgroup, and one 32-row tile's operands then fit the 160 KiB of LDS), else 0.  The pointers are not looked at.
+ * srl_instr_lstm_groups: host-only, no launch: the workgroups srl_instr_lstm_fwd (workspace_bytes < 0) / srl_instr_lstm_bwd
+ *   with a workspace of workspace_bytes >= 0 bytes would launch for `rows` rows of 32-row tiles (workgroup w takes the tiles
+ *   w, w + groups, ...), from the code the launches themselves use; 0 where the call launches nothing (rows <= 0) or is
+ *   refused (an unsupported shape, a workspace short of one workgroup's states).  The pointers are not looked at. */
 typedef struct srl_instr_lstm {
   int32_t V, Ed, H, L;      /* vocabulary, embedding width, LSTM units, tokens per row */
   int32_t tok_i32, pad_;    /* tokens are int32 (else float32) */
@@ -1038,6 +1048,7 @@ typedef struct srl_instr_lstm {
 } srl_instr_lstm;
 int srl_instr_lstm_supported(const srl_instr_lstm* d);
 int64_t srl_instr_lstm_bwd_workspace(const srl_instr_lstm* d, int64_t rows);
+int64_t srl_instr_lstm_groups(const srl_instr_lstm* d, int64_t rows, int64_t workspace_bytes);
 int srl_instr_lstm_fwd(void* stream, const srl_instr_lstm* d, int64_t rows, float* out, int64_t ldo);
 int srl_instr_lstm_bwd(void* stream, const srl_instr_lstm* d, int64_t rows, const float* d_out, int64_t lddo, void* workspace,
                        int64_t workspace_bytes);

@@ -619,6 +619,27 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
   }
 }
 
+// The grid a plan runs `rows` rows on: what launch<> uses and what srl_entity_attn_plan reports.
+struct EaGrid {
+  size_t lds;       // dynamic LDS bytes of a workgroup
+  int64_t ntiles;   // tiles of R rows
+  unsigned groups;  // workgroups launched: min(ntiles, CUs x workgroups a CU holds)
+};
+
+EaGrid make_grid(const EaPlan& pl, int64_t rows) {
+  EaGrid g;
+  int cus = 256;
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  g.lds = (size_t)pl.total * sizeof(float);
+  g.ntiles = srl_ceil_div(rows, (int64_t)pl.R);
+  int per_cu = (int)((size_t)(160 * 1024) / (g.lds ? g.lds : 1));
+  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);   // (a CU holds at most two workgroups of 1024 threads)
+  const int64_t cap = (int64_t)cus * per_cu;
+  g.groups = (unsigned)(g.ntiles < cap ? g.ntiles : cap);
+  return g;
+}
+
 template <bool BWD>
 int launch(void* stream, const srl_entity_attn* d, const EaPlan& pl, int64_t rows, float* out, int64_t ldo, const float* dout,
            int64_t lddo) {
@@ -628,15 +649,8 @@ int launch(void* stream, const srl_entity_attn* d, const EaPlan& pl, int64_t row
   a.pl = pl;
   a.rows = rows; a.out = out; a.ldo = ldo; a.dout = dout; a.lddo = lddo;
   if (rows == 0) return 0;
-  int cus = 256;
-  int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t lds = (size_t)a.pl.total * sizeof(float);
-  const int64_t ntiles = srl_ceil_div(rows, (int64_t)a.pl.R);
-  int per_cu = (int)((size_t)(160 * 1024) / (lds ? lds : 1));
-  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);   // (a CU holds at most two workgroups of 1024 threads)
-  const int64_t cap = (int64_t)cus * per_cu;
-  const unsigned grid = (unsigned)(ntiles < cap ? ntiles : cap);
+  const EaGrid g = make_grid(a.pl, rows);
+  const size_t lds = g.lds;
   void (*kern)(const EaArgs) = nullptr;
   switch (d->D / kHeads) {
     case 4: kern = entity_attn_kernel<4, BWD>; break;
@@ -645,15 +659,21 @@ int launch(void* stream, const srl_entity_attn* d, const EaPlan& pl, int64_t row
   }
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kern, dim3(g.groups), dim3(kThreads), lds, (hipStream_t)stream, a);
   SRL_LAUNCH_CHECK();
   return 0;
 }
 
-int check_desc(const srl_entity_attn* d, bool bwd, EaPlan* plan, const char** why) {
+// the shape part of check_desc (no pointer is looked at)
+int check_shape(const srl_entity_attn* d, bool bwd, EaPlan* plan, const char** why) {
   if (!valid_shape(d)) { *why = "unsupported shape (srl_entity_attn_supported)"; return 0; }
-  EaPlan& pl = *plan;
-  if (!make_plan(*d, bwd, &pl)) { *why = "one row does not fit the LDS"; return 0; }
+  if (!make_plan(*d, bwd, plan)) { *why = "one row does not fit the LDS"; return 0; }
+  return 1;
+}
+
+int check_desc(const srl_entity_attn* d, bool bwd, EaPlan* plan, const char** why) {
+  if (!check_shape(d, bwd, plan, why)) return 0;
+  const EaPlan& pl = *plan;
   for (int s = 0; s < NS; ++s) {
     if (pl.n[s] && (!d->p[s] || (bwd && !d->g[s]))) { *why = "null parameter / gradient"; return 0; }
   }
@@ -669,6 +689,17 @@ extern "C" int srl_entity_attn_supported(const srl_entity_attn* d) {
   if (!valid_shape(d)) return 0;
   EaPlan pl;
   return make_plan(*d, false, &pl) && make_plan(*d, true, &pl) ? 1 : 0;
+}
+
+extern "C" int srl_entity_attn_plan(const srl_entity_attn* d, int bwd, int64_t rows, int32_t* out) {
+  const char* why = "";
+  EaPlan pl;
+  SRL_CHECK_ARG(check_shape(d, bwd != 0, &pl, &why), why);
+  SRL_CHECK_ARG(out && rows >= 0, "null out / negative rows");
+  const EaGrid g = make_grid(pl, rows);
+  out[0] = pl.R; out[1] = pl.stage_p; out[2] = pl.stage_g; out[3] = (int32_t)g.lds;
+  out[4] = (int32_t)g.groups; out[5] = (int32_t)g.ntiles;
+  return 0;
 }
 
 extern "C" int srl_entity_attn_fwd(void* stream, const srl_entity_attn* d, int64_t rows, float* out, int64_t ldo) {

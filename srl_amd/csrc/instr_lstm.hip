@@ -333,6 +333,22 @@ int check_desc(const srl_instr_lstm* d, bool bwd, const char** why) {
   return 1;
 }
 
+// workgroups a launch runs `rows` rows on (the staged weights take more than half the LDS: one workgroup per CU), at most
+// `max_groups`: what launch<> uses and what srl_instr_lstm_groups reports
+int64_t make_grid(int64_t rows, int64_t max_groups) {
+  int cus = 256;
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int64_t ntiles = srl_ceil_div(rows, (int64_t)kRows);
+  const int64_t grid = ntiles < cus ? ntiles : cus;
+  return grid < max_groups ? grid : max_groups;
+}
+
+// workgroups a caller's workspace holds the states of (srl_instr_lstm_bwd refuses 0)
+int64_t ws_groups(const srl_instr_lstm& d, int64_t workspace_bytes) {
+  return workspace_bytes / (ws_floats_per_group(d) * (int64_t)sizeof(float));
+}
+
 template <bool BWD>
 int launch(void* stream, const srl_instr_lstm* d, int64_t rows, float* out, int64_t ldo, const float* dout, int64_t lddo, float* ws,
            int64_t max_groups) {
@@ -342,13 +358,8 @@ int launch(void* stream, const srl_instr_lstm* d, int64_t rows, float* out, int6
   a.d = *d;
   make_plan(*d, BWD, &a.pl);
   a.rows = rows; a.out = out; a.ldo = ldo; a.dout = dout; a.lddo = lddo; a.ws = ws;
-  int cus = 256;
-  int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const size_t lds = (size_t)a.pl.total * sizeof(float);
-  const int64_t ntiles = srl_ceil_div(rows, (int64_t)kRows);
-  int64_t grid = ntiles < cus ? ntiles : cus;   // the staged weights take more than half the LDS: one workgroup per CU
-  if (grid > max_groups) grid = max_groups;
+  const int64_t grid = make_grid(rows, max_groups);
   void (*kern)(const IlArgs) = d->H == 64 ? instr_lstm_kernel<2, BWD> : instr_lstm_kernel<1, BWD>;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -387,7 +398,13 @@ extern "C" int srl_instr_lstm_bwd(void* stream, const srl_instr_lstm* d, int64_t
   SRL_CHECK_ARG(srl_instr_lstm_supported(d), "unsupported shape (srl_instr_lstm_supported)");
   SRL_CHECK_ARG(d_out && rows >= 0 && lddo >= d->H, "null d_out / short d_out rows");
   if (rows == 0) return 0;
-  const int64_t per = ws_floats_per_group(*d) * (int64_t)sizeof(float);
-  SRL_CHECK_ARG(workspace && workspace_bytes >= per, "workspace smaller than one workgroup's states (srl_instr_lstm_bwd_workspace)");
-  return launch<true>(stream, d, rows, nullptr, 0, d_out, lddo, static_cast<float*>(workspace), workspace_bytes / per);
+  SRL_CHECK_ARG(workspace && ws_groups(*d, workspace_bytes) >= 1, "workspace smaller than one workgroup's states (srl_instr_lstm_bwd_workspace)");
+  return launch<true>(stream, d, rows, nullptr, 0, d_out, lddo, static_cast<float*>(workspace), ws_groups(*d, workspace_bytes));
+}
+
+extern "C" int64_t srl_instr_lstm_groups(const srl_instr_lstm* d, int64_t rows, int64_t workspace_bytes) {
+  if (!srl_instr_lstm_supported(d) || rows <= 0) return 0;
+  if (workspace_bytes < 0) return make_grid(rows, kMaxGrid);
+  const int64_t fit = ws_groups(*d, workspace_bytes);
+  return fit >= 1 ? make_grid(rows, fit) : 0;
 }

@@ -1023,6 +1023,17 @@ def entity_attn_supported(D, S, keys) -> bool:
     return bool(lib().srl_entity_attn_supported(ctypes.byref(entity_attn_desc(D, S, keys))))
 
 
+def entity_attn_plan(D, S, keys, bwd, rows) -> dict:
+    """The plan ``entity_attn_fwd`` (``bwd`` false) / ``_bwd`` would run ``rows`` rows on (``srl_entity_attn_plan``: the code the
+    launches use; needs the library, not a GPU): R rows per tile, stage_p / stage_g (parameters / gradient sums in LDS), lds
+    bytes, groups launched, tiles."""
+    if len(keys) > EATTN_MAX_KEYS:
+        raise HipError(f"entity_attn_plan: {len(keys)} entity leaves, at most {EATTN_MAX_KEYS}")
+    out = (ctypes.c_int32 * 6)()
+    _check(lib().srl_entity_attn_plan(ctypes.byref(entity_attn_desc(D, S, keys)), int(bool(bwd)), int(rows), out), "srl_entity_attn_plan")
+    return dict(zip(("R", "stage_p", "stage_g", "lds", "groups", "tiles"), (int(v) for v in out)))
+
+
 def _entity_attn_leaves(d: EntityAttn, x_self, x_keys, mask) -> EntityAttn:
     """A copy of the descriptor with this call's leaves, each (raw pointer, row pitch in elements): a descriptor that an executor
     keeps is never written to, so calls from two threads do not meet in it."""
@@ -1075,6 +1086,12 @@ def _instr_lstm_tokens(d: InstrLstm, tok_ptr, ld_tok, tok_i32) -> InstrLstm:
 def instr_lstm_bwd_workspace(d: InstrLstm, rows) -> int:
     """Bytes of workspace ``instr_lstm_bwd`` wants for ``rows`` rows (``srl_instr_lstm_bwd_workspace``)."""
     return int(lib().srl_instr_lstm_bwd_workspace(ctypes.byref(d), int(rows)))
+
+
+def instr_lstm_groups(d: InstrLstm, rows, workspace_bytes=-1) -> int:
+    """Workgroups ``instr_lstm_fwd`` (``workspace_bytes`` < 0) / ``instr_lstm_bwd`` with that many bytes of workspace launches for
+    ``rows`` rows (``srl_instr_lstm_groups``: the code the launches use); 0: nothing is launched, or the call is refused."""
+    return int(lib().srl_instr_lstm_groups(ctypes.byref(d), int(rows), int(workspace_bytes)))
 
 
 def instr_lstm_fwd(d: InstrLstm, tok_ptr, ld_tok, tok_i32, rows, out_ptr, ldo):
