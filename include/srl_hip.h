@@ -79,6 +79,14 @@ int srl_dispatch_tiles(uint64_t* keys, int64_t* counts, int cap, int reset);
  * there and the last one to finish adds them in a fixed order and overwrites stats: no extra launch,
  * bitwise reproducible sums (batches below 98 304 columns; wider ones stream for hundreds of microseconds
  * and keep the memset + atomics, which is faster there).
+ *
+ * srl_gae_scan_plan: host-only, no launch: the tiling srl_gae_scan would run a [T, B, Nc] call on, from the function the
+ * launch itself uses.  aligned != 0: every float leaf lies on 16 bytes and every flag leaf on 4 (what srl_gae_scan tests on
+ * its pointers); vtrace != 0: imp_ratio given; tensors != 0: gamma_t or lambda_t given.  out [7]: out[0] kernel (0 the
+ * register-resident scan: Nc == 1, B % 4 == 0, aligned, no per-step tensors; 1 the LDS-staged one), out[1] its width (column
+ * quads per workgroup row: 4, 8, 32, 64, 128, 256; columns of the LDS kernel: 16, 64), out[2] time rows per lane (1, 2, 4; 0
+ * for the LDS kernel), out[3] rows of a time tile, out[4] time tiles = ceil(T / out[3]), taken from the end so that the one
+ * holding row 0 is the partial one, out[5] workgroups (0 for an empty batch), out[6] 1 when a workspace would be used.
  */
 int srl_gae_scan(void* stream, const float* reward, const float* value, const uint8_t* done,
                  const uint8_t* truncated, const uint8_t* on_reset, const float* imp_ratio,
@@ -86,6 +94,7 @@ int srl_gae_scan(void* stream, const float* reward, const float* value, const ui
                  double lambda, double rho, double c, float* adv, float* ret, double* stats,
                  void* workspace);
 long srl_gae_scan_workspace_bytes(int B, int Nc);
+int srl_gae_scan_plan(int T, int B, int Nc, int aligned, int vtrace, int tensors, int32_t* out);
 
 /* Masked statistics {n, sum x*mask, sum (x*mask)^2} in float64 (utils.py:38-57).
  * mask: uint8[n] or NULL (no mask: n = count); mask_invert != 0 means mask = 1 - byte

@@ -14,7 +14,8 @@
 // unbounded.  All arithmetic that the reference does in float64 (gae.py:46-48) is float64 here.
 // Two kernels share that scheme: gae_scan_reg_kernel (one value channel, B % 4 == 0 -- the trainer's
 // layout; register-resident quads of columns, 16-byte loads, log-step scan over chunk maps) and
-// gae_scan_kernel (any Nc / alignment; LDS-staged tile).
+// gae_scan_kernel (any Nc / alignment; LDS-staged tile).  Which one a call takes, at which width, rows per lane and time tile, is
+// decided in gae_plan(), which srl_gae_scan launches from and srl_gae_scan_plan reports.
 #include "srl_common.h"
 
 namespace {
@@ -209,9 +210,24 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(GaeParams p) {
   stats_finish(p, acc, red);
 }
 
-template <int COLS>
-size_t gae_lds_bytes(int TT, bool vtrace, bool glt) {
-  constexpr int SEG = 256 / COLS;
+// ---- the launch choice -------------------------------------------------------------------------------
+// Which kernel, how wide, how many rows per lane, which time tile and grid a call takes: decided here and nowhere else.
+// srl_gae_scan launches what gae_plan() returns and srl_gae_scan_plan reports it, so a test that asks the plan sees the
+// thresholds the launch uses.
+struct GaePlan {
+  int kernel;  // 0: gae_scan_reg_kernel, 1: gae_scan_kernel
+  int width;   // CQ (column quads per workgroup row) of the register kernel, COLS of the LDS kernel
+  int L;       // time rows per lane of the register kernel; 0 for the LDS kernel
+  int TT;      // time tile: SEG * L rows (register), the largest tile under the LDS budget (LDS)
+  int tiles;   // ceil(T / TT)
+  long grid;   // workgroups (0: nothing is launched)
+  int ws;      // a workspace, if given, is used for the statistics
+  size_t lds;  // dynamic LDS bytes (LDS kernel)
+};
+
+// LDS carve of gae_scan_kernel<COLS, vtrace, glt> at a time tile of TT rows
+size_t gae_lds_bytes(int COLS, int TT, bool vtrace, bool glt) {
+  const int SEG = 256 / COLS;
   size_t b = sizeof(double) * (2 * SEG * COLS + COLS + 12);
   b += sizeof(float) * ((size_t)TT * COLS + (size_t)(TT + 1) * COLS + (vtrace ? (size_t)TT * COLS : 0) +
                         (glt ? 2 * (size_t)TT * COLS : 0));
@@ -219,17 +235,55 @@ size_t gae_lds_bytes(int TT, bool vtrace, bool glt) {
   return (b + 15) & ~size_t(15);
 }
 
+// `aligned`: every float leaf on 16 bytes and every flag leaf on 4 (the test srl_gae_scan makes on its pointers)
+GaePlan gae_plan(int T, int B, int Nc, bool aligned, bool vtrace, bool glt) {
+  GaePlan pl{};
+  const long ncols = (long)B * Nc;
+  // The ticketed reduction pays a release fence per workgroup (its own stores must have landed before the ticket): worth it
+  // where the zeroing launch is a large part of the call (<= 768 workgroups), not on grids that stream for hundreds of
+  // microseconds (measured at 2^20 environments: 547 us against 505 with the memset + atomics)
+  pl.ws = ncols < 98304;
+  const bool quads = Nc == 1 && B % 4 == 0 && !glt && aligned;
+  if (quads) {
+    // Row width per workgroup grows with the batch (measured on MI355X, scripts/gae_sweep.py): wide
+    // rows stream best (1 KiB = 8 whole cache lines per wave load) but need B/256 >> 256 workgroups.
+    int lmax = 4;
+    if (ncols < 2048) pl.width = 4;
+    else if (ncols < 16384) pl.width = 8;
+    else if (ncols < 98304) pl.width = 32;
+    else if (ncols < 393216) pl.width = 64;
+    else if (ncols < 786432) pl.width = 128, lmax = 2;
+    else pl.width = 256, lmax = 2;  // one lane per column quad, pure streaming over T
+    const int SEG = 256 / pl.width;
+    const int need = (T + SEG - 1) / SEG;  // rows per lane if one time tile covered all of T
+    // longer T: several time tiles, carry in registers
+    pl.L = need <= 1 ? 1 : (need <= 2 || lmax == 2) ? 2 : 4;
+    pl.kernel = 0;
+    pl.TT = SEG * pl.L;
+    pl.grid = srl_ceil_div(ncols, (long)pl.width * 4);
+  } else {
+    // narrow tiles while the grid would not cover the chip; wide (256-byte rows) once it does
+    pl.width = ncols >= 64L * 512 ? 64 : 16;
+    pl.kernel = 1;
+    // largest time tile that keeps the LDS tile under ~60 KiB (>= 2 workgroups per CU)
+    const size_t budget = 60 * 1024;
+    int TT = T;
+    while (TT > 8 && gae_lds_bytes(pl.width, TT, vtrace, glt) > budget) TT = (TT + 1) / 2;
+    pl.TT = TT;
+    pl.lds = gae_lds_bytes(pl.width, TT, vtrace, glt);
+    pl.grid = srl_ceil_div(ncols, (long)pl.width);
+  }
+  pl.tiles = pl.TT > 0 ? (T + pl.TT - 1) / pl.TT : 0;
+  if (T == 0 || B == 0) pl.grid = 0;  // empty batch: nothing to scan
+  return pl;
+}
+
 template <int COLS>
-int launch_gae(hipStream_t st, GaeParams p, bool vtrace) {
+int launch_gae(hipStream_t st, GaeParams p, bool vtrace, const GaePlan& pl) {
   const bool glt = p.gamma_t != nullptr || p.lambda_t != nullptr;
-  // largest time tile that keeps the LDS tile under ~60 KiB (>= 2 workgroups per CU)
-  const size_t budget = 60 * 1024;
-  int TT = p.T;
-  while (TT > 8 && gae_lds_bytes<COLS>(TT, vtrace, glt) > budget) TT = (TT + 1) / 2;
-  p.TT = TT;
-  const size_t lds = gae_lds_bytes<COLS>(TT, vtrace, glt);
-  const long ncols = (long)p.B * p.Nc;
-  dim3 grid((unsigned)srl_ceil_div(ncols, COLS));
+  p.TT = pl.TT;
+  const size_t lds = pl.lds;
+  dim3 grid((unsigned)pl.grid);
   if (vtrace && glt)
     hipLaunchKernelGGL((gae_scan_kernel<COLS, true, true>), grid, dim3(256), lds, st, p);
   else if (vtrace)
@@ -401,8 +455,8 @@ __global__ __launch_bounds__(256) void gae_scan_reg_kernel(GaeParams p) {
 }
 
 template <int CQ, int L>
-int launch_gae_reg(hipStream_t st, const GaeParams& p, bool vtrace) {
-  dim3 grid((unsigned)srl_ceil_div((long)p.B, (long)CQ * 4));
+int launch_gae_reg(hipStream_t st, const GaeParams& p, bool vtrace, const GaePlan& pl) {
+  dim3 grid((unsigned)pl.grid);
   if (vtrace)
     hipLaunchKernelGGL((gae_scan_reg_kernel<CQ, L, true>), grid, dim3(256), 0, st, p);
   else
@@ -412,12 +466,10 @@ int launch_gae_reg(hipStream_t st, const GaeParams& p, bool vtrace) {
 }
 
 template <int CQ>
-int launch_gae_reg_l(hipStream_t st, const GaeParams& p, bool vtrace, int lmax = 4) {
-  constexpr int SEG = 256 / CQ;
-  const int need = (p.T + SEG - 1) / SEG;  // rows per lane if one time tile covered all of T
-  if (need <= 1 || lmax == 1) return launch_gae_reg<CQ, 1>(st, p, vtrace);
-  if (need <= 2 || lmax == 2) return launch_gae_reg<CQ, 2>(st, p, vtrace);
-  return launch_gae_reg<CQ, 4>(st, p, vtrace);  // longer T: several time tiles, carry in registers
+int launch_gae_reg_l(hipStream_t st, const GaeParams& p, bool vtrace, const GaePlan& pl) {
+  if (pl.L == 1) return launch_gae_reg<CQ, 1>(st, p, vtrace, pl);
+  if (pl.L == 2) return launch_gae_reg<CQ, 2>(st, p, vtrace, pl);
+  return launch_gae_reg<CQ, 4>(st, p, vtrace, pl);
 }
 
 inline bool aligned_to(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
@@ -468,6 +520,15 @@ extern "C" long srl_gae_scan_workspace_bytes(int B, int Nc) {
   return (long)(16 + 24 * gae_max_grid(B, Nc));
 }
 
+extern "C" int srl_gae_scan_plan(int T, int B, int Nc, int aligned, int vtrace, int tensors, int32_t* out) {
+  SRL_CHECK_ARG(T >= 0 && B >= 0 && Nc >= 1, "T, B >= 0 and Nc >= 1 required");
+  SRL_CHECK_ARG(out, "null out");
+  const GaePlan pl = gae_plan(T, B, Nc, aligned != 0, vtrace != 0, tensors != 0);
+  out[0] = pl.kernel; out[1] = pl.width; out[2] = pl.L; out[3] = pl.TT; out[4] = pl.tiles;
+  out[5] = (int32_t)pl.grid; out[6] = pl.ws;
+  return 0;
+}
+
 extern "C" int srl_gae_scan(void* stream, const float* reward, const float* value, const uint8_t* done,
                             const uint8_t* truncated, const uint8_t* on_reset, const float* imp_ratio,
                             const float* gamma_t, const float* lambda_t, int T, int B, int Nc, double gamma,
@@ -476,33 +537,29 @@ extern "C" int srl_gae_scan(void* stream, const float* reward, const float* valu
   SRL_CHECK_ARG(T >= 0 && B >= 0 && Nc >= 1, "T, B >= 0 and Nc >= 1 required");
   hipStream_t st = (hipStream_t)stream;
   SRL_CHECK_ARG(!workspace || aligned_to(workspace, 8), "workspace must be 8-byte aligned");
-  // The ticketed reduction pays a release fence per workgroup (its own stores must have landed before the ticket): worth it
-  // where the zeroing launch is a large part of the call (<= 768 workgroups), not on grids that stream for hundreds of
-  // microseconds (measured at 2^20 environments: 547 us against 505 with the memset + atomics)
-  if ((long)B * Nc >= 98304) workspace = nullptr;
+  const bool aligned = aligned_to(reward, 16) && aligned_to(value, 16) && aligned_to(adv, 16) && aligned_to(ret, 16) &&
+                       aligned_to(done, 4) && aligned_to(truncated, 4) && aligned_to(on_reset, 4) &&
+                       (!imp_ratio || aligned_to(imp_ratio, 16));
+  const bool vt = imp_ratio != nullptr;
+  const GaePlan pl = gae_plan(T, B, Nc, aligned, vt, gamma_t != nullptr || lambda_t != nullptr);
+  if (!pl.ws) workspace = nullptr;
   if (stats && (!workspace || T == 0 || B == 0)) SRL_HIP_TRY(hipMemsetAsync(stats, 0, 3 * sizeof(double), st));
-  if (T == 0 || B == 0) return 0;  // empty batch: nothing to scan (tensors may be null)
+  if (pl.grid == 0) return 0;  // empty batch: nothing to scan (tensors may be null)
   SRL_CHECK_ARG(reward && value && done && truncated && on_reset && adv && ret, "null tensor");
   GaeParams p{reward, value, done, truncated, on_reset, imp_ratio, gamma_t, lambda_t, adv, ret, stats, T, B, Nc, 0,
               gamma,  lambda, rho,  c, stats ? workspace : nullptr};
-  const long ncols = (long)B * Nc;
-  const bool quads = Nc == 1 && B % 4 == 0 && !gamma_t && !lambda_t && aligned_to(reward, 16) && aligned_to(value, 16) &&
-                     aligned_to(adv, 16) && aligned_to(ret, 16) && aligned_to(done, 4) &&
-                     aligned_to(truncated, 4) && aligned_to(on_reset, 4) && (!imp_ratio || aligned_to(imp_ratio, 16));
-  if (quads) {
-    const bool vt = imp_ratio != nullptr;
-    // Row width per workgroup grows with the batch (measured on MI355X, scripts/gae_sweep.py): wide
-    // rows stream best (1 KiB = 8 whole cache lines per wave load) but need B/256 >> 256 workgroups.
-    if (ncols < 2048) return launch_gae_reg_l<4>(st, p, vt);
-    if (ncols < 16384) return launch_gae_reg_l<8>(st, p, vt);
-    if (ncols < 98304) return launch_gae_reg_l<32>(st, p, vt);
-    if (ncols < 393216) return launch_gae_reg_l<64>(st, p, vt);
-    if (ncols < 786432) return launch_gae_reg_l<128>(st, p, vt, 2);
-    return launch_gae_reg_l<256>(st, p, vt, 2);  // one lane per column quad, pure streaming over T
+  if (pl.kernel == 0) {
+    switch (pl.width) {
+      case 4: return launch_gae_reg_l<4>(st, p, vt, pl);
+      case 8: return launch_gae_reg_l<8>(st, p, vt, pl);
+      case 32: return launch_gae_reg_l<32>(st, p, vt, pl);
+      case 64: return launch_gae_reg_l<64>(st, p, vt, pl);
+      case 128: return launch_gae_reg_l<128>(st, p, vt, pl);
+      default: return launch_gae_reg_l<256>(st, p, vt, pl);
+    }
   }
-  // narrow tiles while the grid would not cover the chip; wide (256-byte rows) once it does
-  if (ncols >= 64L * 512) return launch_gae<64>(st, p, imp_ratio != nullptr);
-  return launch_gae<16>(st, p, imp_ratio != nullptr);
+  if (pl.width == 64) return launch_gae<64>(st, p, vt, pl);
+  return launch_gae<16>(st, p, vt, pl);
 }
 
 extern "C" int srl_masked_stats(void* stream, const float* x, const uint8_t* mask, int mask_invert, long n,

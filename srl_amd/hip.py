@@ -249,6 +249,16 @@ def gae_scan_workspace(B, Nc, device) -> torch.Tensor:
     return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device)
 
 
+def gae_scan_plan(T, B, Nc=1, aligned=True, vtrace=False, tensors=False) -> dict:
+    """The tiling ``gae_scan`` would run a ``[T, B, Nc]`` call on (``srl_gae_scan_plan``: the function the launch uses; needs the
+    library, not a GPU): kernel (0 register-resident / 1 LDS-staged), width (column quads / columns per workgroup), L (time rows
+    per lane; 0 for the LDS kernel), TT (rows of a time tile), tiles, grid, workspace (whether one would be used)."""
+    out = (c_int32 * 7)()
+    _check(lib().srl_gae_scan_plan(int(T), int(B), int(Nc), int(bool(aligned)), int(bool(vtrace)), int(bool(tensors)), out),
+           "srl_gae_scan_plan")
+    return dict(zip(("kernel", "width", "L", "TT", "tiles", "grid", "workspace"), (int(v) for v in out)))
+
+
 def gae_scan(reward, value, done, truncated, on_reset, gamma, lmbda, adv, ret, stats=None, imp_ratio=None, rho=1.0,
              c=1.0, workspace=None):
     """reward [>=T,B,Nc] f32, value/done/truncated/on_reset [T+1,B,*]; writes adv/ret rows [0,T); stats f64[3].

@@ -63,6 +63,7 @@ def test_header_counts_and_type_map():
     assert cabi.prototypes["srl_last_error"] == (ctypes.c_char_p, [])
     assert cabi.prototypes["srl_device_info"] == (ctypes.c_int, [vp, vp, ctypes.c_char_p, ctypes.c_int])
     assert cabi.prototypes["srl_gae_scan_workspace_bytes"] == (ctypes.c_long, [ctypes.c_int, ctypes.c_int])
+    assert cabi.prototypes["srl_gae_scan_plan"] == (ctypes.c_int, [ctypes.c_int] * 6 + [vp])      # int32_t* out
     assert cabi.prototypes["srl_gemm"] == (ctypes.c_int, [vp, P(cabi.struct("srl_gemm_desc"))])
     assert cabi.prototypes["srl_step_plan_create"] == (ctypes.c_int, [vp, vp])                       # void**
     assert cabi.prototypes["srl_accumulate_n"][1] == [vp, vp, vp, ctypes.c_int32, ctypes.c_int64]    # const float* const*
