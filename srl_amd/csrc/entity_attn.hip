@@ -21,6 +21,7 @@
 // product and for its transpose) and the parameter gradients are summed there over the workgroup's tiles and added to global
 // memory once, with float atomics -- when they fit beside one row's intermediates in 160 KiB; otherwise the parameters are read
 // from global memory and / or every tile adds its sums with atomics.
+#include "layer_norm.h"
 #include "srl_common.h"
 
 namespace {
@@ -231,18 +232,18 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
       mu /= (float)len;
       float var = 0.0f;
       for (int j = 0; j < len; ++j) { const float t = x[j] - mu; var = fmaf(t, t, var); }
-      const float rs = 1.0f / sqrtf(var / (float)len + 1e-5f);
+      const float rs = ln_rstd(var, len);
       for (int j = 0; j < len; ++j) {
-        const float h = (x[j] - mu) * rs;
+        const float h = ln_xhat(x[j], mu, rs);
         if (BWD) xh_[r * in_row + off + j] = h;
-        x[j] = fmaf(h, w[j], b[j]);
+        x[j] = ln_affine(h, w[j], b[j]);
       }
     }
     for (int i = tid; i < nv * E; i += NT) {
       const int r = i / E, e = i % E;
       float ms = 0.0f;
       for (int j = 0; j < E; ++j) ms += m_(r)[j];
-      c_(r)[e] = m_(r)[e] / (ms + 1e-5f);
+      c_(r)[e] = m_(r)[e] / (ms + 1e-5f);   // the masked mean's guard against an empty set, not LayerNorm's eps
     }
     __syncthreads();
 
@@ -280,10 +281,10 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
       mu /= (float)D;
       float var = 0.0f;
       for (int c = 0; c < D; ++c) { const float t = x[c] - mu; var = fmaf(t, t, var); }
-      const float rs = 1.0f / sqrtf(var / (float)D + 1e-5f);
+      const float rs = ln_rstd(var, D);
       mean_(r)[e] = mu;
       rstd_(r)[e] = rs;
-      for (int c = 0; c < D; ++c) xn_[u * DP + c] = fmaf((x[c] - mu) * rs, w[c], b[c]);
+      for (int c = 0; c < D; ++c) xn_[u * DP + c] = ln_affine(ln_xhat(x[c], mu, rs), w[c], b[c]);
     }
     __syncthreads();
 
@@ -494,9 +495,7 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
       for (int r = 0; r < nv; ++r)
         for (int e = 0; e < E; ++e) {
           const int u = r * E + e;
-          const float g = q_[u * DP + c];
-          gw = fmaf(g, (emb_[u * DP + c] - mean_(r)[e]) * rstd_(r)[e], gw);
-          gb += g;
+          ln_bwd_param_sums(q_[u * DP + c], ln_xhat(emb_[u * DP + c], mean_(r)[e], rstd_(r)[e]), gw, gb);
         }
       gadd(SRL_EATTN_PRE_W, c, gw); gadd(SRL_EATTN_PRE_B, c, gb);
     }
@@ -505,16 +504,11 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
       const float* w = vecp(SRL_EATTN_PRE_W);
       const float mu = mean_(r)[e], rs = rstd_(r)[e];
       float s1 = 0.0f, s2 = 0.0f;
-      for (int c = 0; c < D; ++c) {
-        const float g = q_[u * DP + c] * w[c];
-        s1 += g;
-        s2 = fmaf(g, (emb_[u * DP + c] - mu) * rs, s2);
-      }
+      for (int c = 0; c < D; ++c) ln_bwd_row_sums(q_[u * DP + c], w[c], ln_xhat(emb_[u * DP + c], mu, rs), s1, s2);
       s1 /= (float)D; s2 /= (float)D;
       for (int c = 0; c < D; ++c) {
         const float x = emb_[u * DP + c];
-        const float g = q_[u * DP + c] * w[c];
-        k_[u * DP + c] = x > 0.0f ? rs * (g - s1 - (x - mu) * rs * s2) : 0.0f;
+        k_[u * DP + c] = x > 0.0f ? ln_dx(q_[u * DP + c], w[c], ln_xhat(x, mu, rs), s1, s2, rs) : 0.0f;
       }
     }
     __syncthreads();
@@ -586,9 +580,7 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
     for (int j = tid; j < S; j += NT) {
       float gw = 0.0f, gb = 0.0f;
       for (int r = 0; r < nv; ++r) {
-        const float g = a_[r * in_row + j];
-        gw = fmaf(g, xh_[r * in_row + j], gw);
-        gb += g;
+        ln_bwd_param_sums(a_[r * in_row + j], xh_[r * in_row + j], gw, gb);
       }
       gadd(SRL_EATTN_LN_SELF_W, j, gw); gadd(SRL_EATTN_LN_SELF_B, j, gb);
     }
@@ -599,8 +591,7 @@ __global__ void __launch_bounds__(kThreads) entity_attn_kernel(const EaArgs A) {
         for (int r = 0; r < nv; ++r)
           for (int le = 0; le < cnt; ++le) {
             const int o = r * in_row + ko + le * f + j;
-            gw = fmaf(a_[o], xh_[o], gw);
-            gb += a_[o];
+            ln_bwd_param_sums(a_[o], xh_[o], gw, gb);
           }
         gadd(SRL_EATTN_LN_KEY_W + k, j, gw); gadd(SRL_EATTN_LN_KEY_B + k, j, gb);
       }

@@ -182,17 +182,6 @@ __device__ __forceinline__ uint32_t sign_words(const float (&v)[16], int lane31,
   (sign_rows<R>(v, lane31, wv), ...);
   return wv;
 }
-__device__ __forceinline__ void absmax_commit(float* dst, float mx) {  // mx >= 0: unsigned order = float order
-  // One atomic per wavefront to ONE address is a serial chain through one L2 channel (~10 ns each): 51 000 wavefronts of a
-  // strided data gradient spent 0.2 ms of its 0.67 there.  The slot only grows, so a wavefront whose maximum does not exceed
-  // what a (relaxed, possibly stale -- staleness only means a superfluous atomic) load returns has nothing to add: after the
-  // first few tiles almost every wavefront leaves with the load alone.
-  mx = wave_allmax(mx);
-  if ((threadIdx.x & 63) == 0 && mx > 0.f) {
-    unsigned int* d = reinterpret_cast<unsigned int*>(dst);
-    if (__float_as_uint(mx) > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, __float_as_uint(mx));
-  }
-}
 
 // Odometer over the k-steps of a forward convolution, slowest digit first: 128-byte line of the pixel (two 16-channel
 // blocks), parity class of the tap (kh % S, kw % S), the taps of the class, the blocks of the line.  Taps that read the
@@ -862,7 +851,7 @@ __device__ __forceinline__ void gemm_epilogue(GemmArgs& g, f32x16 (&acc)[TM][TN]
     if (interior) blocks(std::true_type{});
     else blocks(std::false_type{});
   }
-  if (g.out_absmax) absmax_commit(g.out_absmax, amx);
+  if (g.out_absmax) wave_absmax_fold(amx, g.out_absmax);
 }
 
 // GEN: the dense operands may need the element-wise (unaligned / ragged leading dimension) staging path.  The

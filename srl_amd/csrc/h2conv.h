@@ -648,14 +648,7 @@ __global__ __launch_bounds__(512, 2) void h2conv_kernel(H2ConvArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < NEP; ++k) epi_piece(k, pacc, pm);
-  {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    if (lane == 0) {
-      const float cur = __hip_atomic_load(a.out_absmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (amax > cur) atomicMax(reinterpret_cast<int*>(a.out_absmax), __float_as_int(amax));
-    }
-  }
+  wave_absmax_fold(amax, a.out_absmax);
 }
 
 template <int ID, int NSLOT = 2>

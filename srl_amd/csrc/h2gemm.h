@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srl_common.h"
+
 namespace srlh2 {
 
 typedef _Float16 h2_f16x8 __attribute__((ext_vector_type(8)));
@@ -638,14 +640,7 @@ __global__ __launch_bounds__(512, 2) void h2gemm_kernel(H2Args g) {
       }
     }
   }
-  if (g.out_absmax) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    if (lane == 0) {
-      const float cur = __hip_atomic_load(g.out_absmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (amax > cur) atomicMax(reinterpret_cast<int*>(g.out_absmax), __float_as_int(amax));  // non-negative floats order as ints
-    }
-  }
+  if (g.out_absmax) wave_absmax_fold(amax, g.out_absmax);
 }
 
 template <int NCB, int XMODE, int S, bool KSPLIT = true>

@@ -384,15 +384,7 @@ __global__ __launch_bounds__(512, 2) void h2gemmp_kernel(H2Args g) {
     epilogue(k);
     zero_acc();
   }
-  if (g.out_absmax) {
-    amax = fmaxf(amax, amax_raw * inv);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    if (lane == 0) {
-      const float cur = __hip_atomic_load(g.out_absmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (amax > cur) atomicMax(reinterpret_cast<int*>(g.out_absmax), __float_as_int(amax));  // non-negative floats order as ints
-    }
-  }
+  if (g.out_absmax) wave_absmax_fold(fmaxf(amax, amax_raw * inv), g.out_absmax);
 }
 
 inline int h2gemmp_launch(hipStream_t st, H2Args a, int ncu = 256) {

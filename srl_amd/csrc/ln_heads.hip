@@ -9,13 +9,13 @@
 // forms them again from x and the stored (mean, rstd).  Forward: x is read once (33.5 MB).  Backward: x read, dx written, and
 // every parameter gradient of the LayerNorm and the heads summed in registers over the rows a wavefront walks, met in LDS per
 // workgroup, one atomic per parameter and workgroup at the end.
+#include "layer_norm.h"
 #include "srl_common.h"
 
 #include "../../include/srl_hip.h"
 
 namespace {
 
-constexpr float kEps = 1e-5f;       // nn.LayerNorm default
 constexpr int kMaxOut = SRL_LN_HEADS_MAX_OUT;   // outputs of all heads together at most
 constexpr int kWaves = 8;           // wavefronts per workgroup
 constexpr int kDbGroups = 8;        // workgroups that form the heads' bias gradients
@@ -153,13 +153,13 @@ __global__ __launch_bounds__(64 * kWaves) void ln_heads_fwd_kernel(LhArgs a) {
       x[k] -= mean;
       q = fmaf(x[k], x[k], q);
     }
-    const float rstd = rsqrtf(allsum(q) / (float)D + kEps);
+    const float rstd = ln_rstd(allsum(q), D);
     float p[kMaxOut];
 #pragma unroll
     for (int o = 0; o < kMaxOut; ++o) p[o] = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-      const float f = fmaf(x[k] * rstd, g[k], be[k]);
+      const float f = ln_affine(x[k] * rstd, g[k], be[k]);   // x holds x - mean
 #pragma unroll
       for (int o = 0; o < kMaxOut; ++o) p[o] = fmaf(f, w[o][k], p[o]);
     }
@@ -214,19 +214,15 @@ __global__ __launch_bounds__(64 * kWaves) void ln_heads_bwd_kernel(LhArgs a) {
     float m1 = 0.f, m2 = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-      xh[k] = (x[k] - mean) * rstd;
-      const float f = fmaf(xh[k], g[k], be[k]);
+      xh[k] = ln_xhat(x[k], mean, rstd);
+      const float f = ln_affine(xh[k], g[k], be[k]);
       float df = 0.f;
 #pragma unroll
       for (int o = 0; o < kMaxOut; ++o) {
         df = fmaf(dyv[o], w[o][k], df);
         accw[o][k] = fmaf(dyv[o], f, accw[o][k]);
       }
-      accb[k] += df;
-      accg[k] = fmaf(df, xh[k], accg[k]);
-      gg[k] = df * g[k];
-      m1 += gg[k];
-      m2 = fmaf(gg[k], xh[k], m2);
+      gg[k] = ln_bwd_accumulate(df, g[k], xh[k], m1, m2, accg[k], accb[k]);
     }
     m1 = allsum(m1) / (float)D;
     m2 = allsum(m2) / (float)D;
@@ -234,7 +230,7 @@ __global__ __launch_bounds__(64 * kWaves) void ln_heads_bwd_kernel(LhArgs a) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const float der = a.in_act == 1 ? (x[k] > 0.f ? 1.f : 0.f) : (a.in_act == 2 ? 1.f - x[k] * x[k] : 1.f);
-      dx[k] = rstd * (gg[k] - m1 - xh[k] * m2) * der;
+      dx[k] = ln_dx(gg[k], xh[k], m1, m2, rstd) * der;
       amax = fmaxf(amax, fabsf(dx[k]));
     }
     store_row<NV>(a.dx + row * a.lddx, lane, dx);

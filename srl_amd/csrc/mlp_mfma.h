@@ -119,7 +119,7 @@ __device__ __forceinline__ void mm_ln_stats(const float (&v)[kMB][16], int dim, 
       q += (32 * ib + mm_ch(e, hb) < dim) ? d * d : 0.f;
     }
   q += __shfl_xor(q, 32);
-  rstd = rsqrtf(q / (float)dim + kLnEps);
+  rstd = ln_rstd(q, dim);
 }
 
 // stage the chain's parameters into LDS in operand order (every thread of the workgroup); ONE copy serves both directions
@@ -163,7 +163,7 @@ __device__ __forceinline__ void mm_layer_fwd(const MArgs& m, const float* sm, in
         }
         const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cur[ib][4 * j + q] = fmaf((cur[ib][4 * j + q] - mean) * rstd, gv[q], bv[q]);
+        for (int q = 0; q < 4; ++q) cur[ib][4 * j + q] = ln_affine(ln_xhat(cur[ib][4 * j + q], mean, rstd), gv[q], bv[q]);
       }
     return;
   }
@@ -411,12 +411,10 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
             for (int q = 0; q < 4; ++q) {
               const int e = 4 * j + q;
               const bool in = 32 * ib + mm_ch(e, hb) < L.in;
-              const float xh = in ? (xin[ib][e] - mean) * rstd : 0.f;
+              const float xh = in ? ln_xhat(xin[ib][e], mean, rstd) : 0.f;
               xin[ib][e] = in ? xin[ib][e] : 0.f;
               gyx[e] = d[ib][e] * xh;
-              gg[ib][e] = d[ib][e] * gv[q];
-              m1 += gg[ib][e];
-              m2 = fmaf(gg[ib][e], xh, m2);
+              gg[ib][e] = ln_bwd_row_sums(d[ib][e], gv[q], xh, m1, m2);
             }
           }
           if (ib < nb) {
@@ -436,8 +434,8 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void mlp_bwd_mfma_kernel(MArgs m
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
               const bool in = 32 * ib + mm_ch(e, hb) < L.in;
-              const float xh = (xin[ib][e] - mean) * rstd;
-              d[ib][e] = in ? rstd * (gg[ib][e] - m1 - xh * m2) * act_der(xin[ib][e], pact) : 0.f;
+              const float xh = ln_xhat(xin[ib][e], mean, rstd);
+              d[ib][e] = in ? ln_dx(gg[ib][e], xh, m1, m2, rstd) * act_der(xin[ib][e], pact) : 0.f;
             }
         }
       }

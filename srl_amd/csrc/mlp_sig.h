@@ -148,7 +148,7 @@ __device__ __forceinline__ void sx_ln_stats(const float (&v)[kMB][16], int hb, f
         q += sx_valid<DIM>(ib, e, hb) ? d * d : 0.f;
       }
   q += __shfl_xor(q, 32);
-  rstd = rsqrtf(q / (float)DIM + kLnEps);
+  rstd = ln_rstd(q, DIM);
 }
 
 // LayerNorm I on the rows in `cur`; gt: the layer's gamma | beta tables in LDS
@@ -166,7 +166,7 @@ __device__ __forceinline__ void sx_ln_fwd(const float* gt, float (&cur)[kMB][16]
         const float4 b4 = *reinterpret_cast<const float4*>(gt + nb * 32 + 32 * ib + 8 * j + 4 * hb);
         const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cur[ib][4 * j + q] = fmaf((cur[ib][4 * j + q] - mean) * rstd, gv[q], bv[q]);
+        for (int q = 0; q < 4; ++q) cur[ib][4 * j + q] = ln_affine(ln_xhat(cur[ib][4 * j + q], mean, rstd), gv[q], bv[q]);
       }
 }
 
@@ -237,12 +237,10 @@ __device__ __forceinline__ void sx_ln_bwd(const float* gt, float* fT, float* pgs
           for (int q = 0; q < 4; ++q) {
             const int e = 4 * j + q;
             const bool ok = sx_valid<in>(ib, e, hb);
-            const float xh = ok ? (xin[ib][e] - mean) * rstd : 0.f;
+            const float xh = ok ? ln_xhat(xin[ib][e], mean, rstd) : 0.f;
             xin[ib][e] = ok ? xin[ib][e] : 0.f;
             gyx[e] = d[ib][e] * xh;
-            gg[ib][e] = d[ib][e] * gv[q];
-            m1 += gg[ib][e];
-            m2 = fmaf(gg[ib][e], xh, m2);
+            gg[ib][e] = ln_bwd_row_sums(d[ib][e], gv[q], xh, m1, m2);
           }
         }
       sx_half_write<mm_ne(in, ib)>(fT, r, hb, gyx);                 // dgamma's terms
@@ -260,8 +258,8 @@ __device__ __forceinline__ void sx_ln_bwd(const float* gt, float* fT, float* pgs
 #pragma unroll
       for (int e = 0; e < 16; ++e)
         if (e < mm_ne(in, ib)) {
-          const float xh = (xin[ib][e] - mean) * rstd;
-          d[ib][e] = sx_valid<in>(ib, e, hb) ? rstd * (gg[ib][e] - m1 - xh * m2) * act_der(xin[ib][e], pact) : 0.f;
+          const float xh = ln_xhat(xin[ib][e], mean, rstd);
+          d[ib][e] = sx_valid<in>(ib, e, hb) ? ln_dx(gg[ib][e], xh, m1, m2, rstd) * act_der(xin[ib][e], pact) : 0.f;
         }
   }
 }

@@ -12,6 +12,7 @@
 // inside a workgroup; across workgroups the atomics' order is not fixed, like the LayerNorm backward kernels' already.
 // Reference: the nn.Sequential of modules/utils.py:154-161 (mlp: LayerNorm -> Linear -> activation ...) and the heads of
 // actor_critic_policy.py:92-107, as one kernel per direction.
+#include "layer_norm.h"
 #include "srl_common.h"
 
 #include "../../include/srl_hip.h"
@@ -21,7 +22,6 @@ namespace {
 constexpr int kRB = 16;     // rows per workgroup (16 lanes per row)
 constexpr int kMaxD = 128;  // widest layer
 constexpr int kLd = kMaxD + 1;
-constexpr float kLnEps = 1e-5f;  // nn.LayerNorm default
 constexpr int kMaxP = 12288;     // parameter-gradient floats a backward workgroup can keep in LDS (48 KB)
 constexpr int kBwdGroups = 512;  // backward workgroups at most: each walks its 16-row blocks and flushes its sums once
 
@@ -96,8 +96,8 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(Args a) {
         const float d = cur[r][k] - mean;
         q = fmaf(d, d, q);
       }
-      const float rstd = rsqrtf(sum16(q) / (float)L.in + kLnEps);
-      for (int k = c; k < L.in; k += 16) cur[r][k] = (cur[r][k] - mean) * rstd * L.w[k] + L.b[k];
+      const float rstd = ln_rstd(sum16(q), L.in);
+      for (int k = c; k < L.in; k += 16) cur[r][k] = ln_affine(ln_xhat(cur[r][k], mean, rstd), L.w[k], L.b[k]);
       dim = L.in;
     } else {
       __syncthreads();  // the previous Linear's readers of Wt are done
@@ -211,15 +211,14 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(Args a) {
           const float d = xin[r][k] - mean;
           q = fmaf(d, d, q);
         }
-        const float rstd = rsqrtf(sum16(q) / (float)L.in + kLnEps);
+        const float rstd = ln_rstd(sum16(q), L.in);
         __syncthreads();  // Ws (scratch) is free
         float m1 = 0.f, m2 = 0.f;
         for (int k = c; k < L.in; k += 16) {
-          const float xh = (xin[r][k] - mean) * rstd, gy = g[r][k], gg = gy * L.w[k];
-          Ws[r * kLd + k] = gy * xh;
+          const float xh = ln_xhat(xin[r][k], mean, rstd), gy = g[r][k];
+          Ws[r * kLd + k] = gy * xh;   // dgamma's and dbeta's terms: the columns are summed over the block's rows below
           Ws[(kRB + r) * kLd + k] = gy;
-          m1 += gg;
-          m2 = fmaf(gg, xh, m2);
+          ln_bwd_row_sums(gy, L.w[k], xh, m1, m2);
         }
         m1 = sum16(m1) / (float)L.in;
         m2 = sum16(m2) / (float)L.in;
@@ -240,10 +239,8 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(Args a) {
           }
         }
         if (i > 0)
-          for (int k = c; k < L.in; k += 16) {
-            const float xh = (xin[r][k] - mean) * rstd;
-            g[r][k] = rstd * (g[r][k] * L.w[k] - m1 - xh * m2) * act_der(xin[r][k], pact);
-          }
+          for (int k = c; k < L.in; k += 16)
+            g[r][k] = ln_dx(g[r][k], L.w[k], ln_xhat(xin[r][k], mean, rstd), m1, m2, rstd) * act_der(xin[r][k], pact);
       }
     }
     __syncthreads();  // the next block's loads overwrite g / xin, which layer 0's sums read across rows

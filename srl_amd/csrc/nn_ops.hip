@@ -3,10 +3,9 @@
 // the gather form of col2im, column sums, strided copies.
 #include "srl_common.h"
 #include "gemm_bf16x3.h"
+#include "layer_norm.h"
 
 namespace {
-
-constexpr float kLnEps = 1e-5f;  // nn.LayerNorm default, used everywhere in the reference
 
 // ---- LayerNorm over the last dim: one wavefront per row ------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* x, long ldx, const float* gamma,
@@ -24,9 +23,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* x, long
     const float d = xr[j] - mean;
     q += d * d;
   }
-  const float rstd = rsqrtf(wave_allsum(q) / (float)D + kLnEps);
+  const float rstd = ln_rstd(wave_allsum(q), D);
   float* yr = y + row * ldy;
-  for (int j = lane; j < D; j += 64) yr[j] = (xr[j] - mean) * rstd * gamma[j] + beta[j];
+  for (int j = lane; j < D; j += 64) yr[j] = ln_affine(ln_xhat(xr[j], mean, rstd), gamma[j], beta[j]);
   if (lane == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
@@ -55,11 +54,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_small_kernel(const float* x
   if (ok) v = *reinterpret_cast<const float4*>(x + row * ldx + sl * 4);
   const float mean = sub_allsum<LPR>(v.x + v.y + v.z + v.w) / (float)D;
   const float4 d = ok ? make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float rstd = rsqrtf(sub_allsum<LPR>(d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w) / (float)D + kLnEps);
+  const float rstd = ln_rstd(sub_allsum<LPR>(d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w), D);
   if (!ok) return;
   const float4 g = *reinterpret_cast<const float4*>(gamma + sl * 4), b = *reinterpret_cast<const float4*>(beta + sl * 4);
   *reinterpret_cast<float4*>(y + row * ldy + sl * 4) =
-      make_float4(d.x * rstd * g.x + b.x, d.y * rstd * g.y + b.y, d.z * rstd * g.z + b.z, d.w * rstd * g.w + b.w);
+      make_float4(ln_affine(ln_xhat(v.x, mean, rstd), g.x, b.x), ln_affine(ln_xhat(v.y, mean, rstd), g.y, b.y),
+                  ln_affine(ln_xhat(v.z, mean, rstd), g.z, b.z), ln_affine(ln_xhat(v.w, mean, rstd), g.w, b.w));
   if (sl == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
@@ -98,12 +98,8 @@ __global__ __launch_bounds__(1024) void layernorm_bwd_small_kernel(const float* 
     float s1 = 0.f, s2 = 0.f, xh[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      xh[e] = ok ? (xv[e] - mu) * rs : 0.f;
-      const float g = dv[e] * gv[e];
-      s1 += g;
-      s2 += g * xh[e];
-      pg[e] += dv[e] * xh[e];
-      pb[e] += dv[e];
+      xh[e] = ok ? ln_xhat(xv[e], mu, rs) : 0.f;
+      ln_bwd_accumulate(dv[e], gv[e], xh[e], s1, s2, pg[e], pb[e]);
     }
     if (dx) {
       const float m1 = sub_allsum<LPR>(s1) / (float)D, m2 = sub_allsum<LPR>(s2) / (float)D;
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(1024) void layernorm_bwd_small_kernel(const float* 
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          o[e] = rs * (dv[e] * gv[e] - m1 - xh[e] * m2);
+          o[e] = ln_dx(dv[e], gv[e], xh[e], m1, m2, rs);
           if (dact) o[e] *= act_grad_from_output(xv[e], dact);  // x is the activation output that fed this LayerNorm
         }
         *reinterpret_cast<float4*>(dx + row * lddx + sl * 4) = make_float4(o[0], o[1], o[2], o[3]);
@@ -177,12 +173,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* dy, lon
     for (int v = 0; v < LN_MAXV; ++v) {
       const int j = lane + v * 64;
       if (j < D) {
-        const float xh = (xr[j] - mu) * rs, d = dyr[j];
-        const float g = d * gamma[j];
-        s1 += g;
-        s2 += g * xh;
-        pg[v] += d * xh;
-        pb[v] += d;
+        ln_bwd_accumulate(dyr[j], gamma[j], ln_xhat(xr[j], mu, rs), s1, s2, pg[v], pb[v]);
       }
     }
     if (dx) {
@@ -193,8 +184,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* dy, lon
         const int j = lane + v * 64;
         if (j < D) {
           const float xv = xr[j];
-          const float xh = (xv - mu) * rs;
-          float o = rs * (dyr[j] * gamma[j] - m1 - xh * m2);
+          float o = ln_dx(dyr[j], gamma[j], ln_xhat(xv, mu, rs), m1, m2, rs);
           if (dact) o *= act_grad_from_output(xv, dact);  // x is the activation output that fed this LayerNorm
           dxr[j] = o;
           amx = fmaxf(amx, fabsf(o));
@@ -202,13 +192,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* dy, lon
       }
     }
   }
-  if (dx_absmax) {  // the slot only grows: load first, atomic only when this wavefront has something to add (gemm_core.h)
-    amx = wave_allmax(amx);
-    if (lane == 0 && amx > 0.f) {
-      unsigned int* d = reinterpret_cast<unsigned int*>(dx_absmax);
-      if (__float_as_uint(amx) > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, __float_as_uint(amx));
-    }
-  }
+  if (dx_absmax) wave_absmax_fold(amx, dx_absmax);
   // combine the 4 wavefronts through LDS, then one atomic per column per workgroup
   __shared__ float sg[4][64 * LN_MAXV / 4 + 1];  // processed in 4 passes of LN_MAXV/4 values to bound LDS
   for (int pass = 0; pass < 4; ++pass) {
@@ -266,13 +250,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_vec_kernel(const float* dy,
       float* pga = reinterpret_cast<float*>(&pg[v]);
       float* pba = reinterpret_cast<float*>(&pb[v]);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float xh = (xa[q] - mu) * rs, g = da[q] * ga[q];
-        s1 += g;
-        s2 += g * xh;
-        pga[q] += da[q] * xh;
-        pba[q] += da[q];
-      }
+      for (int q = 0; q < 4; ++q) ln_bwd_accumulate(da[q], ga[q], ln_xhat(xa[q], mu, rs), s1, s2, pga[q], pba[q]);
     }
     if (dx) {
       const float m1 = wave_allsum(s1) / (float)D, m2 = wave_allsum(s2) / (float)D;
@@ -283,8 +261,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_vec_kernel(const float* dy,
         float o[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const float xh = (xa[q] - mu) * rs;
-          o[q] = rs * (da[q] * ga[q] - m1 - xh * m2);
+          o[q] = ln_dx(da[q], ga[q], ln_xhat(xa[q], mu, rs), m1, m2, rs);
           if (dact) o[q] *= act_grad_from_output(xa[q], dact);
           amx = fmaxf(amx, fabsf(o[q]));
         }
@@ -292,13 +269,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_vec_kernel(const float* dy,
       }
     }
   }
-  if (dx_absmax) {
-    amx = wave_allmax(amx);
-    if (lane == 0 && amx > 0.f) {
-      unsigned int* d = reinterpret_cast<unsigned int*>(dx_absmax);
-      if (__float_as_uint(amx) > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, __float_as_uint(amx));
-    }
-  }
+  if (dx_absmax) wave_absmax_fold(amx, dx_absmax);
   // the 8 wavefronts' column sums fold in LDS, then one atomic per column and workgroup (at most 256 workgroups: the 2 D float
   // atomics of each were the kernel's floor at 1024 workgroups -- 1 M atomics, ~36 us)
   __shared__ float sg[2][D];
@@ -334,11 +305,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wide_dx_kernel(const float*
   const float* dyr = dy + row * lddy;
   const float mu = mean[row], rs = rstd[row];
   float s1 = 0.f, s2 = 0.f;
-  for (int j = threadIdx.x; j < D; j += 256) {
-    const float g = dyr[j] * gamma[j];
-    s1 += g;
-    s2 += g * (xr[j] - mu) * rs;
-  }
+  for (int j = threadIdx.x; j < D; j += 256) ln_bwd_row_sums(dyr[j], gamma[j], ln_xhat(xr[j], mu, rs), s1, s2);
   s1 = wave_allsum(s1);
   s2 = wave_allsum(s2);
   if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s1, red[1][threadIdx.x >> 6] = s2;
@@ -348,8 +315,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wide_dx_kernel(const float*
   float* dxr = dx + row * lddx;
   for (int j = threadIdx.x; j < D; j += 256) {
     const float xv = xr[j];
-    const float xh = (xv - mu) * rs;
-    float o = rs * (dyr[j] * gamma[j] - m1 - xh * m2);
+    float o = ln_dx(dyr[j], gamma[j], ln_xhat(xv, mu, rs), m1, m2, rs);
     if (dact) o *= act_grad_from_output(xv, dact);
     dxr[j] = o;
   }
@@ -364,11 +330,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wide_param_kernel(const flo
   const long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
   if (j >= D) return;
   float pg = 0.f, pb = 0.f;
-  for (long row = r0; row < r1; ++row) {
-    const float d = dy[row * lddy + j];
-    pg += d * (x[row * ldx + j] - mean[row]) * rstd[row];
-    pb += d;
-  }
+  for (long row = r0; row < r1; ++row)
+    ln_bwd_param_sums(dy[row * lddy + j], ln_xhat(x[row * ldx + j], mean[row], rstd[row]), pg, pb);
   atomicAdd(dgamma + j, pg);
   atomicAdd(dbeta + j, pb);
 }
@@ -404,7 +367,7 @@ __global__ __launch_bounds__(256) void obs_ln_stats_kernel(const void* obs, long
     double var = acc[1] / D - mu * mu;
     var = var > 0.0 ? var : 0.0;
     mean[s] = (float)mu;
-    rstd[s] = (float)(1.0 / sqrt(var + (double)kLnEps));
+    rstd[s] = ln_rstd_f64(var);
   }
 }
 
@@ -425,7 +388,7 @@ __global__ __launch_bounds__(256) void im2col_obs_ln_kernel(const void* obs, con
     const int pos = (c * H + oh * S + kh) * W + ow * S + kw;
     const long src = s * (long)C * H * W + pos;
     const float x = U8 ? (float)static_cast<const uint8_t*>(obs)[src] : static_cast<const float*>(obs)[src];
-    P[e] = (x - mean[s]) * rstd[s] * gamma[pos] + beta[pos];
+    P[e] = ln_affine(ln_xhat(x, mean[s], rstd[s]), gamma[pos], beta[pos]);
   }
 }
 
@@ -457,8 +420,7 @@ __global__ __launch_bounds__(256) void obs_ln_affine_bwd_kernel(const float* dP,
     }
     const long src = s * (long)D + pos;
     const float x = U8 ? (float)static_cast<const uint8_t*>(obs)[src] : static_cast<const float*>(obs)[src];
-    ag += d * ((x - mean[s]) * rstd[s]);
-    ab += d;
+    ln_bwd_param_sums(d, ln_xhat(x, mean[s], rstd[s]), ag, ab);
   }
   atomicAdd(dgamma + pos, ag);
   atomicAdd(dbeta + pos, ab);
@@ -839,7 +801,7 @@ __global__ __launch_bounds__(256) void obs_s2d_kernel(const void* obs, long n, i
     double var = acc[1] / D - mu * mu;
     var = var > 0.0 ? var : 0.0;
     mean[smp] = (float)mu;
-    rstd[smp] = (float)(1.0 / sqrt(var + (double)kLnEps));
+    rstd[smp] = ln_rstd_f64(var);
   }
 }
 }  // namespace

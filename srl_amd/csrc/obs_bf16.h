@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256, 3) void obs_fwd_bf16_kernel(FwdArgs a) {
     cen = cen_next;
     set ^= 1;
   }
-  if (a.y_absmax) srlgemm::absmax_commit(a.y_absmax, amx);
+  if (a.y_absmax) wave_absmax_fold(amx, a.y_absmax);
 }
 
 // ---- backward: Q[pos][o][k] (+ split-K slabs), R[pos][o] += sum dz, C[pos][o] += sum dz' mean -----------------------------

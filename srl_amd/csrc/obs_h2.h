@@ -378,7 +378,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) void obs_fwd_h2_k
     stage = stage == kStages - 1 ? 0 : stage + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (a.y_absmax) srlgemm::absmax_commit(a.y_absmax, amx);
+  if (a.y_absmax) wave_absmax_fold(amx, a.y_absmax);
 #undef SRL_OBS_WAIT
 #undef SRL_OBS_FINISH
 }

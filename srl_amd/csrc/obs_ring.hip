@@ -1,6 +1,7 @@
 // Row gathers behind the HBM observation ring (srl_amd/runtime/obs_ring.py): the frames a rollout uploaded stay in a
 // ring of fixed-size rows; a training sample names its rows by ring slot and the chunk's rows are gathered from there
 // instead of crossing PCIe a second time.  HBM-bound copies: 2 x row_bytes per row.
+#include "layer_norm.h"
 #include "srl_common.h"
 
 namespace {
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void ring_slots_kernel(const int64_t* __restri
 // the same pass (integer sums, exact: bit-identical to srl_obs_space_to_depth on the assembled stack).
 __global__ __launch_bounds__(256) void stack_push_kernel(uint8_t* __restrict__ store, const uint8_t* __restrict__ planes,
                                                          const int32_t* __restrict__ prev, long slot0, int C, int H, int W,
-                                                         float* __restrict__ mean, float* __restrict__ rstd, float eps) {
+                                                         float* __restrict__ mean, float* __restrict__ rstd) {
   extern __shared__ __attribute__((aligned(16))) uint32_t plane_lds[];
   __shared__ double red[8];
   const long r = blockIdx.x;
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void stack_push_kernel(uint8_t* __restrict__ s
     double var = acc[1] / D - mu * mu;
     var = var > 0.0 ? var : 0.0;
     mean[slot0 + r] = (float)mu;
-    rstd[slot0 + r] = (float)(1.0 / sqrt(var + (double)eps));
+    rstd[slot0 + r] = ln_rstd_f64(var);
   }
 }
 
@@ -98,7 +99,7 @@ extern "C" int srl_ring_stack_push(void* stream, void* store, const void* planes
   SRL_CHECK_ARG((((uintptr_t)store | (uintptr_t)planes) & 15) == 0, "unaligned tensor");
   if (n == 0) return 0;
   hipLaunchKernelGGL(stack_push_kernel, dim3((unsigned)n), dim3(256), (size_t)H * W, (hipStream_t)stream, static_cast<uint8_t*>(store),
-                     static_cast<const uint8_t*>(planes), prev, (long)slot0, C, H, W, mean, rstd, 1e-5f);
+                     static_cast<const uint8_t*>(planes), prev, (long)slot0, C, H, W, mean, rstd);
   SRL_LAUNCH_CHECK();
   return 0;
 }

@@ -90,6 +90,18 @@ __device__ __forceinline__ float wave_allmax(float v) {
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
+// Fold the wavefront's max of amx (>= 0 in every lane: unsigned order = float order) into *slot, a range slot that only grows.
+// One atomic per wavefront to ONE address is a serial chain through one L2 channel (~10 ns each): 51 000 wavefronts of a
+// strided data gradient spent 0.2 ms of its 0.67 there.  So a wavefront whose maximum does not exceed what a (relaxed, possibly
+// stale -- staleness only means a superfluous atomic) load returns has nothing to add: after the first few tiles almost every
+// wavefront leaves with the load alone.
+__device__ __forceinline__ void wave_absmax_fold(float amx, float* slot) {
+  amx = wave_allmax(amx);
+  if ((threadIdx.x & 63) == 0 && amx > 0.f) {
+    unsigned int* d = reinterpret_cast<unsigned int*>(slot);
+    if (__float_as_uint(amx) > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, __float_as_uint(amx));
+  }
+}
 
 // Sum NV doubles per thread across a block of NT threads (NT multiple of 64, <= 1024).
 // Result valid in thread 0.  `scratch` must hold (NT/64)*NV doubles of LDS.

@@ -538,6 +538,87 @@ def test_layernorm_fwd_bwd(rows, D):
     assert rel_close(dbo.cpu().numpy(), tb.grad.numpy(), 2e-5, scale=float(np.sqrt(rows)))
 
 
+def _ln_case(rows, D, pitch=None):
+    """Inputs of a LayerNorm behind a ReLU in buffers of row pitch ``pitch`` (default: dense) and the float64 torch oracle:
+    ``(x, gamma, beta, dy)`` on the device, ``(y, dx, dgamma, dbeta)`` as float64 arrays."""
+    pitch = pitch or D
+    rng = np.random.default_rng(rows + D)
+    x = np.maximum((rng.standard_normal((rows, D)) * 2 + 0.5).astype(np.float32), 0)
+    gamma = (1 + 0.1 * rng.standard_normal(D)).astype(np.float32)
+    beta = (0.1 * rng.standard_normal(D)).astype(np.float32)
+    dy = rng.standard_normal((rows, D)).astype(np.float32)
+    tx = torch.from_numpy(x).double().requires_grad_(True)
+    tg = torch.from_numpy(gamma).double().requires_grad_(True)
+    tb = torch.from_numpy(beta).double().requires_grad_(True)
+    ty = torch.nn.functional.layer_norm(torch.relu(tx.clone()), (D,), tg, tb, 1e-5)
+    ty.backward(torch.from_numpy(dy).double())
+
+    def pitched(a):
+        buf = torch.zeros((rows, pitch), device=DEV)
+        buf[:, :D] = dev(a)
+        return buf
+
+    return ((pitched(x), dev(gamma), dev(beta), pitched(dy)),
+            (ty.detach().numpy(), tx.grad.numpy(), tg.grad.numpy(), tb.grad.numpy()))
+
+
+def _ln_fwd(x, gamma, beta, rows, D, y):
+    mean = torch.empty(rows, device=DEV)
+    rstd = torch.empty(rows, device=DEV)
+    hip.layernorm_fwd(x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(), rows, D, y.data_ptr(), y.stride(0),
+                      mean.data_ptr(), rstd.data_ptr())
+    return mean, rstd
+
+
+@pytest.mark.parametrize("rows,D", [(5, 4), (5, 132), (9, 256), (3, 1408)])  # small (LPR = 4), general, vec (NV = 1), wide
+def test_layernorm_bwd_params_only(rows, D):
+    """dx = None (HipNet._ln_bwd without need_dx): the parameter gradients alone, on every width branch."""
+    (x, gamma, beta, dy), (_, _, ref_dg, ref_db) = _ln_case(rows, D)
+    mean, rstd = _ln_fwd(x, gamma, beta, rows, D, torch.empty((rows, D), device=DEV))
+    dgo = torch.zeros(D, device=DEV)
+    dbo = torch.zeros(D, device=DEV)
+    hip.layernorm_bwd(dy.data_ptr(), D, x.data_ptr(), D, gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, D, None, 0,
+                      1, dgo.data_ptr(), dbo.data_ptr(), dx_absmax=None)
+    assert rel_close(dgo.cpu().numpy(), ref_dg, 2e-5, scale=float(np.sqrt(rows)))
+    assert rel_close(dbo.cpu().numpy(), ref_db, 2e-5, scale=float(np.sqrt(rows)))
+
+
+@pytest.mark.parametrize("rows,D", [(70, 64), (70, 256)])
+def test_layernorm_bwd_accumulates(rows, D):
+    """dgamma / dbeta are += targets: two calls into the same buffers leave twice the gradient."""
+    (x, gamma, beta, dy), (_, _, ref_dg, ref_db) = _ln_case(rows, D)
+    mean, rstd = _ln_fwd(x, gamma, beta, rows, D, torch.empty((rows, D), device=DEV))
+    dxo = torch.empty((rows, D), device=DEV)
+    dgo = torch.zeros(D, device=DEV)
+    dbo = torch.zeros(D, device=DEV)
+    for _ in range(2):
+        hip.layernorm_bwd(dy.data_ptr(), D, x.data_ptr(), D, gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, D,
+                          dxo.data_ptr(), D, 1, dgo.data_ptr(), dbo.data_ptr())
+    assert rel_close(dgo.cpu().numpy(), 2 * ref_dg, 2e-5, scale=float(np.sqrt(rows)))
+    assert rel_close(dbo.cpu().numpy(), 2 * ref_db, 2e-5, scale=float(np.sqrt(rows)))
+
+
+@pytest.mark.parametrize("rows,D,pitch", [(33, 96, 128), (33, 132, 200)])  # small and general branch
+def test_layernorm_pitched_rows(rows, D, pitch):
+    """ldx, ldy, lddy, lddx > D: the results are right and the pad columns of y and dx keep their bits."""
+    (x, gamma, beta, dy), (ref_y, ref_dx, ref_dg, ref_db) = _ln_case(rows, D, pitch)
+    sentinel = -777.25
+    y = torch.full((rows, pitch), sentinel, device=DEV)
+    dxo = torch.full((rows, pitch), sentinel, device=DEV)
+    mean, rstd = _ln_fwd(x, gamma, beta, rows, D, y)
+    dgo = torch.zeros(D, device=DEV)
+    dbo = torch.zeros(D, device=DEV)
+    hip.layernorm_bwd(dy.data_ptr(), pitch, x.data_ptr(), pitch, gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, D,
+                      dxo.data_ptr(), pitch, 1, dgo.data_ptr(), dbo.data_ptr())
+    y, dxo = y.cpu().numpy(), dxo.cpu().numpy()
+    assert rel_close(y[:, :D], ref_y, 1e-5, scale=1.0)
+    assert rel_close(dxo[:, :D], ref_dx, 2e-5, scale=1.0)
+    assert rel_close(dgo.cpu().numpy(), ref_dg, 2e-5, scale=float(np.sqrt(rows)))
+    assert rel_close(dbo.cpu().numpy(), ref_db, 2e-5, scale=float(np.sqrt(rows)))
+    pad = np.full((rows, pitch - D), sentinel, np.float32)
+    assert (y[:, D:].view(np.uint32) == pad.view(np.uint32)).all() and (dxo[:, D:].view(np.uint32) == pad.view(np.uint32)).all()
+
+
 # ------------------------------------------------------------------------------------------------ convolution pieces
 def test_obs_ln_im2col_and_affine_bwd():
     rng = np.random.default_rng(3)
