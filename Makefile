@@ -11,6 +11,10 @@ FLAGS := -O3 --offload-arch=$(ARCH) -std=c++17 -fPIC
 
 all: $(LIB)
 
+# rnn_wseq.hip (beside rnn_seq.hip in the wildcard above) keeps W_hh in registers: the build prints what each of its kernels
+# took (registers, scratch -- which must be 0), and its cell arithmetic beside the MFMAs stays on unpacked float32 ops.
+$(OBJD)/rnn_wseq.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops -Rpass-analysis=kernel-resource-usage
+
 $(OBJD)/%.o: srl_amd/csrc/%.hip $(HDRS)
 	@mkdir -p $(OBJD)
 	$(HIPCC) $(FLAGS) -c -o $@ $<

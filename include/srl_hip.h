@@ -228,6 +228,22 @@ int srl_gru_step_fwd(void* stream, float* gi_t, float* gh_t, const float* w_hh, 
 int srl_lstm_step_fwd(void* stream, float* pre_t, const float* w_hh, const float* b_hh, const float* hin_t, const float* cin_t,
                       const uint8_t* reset_next, int64_t N, int H, float* y_t, float* cnew_t, float* hin_next, float* cin_next);
 
+/* The whole time loop of a chunk in one launch at H = 128 (added at ABI 23: additive, the version is unchanged;
+ * csrc/rnn_wseq.hip; srl_rnn_wseq_supported(kind, H), kind 0 GRU, 1 LSTM, is 1 for H == 128 only).  Arguments, buffers,
+ * the [C][N][.] layout, the reset rule, the saved values and the in-place effect of the backward are those of
+ * srl_lstm_seq_fwd/_bwd and srl_gru_seq_fwd/_bwd above, so either direction can follow the per-step entry points on the same
+ * buffers; the gates are libm's, as on the per-step path.  W_hh stays in the registers of a four-wavefront workgroup that
+ * walks tiles of 32 rows, the state goes through LDS.  w_hh 16-byte aligned; ld_dy below 2^24. */
+int srl_rnn_wseq_supported(int kind, int H);
+int srl_lstm_wseq_fwd(void* stream, float* pre, const float* w_hh, const float* b_hh, float* hin, float* cin,
+                      const uint8_t* reset, int64_t N, int H, int C, float* y, float* cnew);
+int srl_lstm_wseq_bwd(void* stream, const float* dy, int64_t ld_dy, float* gates, const float* w_hh, const float* cin,
+                      const float* cnew, const uint8_t* reset, int64_t N, int H, int C);
+int srl_gru_wseq_fwd(void* stream, float* gi, float* gh, const float* w_hh, const float* b_hh, float* hin,
+                     const uint8_t* reset, int64_t N, int H, int C, float* y);
+int srl_gru_wseq_bwd(void* stream, const float* dy, int64_t ld_dy, float* gates, float* gh, const float* w_hh,
+                     const float* hin, const uint8_t* reset, int64_t N, int H, int C);
+
 /* Rows of D floats between time-major [T*B] and chunk-major order: dst[(c, k*B + b)] = src[((k*C + c), b)]
  * (modules/utils.py:164-182 `to_chunk`: torch.cat(torch.split(x, C, dim=0), dim=1)); inverse != 0 undoes it. */
 int srl_chunk_rows(void* stream, const float* src, float* dst, int T, int B, int C, int D, int inverse);

@@ -39,14 +39,21 @@ RnnSaved = NamedTuple("RnnSaved", [("layers", list), ("ctx", RnnCtx), ("cm", boo
 # `r(c)`: the address of step c's reset flags, or None; `path`: one of PATHS, by default `time_loop_path`'s.  The backward of
 # "fused" is "cell"'s (the fused step saves what the cell saves); it writes d h_in (d c_in) of step c to the addresses
 # `carry(c)` gives, which stay untouched until step c - 1 has read them.
-PATHS = ("seq", "fused", "cell")
+PATHS = ("seq", "wseq", "fused", "cell")
+
+# The path the layer loop below names for every layer; None: `time_loop_path` chooses.  A plain attribute, like
+# `hip.RNN_STEP_FUSED` (the set of environment switches is closed).  "wseq" (csrc/rnn_wseq.hip, H = 128: W_hh stationary in
+# registers, the chunk in one launch per direction) runs only where it is named: the default at that width is a measured
+# decision that has not been taken.
+NAMED: Optional[str] = None
 
 
 def time_loop_path(kind: str, H: int, named: Optional[str] = None) -> str:
     """Where the path is chosen: the whole chunk in one launch (csrc/rnn_seq.hip) where the library has the width; else W_hh h and
     the cell of a step in one launch (csrc/rnn_step.hip); else srl_gemm plus a cell of csrc/gru.hip per step.  ``named``: the
-    caller's choice instead (the tests' and the bench's reference sides)."""
+    caller's choice instead (the tests' and the bench's reference sides; "wseq", csrc/rnn_wseq.hip, is taken no other way)."""
     assert named is None or named in PATHS, named
+    assert named != "wseq" or hip.rnn_wseq_supported(kind, H), (kind, H)
     return named or ("seq" if hip.rnn_seq_supported(kind, H) else "fused" if hip.rnn_step_supported(kind, H) else "cell")
 
 
@@ -59,8 +66,8 @@ class _Lstm:
     def fwd(self, s, w_hh, b_hh, r, N, H, C, path=None):
         path = time_loop_path(self.kind, H, path)
         pre, hin, cin, cnew, y = s
-        if path == "seq":
-            return hip.lstm_seq_fwd(pre, w_hh, b_hh, hin, cin, r(0), N, H, C, y, cnew)
+        if path in ("seq", "wseq"):
+            return (hip.lstm_seq_fwd if path == "seq" else hip.lstm_wseq_fwd)(pre, w_hh, b_hh, hin, cin, r(0), N, H, C, y, cnew)
         for c in range(C):
             o4, o1, o1n, nxt = 4 * c * N * 4 * H, 4 * c * N * H, 4 * (c + 1) * N * H, c + 1 < C
             out = (r(c + 1) if nxt else None, N, H, y + o1, cnew + o1, hin + o1n if nxt else None, cin + o1n if nxt else None)
@@ -72,10 +79,10 @@ class _Lstm:
 
     def bwd(self, s, dy, ld_dy, w_hh, r, N, H, C, carry, path=None):
         path = time_loop_path(self.kind, H, path)
-        assert path == "seq" or ld_dy == H, "the per-step cells read d y in rows of H"
+        assert path in ("seq", "wseq") or ld_dy == H, "the per-step cells read d y in rows of H"
         pre, _, cin, cnew, _ = s
-        if path == "seq":
-            return hip.lstm_seq_bwd(dy, ld_dy, pre, w_hh, cin, cnew, r(0), N, H, C)
+        if path in ("seq", "wseq"):
+            return (hip.lstm_seq_bwd if path == "seq" else hip.lstm_wseq_bwd)(dy, ld_dy, pre, w_hh, cin, cnew, r(0), N, H, C)
         ch = cc = None
         for c in range(C - 1, -1, -1):
             o4, o1, (dh, dc) = 4 * c * N * 4 * H, 4 * c * N * H, carry(c)
@@ -93,8 +100,8 @@ class _Gru:
     def fwd(self, s, w_hh, b_hh, r, N, H, C, path=None):
         path = time_loop_path(self.kind, H, path)
         gi, gh, hin, y = s
-        if path == "seq":
-            return hip.gru_seq_fwd(gi, gh, w_hh, b_hh, hin, r(0), N, H, C, y)
+        if path in ("seq", "wseq"):
+            return (hip.gru_seq_fwd if path == "seq" else hip.gru_wseq_fwd)(gi, gh, w_hh, b_hh, hin, r(0), N, H, C, y)
         for c in range(C):
             o3, o1, nxt = 4 * c * N * 3 * H, 4 * c * N * H, c + 1 < C
             out = (r(c + 1) if nxt else None, N, H, y + o1, hin + 4 * (c + 1) * N * H if nxt else None)
@@ -106,10 +113,10 @@ class _Gru:
 
     def bwd(self, s, dy, ld_dy, w_hh, r, N, H, C, carry, path=None):
         path = time_loop_path(self.kind, H, path)
-        assert path == "seq" or ld_dy == H, "the per-step cells read d y in rows of H"
+        assert path in ("seq", "wseq") or ld_dy == H, "the per-step cells read d y in rows of H"
         gi, gh, hin, _ = s
-        if path == "seq":
-            return hip.gru_seq_bwd(dy, ld_dy, gi, gh, w_hh, hin, r(0), N, H, C)
+        if path in ("seq", "wseq"):
+            return (hip.gru_seq_bwd if path == "seq" else hip.gru_wseq_bwd)(dy, ld_dy, gi, gh, w_hh, hin, r(0), N, H, C)
         prev = None
         for c in range(C - 1, -1, -1):
             o3, o1, (cur,) = 4 * c * N * 3 * H, 4 * c * N * H, carry(c)
@@ -191,7 +198,7 @@ def forward(net, G, x, tag: str, ctx: RnnCtx, cm: bool):
                 hip.copy2d(src, SW, s.y.ptr, H, N, H)
                 src = s.y.ptr
             hip.gru_mask_state(src, r(0), N, H, getattr(s, first).ptr)
-        k.fwd(k.Bufs(*[b.ptr for b in s]), w_hh, b_hh, r, N, H, C)   # the time loop: in one launch, or step by step
+        k.fwd(k.Bufs(*[b.ptr for b in s]), w_hh, b_hh, r, N, H, C, NAMED)   # the time loop: in one launch, or step by step
         for j, (_, final) in enumerate(k.state):
             hip.copy2d(getattr(s, final).ptr + end, H, last[l].data_ptr() + 4 * j * H, SW, N, H)
         saved.append((inp, s))
@@ -210,7 +217,7 @@ def backward(net, G, saved: RnnSaved, dy, in_act: int, need_dx: bool, tag: str):
         inp, s = saved.layers[l]
         w_ih, w_hh = net._p(f"{G.prefix}.weight_ih_l{l}"), net._p(f"{G.prefix}.weight_hh_l{l}")
         carry, per = [net._buf(f"{name}.{b}", N, H).ptr for b in k.carries], len(k.carries) // 2   # two alternating sets
-        k.bwd(k.Bufs(*[b.ptr for b in s]), dout.ptr, dout.ld, w_hh, r, N, H, ctx.C, lambda c: carry[per * (c & 1):][:per])
+        k.bwd(k.Bufs(*[b.ptr for b in s]), dout.ptr, dout.ld, w_hh, r, N, H, ctx.C, lambda c: carry[per * (c & 1):][:per], NAMED)
         # parameter gradients over all steps at once (the bias gradients, column sums, come out of the same kernels)
         net._wgrad(k.gates * H, H, n, getattr(s, k.d_hh), s.hin.ptr, H, net._g(f"{G.prefix}.weight_hh_l{l}"),
                    net._g(f"{G.prefix}.bias_hh_l{l}"))

@@ -373,6 +373,40 @@ def gru_seq_bwd(dy_ptr, ld_dy, gates_ptr, gh_ptr, w_hh, hin_ptr, reset_ptr, N, H
            "srl_gru_seq_bwd")
 
 
+def rnn_wseq_supported(kind: str, H: int) -> bool:
+    """Whether the register-stationary chunk kernels take this cell and width (``srl_rnn_wseq_supported``: H = 128,
+    csrc/rnn_wseq.hip).  Not part of the default selection: `rnnpath` runs them where "wseq" is named."""
+    return bool(lib().srl_rnn_wseq_supported(1 if kind == "lstm" else 0, int(H)))
+
+
+def _wseq_flops(gates, N, H, C):
+    return 2.0 * int(C) * int(N) * gates * int(H) * int(H)   # the W_hh product of every step, either direction
+
+
+def lstm_wseq_fwd(pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_ptr, N, H, C, y_ptr, cnew_ptr):
+    with _scope("lstm_wseq_fwd", _wseq_flops(4, N, H, C), "f32"):
+        _check(lib().srl_lstm_wseq_fwd(_stream(), pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_ptr, int(N), int(H), int(C), y_ptr,
+                                       cnew_ptr), "srl_lstm_wseq_fwd")
+
+
+def lstm_wseq_bwd(dy_ptr, ld_dy, gates_ptr, w_hh, cin_ptr, cnew_ptr, reset_ptr, N, H, C):
+    with _scope("lstm_wseq_bwd", _wseq_flops(4, N, H, C), "f32"):
+        _check(lib().srl_lstm_wseq_bwd(_stream(), dy_ptr, int(ld_dy), gates_ptr, w_hh, cin_ptr, cnew_ptr, reset_ptr, int(N), int(H),
+                                       int(C)), "srl_lstm_wseq_bwd")
+
+
+def gru_wseq_fwd(gi_ptr, gh_ptr, w_hh, b_hh, hin_ptr, reset_ptr, N, H, C, y_ptr):
+    with _scope("gru_wseq_fwd", _wseq_flops(3, N, H, C), "f32"):
+        _check(lib().srl_gru_wseq_fwd(_stream(), gi_ptr, gh_ptr, w_hh, b_hh, hin_ptr, reset_ptr, int(N), int(H), int(C), y_ptr),
+               "srl_gru_wseq_fwd")
+
+
+def gru_wseq_bwd(dy_ptr, ld_dy, gates_ptr, gh_ptr, w_hh, hin_ptr, reset_ptr, N, H, C):
+    with _scope("gru_wseq_bwd", _wseq_flops(3, N, H, C), "f32"):
+        _check(lib().srl_gru_wseq_bwd(_stream(), dy_ptr, int(ld_dy), gates_ptr, gh_ptr, w_hh, hin_ptr, reset_ptr, int(N), int(H),
+                                      int(C)), "srl_gru_wseq_bwd")
+
+
 def gru_mask_state(h_ptr, reset_ptr, N, H, out_ptr):
     _check(lib().srl_gru_mask_state(_stream(), h_ptr, reset_ptr, int(N), int(H), out_ptr), "srl_gru_mask_state")
 
