@@ -15,6 +15,9 @@ all: $(LIB)
 # took (registers, scratch -- which must be 0), and its cell arithmetic beside the MFMAs stays on unpacked float32 ops.
 $(OBJD)/rnn_wseq.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops -Rpass-analysis=kernel-resource-usage
 
+# ln_heads_wide.hip likewise: head weights and their gradient sums resident in registers beside the MFMAs, no scratch.
+$(OBJD)/ln_heads_wide.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops -Rpass-analysis=kernel-resource-usage
+
 $(OBJD)/%.o: srl_amd/csrc/%.hip $(HDRS)
 	@mkdir -p $(OBJD)
 	$(HIPCC) $(FLAGS) -c -o $@ $<

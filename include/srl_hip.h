@@ -866,6 +866,21 @@ int srl_ln_heads_bwd(void* stream, const float* x, int64_t ldx, int64_t n, int D
                      const float* mean, const float* rstd, int n_heads, const float* const* W, const int32_t* head_dims,
                      const float* const* dy, const int64_t* lddy, int in_act, float* dx, int64_t lddx, float* dgamma, float* dbeta,
                      float* const* dW, float* const* db, float* dx_absmax);
+/* The same tail (actor_critic_policy.py:117-140) for heads whose outputs together number SRL_LN_HEADS_MAX_OUT + 1 to
+ * SRL_LN_HEADS_WIDE_MAX_OUT -- Atari's full action set of 18 plus the value, any image policy with more than 7 actions
+ * (csrc/ln_heads_wide.hip: the head products on the float32 matrix cores, 32-row tiles through LDS; srl_ln_heads_wide_supported).
+ * Every argument as in srl_ln_heads_fwd / srl_ln_heads_bwd, with the same alignment rules, finishing step and added-to
+ * gradients. */
+#define SRL_LN_HEADS_WIDE_MAX_OUT 32
+int srl_ln_heads_wide_supported(int D, int n_heads, const int32_t* head_dims);
+int srl_ln_heads_wide_fwd(void* stream, const float* x, int64_t ldx, int64_t n, int D, const float* gamma, const float* beta,
+                          int n_heads, const float* const* W, const float* const* b, const int32_t* head_dims, float* const* y,
+                          const int64_t* ldy, float* mean, float* rstd, int x_slabs, int64_t x_slab_stride, const float* x_bias,
+                          int x_act, float* x_out, int64_t ldxo);
+int srl_ln_heads_wide_bwd(void* stream, const float* x, int64_t ldx, int64_t n, int D, const float* gamma, const float* beta,
+                          const float* mean, const float* rstd, int n_heads, const float* const* W, const int32_t* head_dims,
+                          const float* const* dy, const int64_t* lddy, int in_act, float* dx, int64_t lddx, float* dgamma,
+                          float* dbeta, float* const* dW, float* const* db, float* dx_absmax);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser on one flat parameter buffer.

@@ -76,7 +76,7 @@ class ConvSaved(NamedTuple):
     x_range: Optional[int]        # device float bounding max |x| (the producer tracked it), or None
 
 
-LnHeadsSaved = NamedTuple("LnHeadsSaved", [("mean", torch.Tensor), ("rstd", torch.Tensor), ("heads", list)])
+LnHeadsSaved = NamedTuple("LnHeadsSaved", [("mean", torch.Tensor), ("rstd", torch.Tensor), ("heads", list), ("wide", bool)])
 ObsLnSaved = NamedTuple("ObsLnSaved", [("is_u8", bool), ("mean", torch.Tensor), ("rstd", torch.Tensor), ("n", int)])
 def _padded_vol(L) -> tuple:
     """(D, H, W, C) of a convolution's input with its border (ConvSpec: D = 1)."""
@@ -876,12 +876,15 @@ class HipNet:
         xptr, ks, stride, xb, xact, keep = slabs if slabs else (cur.ptr, 1, 0, None, 0, False)
         # (a split product: this launch adds the slabs, the bias and the ReLU while it reads them -- and, when a backward
         # pass follows, writes the finished rows to `cur`)
-        hip.ln_heads_fwd(xptr, cur.ld, n, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
-                         [self._p(f"{h.prefix}.weight") for h in heads], [self._p(f"{h.prefix}.bias") for h in heads],
-                         [h.out_features for h in heads], [o.data_ptr() for o in outs], [h.out_features for h in heads],
-                         mean.data_ptr(), rstd.data_ptr(), x_slabs=ks, x_slab_stride=stride, x_bias=xb, x_act=xact,
-                         x_out=cur.ptr if (slabs and not self._infer) else None, ldxo=cur.ld)
-        st.tape.append(Rec("lnheads", L, cur, LnHeadsSaved(mean, rstd, heads), st.cur_act, L.dim))
+        # (the family `_lnheads_ok` found: up to 8 outputs in lane registers, 9 to 32 on the matrix cores)
+        wide = not hip.ln_heads_supported(L.dim, [h.out_features for h in heads])
+        (hip.ln_heads_wide_fwd if wide else hip.ln_heads_fwd)(
+            xptr, cur.ld, n, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
+            [self._p(f"{h.prefix}.weight") for h in heads], [self._p(f"{h.prefix}.bias") for h in heads],
+            [h.out_features for h in heads], [o.data_ptr() for o in outs], [h.out_features for h in heads],
+            mean.data_ptr(), rstd.data_ptr(), x_slabs=ks, x_slab_stride=stride, x_bias=xb, x_act=xact,
+            x_out=cur.ptr if (slabs and not self._infer) else None, ldxo=cur.ld)
+        st.tape.append(Rec("lnheads", L, cur, LnHeadsSaved(mean, rstd, heads, wide), st.cur_act, L.dim))
         st.finish(None)
 
     @_fwd(ns.InstrLstmSpec, emits=("instr",))
@@ -1259,17 +1262,18 @@ class HipNet:
     def _bwd_lnheads(self, rec, g, g_range, need_dx, tag, below, dv):
         # closing LayerNorm + heads: g is d loss / d first head's output, `dv` the second head's gradient
         L, x = rec.layer, rec.x
-        mean, rstd, heads = rec.saved
+        mean, rstd, heads, wide = rec.saved
         dys = [g] + ([dv] if len(heads) > 1 else [])
         dx = self._buf(f"{tag}{L.prefix}.dx", x.rows, L.dim)
         # a pre-split block below wants max |dx|: tracked here while dx is written, instead of one more pass over it
         amax = below.layer.open_backward(below.saved) if (below is not None and below.kind == "h2cnn") else None
-        hip.ln_heads_bwd(x.ptr, x.ld, x.rows, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
-                         mean.data_ptr(), rstd.data_ptr(), [self._p(f"{h.prefix}.weight") for h in heads],
-                         [h.out_features for h in heads], [d.ptr for d in dys], [d.ld for d in dys], rec.in_act, dx.ptr, dx.ld,
-                         self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"),
-                         [self._g(f"{h.prefix}.weight") for h in heads], [self._g(f"{h.prefix}.bias") for h in heads],
-                         dx_absmax=amax)
+        (hip.ln_heads_wide_bwd if wide else hip.ln_heads_bwd)(
+            x.ptr, x.ld, x.rows, L.dim, self._p(f"{L.prefix}.weight"), self._p(f"{L.prefix}.bias"),
+            mean.data_ptr(), rstd.data_ptr(), [self._p(f"{h.prefix}.weight") for h in heads],
+            [h.out_features for h in heads], [d.ptr for d in dys], [d.ld for d in dys], rec.in_act, dx.ptr, dx.ld,
+            self._g(f"{L.prefix}.weight"), self._g(f"{L.prefix}.bias"),
+            [self._g(f"{h.prefix}.weight") for h in heads], [self._g(f"{h.prefix}.bias") for h in heads],
+            dx_absmax=amax)
         self._release([h.prefix for h in heads] + [L.prefix])
         return dx, ("tracked" if amax is not None else None)
 
@@ -1394,6 +1398,8 @@ class HipNet:
                               dx_absmax=dx_range, x_mask=x_mask, presplit=pre is not None, family=fam)
         return self._crop(tag, L, dx, n), dx_range
 
+    LNHEADS_WIDE = True   # tests/test_gpu_ln_heads_wide.py and scripts/ln_heads_wide_ab.py clear it for the layer-by-layer side
+
     def _lnheads_ok(self, encoders, backbone, heads, n) -> bool:
         """The encoder's closing LayerNorm and the heads right behind it (no backbone layers between) as one launch."""
         if backbone or len(encoders) != 1 or n > self.encoder_rows or not heads or n < 64:
@@ -1401,7 +1407,8 @@ class HipNet:
         last = encoders[0].layers[-1] if encoders[0].layers else None
         if not isinstance(last, ns.LayerNormSpec) or len(encoders[0].layers) < 2 or any(h.in_features != last.dim or h.act for h in heads):
             return False
-        return hip.ln_heads_supported(last.dim, [h.out_features for h in heads])
+        dims = [h.out_features for h in heads]
+        return hip.ln_heads_supported(last.dim, dims) or (self.LNHEADS_WIDE and hip.ln_heads_wide_supported(last.dim, dims))
 
     def _trunk_fwd(self, tag, encoders, backbone, obs: Dict[str, torch.Tensor], n: int, head=None, head_out=None, lnheads=None):
         """``head`` / ``head_out``: the head behind this trunk and the tensor its output goes to -- when the layers that follow the

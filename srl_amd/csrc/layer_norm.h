@@ -13,7 +13,7 @@
 // (g * xhat, dy * xhat) enter it through one explicit fused multiply-add, whatever the compiler's contraction setting.  The whole-observation statistics (the observation
 // LayerNorm in front of the first convolution) come from exact or float64 sums and take the float64 form ln_rstd_f64.
 //
-// Included by nn_ops.hip, ln_heads.hip, entity_attn.hip, obs_ring.hip and mlp_small.hip (and through it by mlp_mfma.h and
+// Included by nn_ops.hip, ln_heads.hip, ln_heads_wide.hip, entity_attn.hip, obs_ring.hip and mlp_small.hip (and through it by mlp_mfma.h and
 // mlp_sig.h).
 #pragma once
 #include "srl_common.h"

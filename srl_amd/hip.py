@@ -777,6 +777,33 @@ def ln_heads_bwd(x_ptr, ldx, n, D, gamma_ptr, beta_ptr, mean_ptr, rstd_ptr, w_pt
                                       dx_ptr, lddx, dgamma_ptr, dbeta_ptr, _ptr_array(dw_ptrs), _ptr_array(db_ptrs), dx_absmax), "srl_ln_heads_bwd")
 
 
+def ln_heads_wide_supported(D: int, head_dims) -> bool:
+    """Whether LayerNorm(D) + these heads -- 9 to 32 outputs together -- run as one launch per direction on the matrix cores
+    (csrc/ln_heads_wide.hip); `ln_heads_supported` answers for up to 8."""
+    return bool(lib().srl_ln_heads_wide_supported(int(D), len(head_dims), _i32_array(head_dims)))
+
+
+def ln_heads_wide_fwd(x_ptr, ldx, n, D, gamma_ptr, beta_ptr, w_ptrs, b_ptrs, head_dims, y_ptrs, ldys, mean_ptr, rstd_ptr, x_slabs=1,
+                      x_slab_stride=0, x_bias=None, x_act=0, x_out=None, ldxo=0):
+    """`ln_heads_fwd` for 9 to 32 head outputs: the same arguments, the same finishing step."""
+    flops = 2.0 * n * D * sum(head_dims)
+    with _scope("ln_heads_wide_fwd", flops, "f32"):
+        _check(lib().srl_ln_heads_wide_fwd(_stream(), x_ptr, ldx, n, int(D), gamma_ptr, beta_ptr, len(head_dims), _ptr_array(w_ptrs),
+                                           _ptr_array(b_ptrs), _i32_array(head_dims), _ptr_array(y_ptrs), (c_int64 * len(ldys))(*ldys),
+                                           mean_ptr, rstd_ptr, int(x_slabs), int(x_slab_stride), x_bias, int(x_act), x_out, int(ldxo)),
+               "srl_ln_heads_wide_fwd")
+
+
+def ln_heads_wide_bwd(x_ptr, ldx, n, D, gamma_ptr, beta_ptr, mean_ptr, rstd_ptr, w_ptrs, head_dims, dy_ptrs, lddys, in_act, dx_ptr, lddx,
+                      dgamma_ptr, dbeta_ptr, dw_ptrs, db_ptrs, dx_absmax=None):
+    flops = 4.0 * n * D * sum(head_dims)
+    with _scope("ln_heads_wide_bwd", flops, "f32"):
+        _check(lib().srl_ln_heads_wide_bwd(_stream(), x_ptr, ldx, n, int(D), gamma_ptr, beta_ptr, mean_ptr, rstd_ptr, len(head_dims),
+                                           _ptr_array(w_ptrs), _i32_array(head_dims), _ptr_array(dy_ptrs), (c_int64 * len(lddys))(*lddys),
+                                           int(in_act), dx_ptr, lddx, dgamma_ptr, dbeta_ptr, _ptr_array(dw_ptrs), _ptr_array(db_ptrs),
+                                           dx_absmax), "srl_ln_heads_wide_bwd")
+
+
 def obs_ln_stats(obs_ptr, is_u8, n, D, mean_ptr, rstd_ptr):
     _check(lib().srl_obs_ln_stats(_stream(), obs_ptr, int(is_u8), n, D, mean_ptr, rstd_ptr), "srl_obs_ln_stats")
 
