@@ -228,6 +228,22 @@ int srl_gru_step_fwd(void* stream, float* gi_t, float* gh_t, const float* w_hh, 
 int srl_lstm_step_fwd(void* stream, float* pre_t, const float* w_hh, const float* b_hh, const float* hin_t, const float* cin_t,
                       const uint8_t* reset_next, int64_t N, int H, float* y_t, float* cnew_t, float* hin_next, float* cin_next);
 
+/* One BACKWARD time step in one launch at the same widths (additive, the version is unchanged; csrc/rnn_step.hip), fused across
+ * the step boundary: the launch for step t forms D = d gates(t+1) . W_hh (GRU: dgh_next [N, 3H]; LSTM: dpre_next [N, 4H]; what
+ * srl_gemm computes after the cell of step t+1 on the two-launch path), then runs the cell backward of step t.
+ * GRU: dh = dy + (direct_next + D) * (1 - reset_next); gates_t <- d gi, gh_t <- d gh in place; direct_t = dh * z.
+ * LSTM: dh = dy + D * (1 - reset_next), dc = dc_next * (1 - reset_next); gates_t <- d pre in place; dc_in_t written.
+ * dy_t [N, ld_dy] or NULL (zeros), ld_dy >= H and a multiple of 4.  At a chunk's last step dgh_next / dpre_next, direct_next /
+ * dc_next and reset_next are all NULL (the cell only); else both set, reset_next optional.  The *_next buffers are read by
+ * every workgroup: they must not alias anything written for step t.  All tensors 16-byte aligned.  d h_in of a chunk's first
+ * step is not formed. */
+int srl_gru_step_bwd(void* stream, const float* dy_t, int64_t ld_dy, const float* dgh_next, const float* direct_next,
+                     const uint8_t* reset_next, const float* w_hh, float* gates_t, float* gh_t, const float* hin_t, int64_t N,
+                     int H, float* direct_t);
+int srl_lstm_step_bwd(void* stream, const float* dy_t, int64_t ld_dy, const float* dpre_next, const float* dc_next,
+                      const uint8_t* reset_next, const float* w_hh, float* gates_t, const float* cin_t, const float* cnew_t,
+                      int64_t N, int H, float* dc_in_t);
+
 /* The whole time loop of a chunk in one launch at H = 128 (added at ABI 23: additive, the version is unchanged;
  * csrc/rnn_wseq.hip; srl_rnn_wseq_supported(kind, H), kind 0 GRU, 1 LSTM, is 1 for H == 128 only).  Arguments, buffers,
  * the [C][N][.] layout, the reset rule, the saved values and the in-place effect of the backward are those of

@@ -3,8 +3,11 @@
   * ``rnnpath``'s forward time loop over C = 40 steps, each path named: GRU and LSTM at H = 512 with N = 128 rows per step (the
     recurrent atari-dqn agent at 64 environments, two chunks) and at H = 128 with N = 256 (the football / overcooked width);
     device events around 10 loops, 9 repetitions, the two ways alternating; microseconds per loop, median / min / max;
+  * the backward time loop at the same four shapes on what the fused forward saved: "cell"'s (srl_*_cell_bwd + srl_gemm per step,
+    the backward of "fused" today) against "step"'s (srl_*_step_bwd, one launch per step), timed the same way;
   * one ``q-learning`` update of the recurrent ``atari-dqn`` agent (GRU, hidden_dim 512, chunk_len 40, burn_in_steps 40, B = 64;
-    120 x 64 frames), host clock around the synchronised step, the two ways alternating; milliseconds.
+    120 x 64 frames), host clock around the synchronised step, the ways alternating (the third: `rnnpath.NAMED = "step"`, the
+    fused forward with the one-launch backward step); milliseconds.
 Prints one JSON line per case and, with ``--out FILE``, writes them all (DESIGN.md / LAB_NOTEBOOK section 19 quote a run of it).
 
     python scripts/rnn_step_bench.py [--out rnn_step_bench.json]
@@ -20,6 +23,7 @@ import torch
 
 import srl_amd
 from srl_amd import hip
+from srl_amd.algorithm import rnnpath
 from srl_amd.algorithm.rnnpath import CELLS, bufs_of
 
 DEV = "cuda:0"
@@ -71,6 +75,56 @@ def loop_case(kind, H, N, C=40, reps=9, inner=10):
     print(kind, H, N, json.dumps(rec), flush=True)
 
 
+def bwd_loop_case(kind, H, N, C=40, reps=9, inner=10):
+    G = 4 if kind == "lstm" else 3
+    g = torch.Generator().manual_seed(2)
+    rn = lambda *s: torch.randn(*s, generator=g).to(DEV)
+    w, b, dy = rn(G * H, H) / H ** 0.5, 0.1 * rn(G * H), rn(C, N, H)
+    pre, gh, hin, cin, y, cnew = rn(C, N, G * H), rn(C, N, 3 * H), 0.5 * rn(C, N, H), 0.5 * rn(C, N, H), rn(C, N, H), rn(C, N, H)
+    rs = (torch.rand(C, N, generator=g) < 0.1).to(torch.uint8).to(DEV)
+    rp = lambda c: rs.data_ptr() + c * N
+    k = CELLS[kind]
+    s = bufs_of(kind, gi=pre, gh=gh, hin=hin, cin=cin, cnew=cnew, y=y)
+    k.fwd(s, w.data_ptr(), b.data_ptr(), rp, N, H, C, path="fused")
+    saved = (pre.clone(), gh.clone())   # the backward overwrites the saved gates: every repetition starts from these
+    carries, per = [torch.zeros(N, H, device=DEV) for _ in k.carries], len(k.carries) // 2
+    carry = lambda c: [x.data_ptr() for x in carries[per * (c & 1):][:per]]
+
+    def run(path):
+        k.bwd(s, dy.data_ptr(), H, w.data_ptr(), rp, N, H, C, carry, path=path)
+
+    def restore():
+        pre.copy_(saved[0]), gh.copy_(saved[1])
+
+    res = {}
+    for path in ("cell", "step"):   # results agree (same inputs): d pre / d gi of both ways
+        restore()
+        run(path)
+        torch.cuda.synchronize()
+        res[path] = pre.clone()
+    diff = float((res["step"] - res["cell"]).abs().max())
+    times = {"cell": [], "step": []}
+    for path in times:   # warm up
+        for _ in range(3):
+            run(path)
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        for path in times:
+            restore()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                run(path)
+            e1.record()
+            torch.cuda.synchronize()
+            times[path].append(e0.elapsed_time(e1) / inner * 1e3)   # us per loop of C steps
+    rec = {("step_bwd" if p == "step" else "cell_gemm"): dict(median_us=statistics.median(v), min_us=min(v), max_us=max(v))
+           for p, v in times.items()}
+    rec["max_abs_dpre_diff"], rec["max_abs_dpre"] = diff, float(res["cell"].abs().max())
+    out[f"bwd_{kind}_H{H}_N{N}_C{C}"] = rec
+    print("bwd", kind, H, N, json.dumps(rec), flush=True)
+
+
 def update_case(reps=5):
     from srl_amd.api import config, trainer as trainer_api
     from srl_amd.api.env_utils import DiscreteAction
@@ -90,21 +144,23 @@ def update_case(reps=5):
                          on_reset=dev(a["on_reset"]), done=dev(a["done"]), truncated=dev(a["truncated"]), action=DiscreteAction(dev(a["action.x"])),
                          reward=dev(a["reward"]), info_mask=a["info_mask"])
     trainer = trainer_api.make(config.Trainer("q-learning", args=targs), config.Policy("atari-dqn", args=pargs))
-    times = {"0": [], "1": []}
-    for mode in ("0", "1"):
-        hip.RNN_STEP_FUSED = mode == "1"
+    times = {"0": [], "1": [], "step": []}
+    for mode in times:
+        hip.RNN_STEP_FUSED, rnnpath.NAMED = mode != "0", "step" if mode == "step" else None
         trainer.step(sample)
     torch.cuda.synchronize()
     import time
     for _ in range(reps):
-        for mode in ("0", "1"):
-            hip.RNN_STEP_FUSED = mode == "1"
+        for mode in times:
+            hip.RNN_STEP_FUSED, rnnpath.NAMED = mode != "0", "step" if mode == "step" else None
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             trainer.step(sample)   # ends in a device-to-host copy of the statistics
             torch.cuda.synchronize()
             times[mode].append((time.perf_counter() - t0) * 1e3)
-    rec = {("fused" if k == "1" else "two_launch"): dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v)) for k, v in times.items()}
+    rnnpath.NAMED = None
+    rec = {{"0": "two_launch", "1": "fused", "step": "fused_fwd_step_bwd"}[k]: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v))
+           for k, v in times.items()}
     out["qlearning_update_gru512_B64_burn40_chunk40"] = rec
     print("update", json.dumps(rec), flush=True)
 
@@ -115,6 +171,8 @@ if __name__ == "__main__":
     loop_case("lstm", 512, 128)
     loop_case("gru", 128, 256)
     loop_case("lstm", 128, 256)
+    for shape in (("gru", 512, 128), ("lstm", 512, 128), ("gru", 128, 256), ("lstm", 128, 256)):
+        bwd_loop_case(*shape)
     update_case()
     if "--out" in sys.argv:
         with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:

@@ -38,22 +38,28 @@ RnnSaved = NamedTuple("RnnSaved", [("layers", list), ("ctx", RnnCtx), ("cm", boo
 # loop below, the kernel tests and scripts/rnn_step_bench.py all run these.  `s`: the cell's `Bufs` of raw device addresses;
 # `r(c)`: the address of step c's reset flags, or None; `path`: one of PATHS, by default `time_loop_path`'s.  The backward of
 # "fused" is "cell"'s (the fused step saves what the cell saves); it writes d h_in (d c_in) of step c to the addresses
-# `carry(c)` gives, which stay untouched until step c - 1 has read them.
-PATHS = ("seq", "wseq", "fused", "cell")
+# `carry(c)` gives, which stay untouched until step c - 1 has read them.  "step" (csrc/rnn_step.hip's backward step) has "fused"'s
+# forward and one launch per backward step: the launch for step c forms d gates(c + 1) . W_hh and runs the cell of step c, so
+# under "step" the buffers of `carry(c)` hold GRU's `direct` = dh z (not d h_in) and LSTM's d c_in (its dh slot is unused), d h_in
+# of step 0 is never formed, and `ld_dy > H` and `dy = None` (zeros) are taken as the chunk kernels take them.
+PATHS = ("seq", "wseq", "fused", "cell", "step")
 
 # The path the layer loop below names for every layer; None: `time_loop_path` chooses.  A plain attribute, like
 # `hip.RNN_STEP_FUSED` (the set of environment switches is closed).  "wseq" (csrc/rnn_wseq.hip, H = 128: W_hh stationary in
 # registers, the chunk in one launch per direction) runs only where it is named: the default at that width is a measured
-# decision that has not been taken.
+# decision that has not been taken.  "step" likewise runs only where it is named, at the fused step's widths: whether it becomes
+# the backward of "fused" is a decision for its measurements.
 NAMED: Optional[str] = None
 
 
 def time_loop_path(kind: str, H: int, named: Optional[str] = None) -> str:
     """Where the path is chosen: the whole chunk in one launch (csrc/rnn_seq.hip) where the library has the width; else W_hh h and
     the cell of a step in one launch (csrc/rnn_step.hip); else srl_gemm plus a cell of csrc/gru.hip per step.  ``named``: the
-    caller's choice instead (the tests' and the bench's reference sides; "wseq", csrc/rnn_wseq.hip, is taken no other way)."""
+    caller's choice instead (the tests' and the bench's reference sides; "wseq", csrc/rnn_wseq.hip, and "step", the one-launch
+    backward step of csrc/rnn_step.hip, are taken no other way)."""
     assert named is None or named in PATHS, named
     assert named != "wseq" or hip.rnn_wseq_supported(kind, H), (kind, H)
+    assert named != "step" or hip.lib().srl_rnn_step_supported(1 if kind == "lstm" else 0, int(H)), (kind, H)
     return named or ("seq" if hip.rnn_seq_supported(kind, H) else "fused" if hip.rnn_step_supported(kind, H) else "cell")
 
 
@@ -71,7 +77,7 @@ class _Lstm:
         for c in range(C):
             o4, o1, o1n, nxt = 4 * c * N * 4 * H, 4 * c * N * H, 4 * (c + 1) * N * H, c + 1 < C
             out = (r(c + 1) if nxt else None, N, H, y + o1, cnew + o1, hin + o1n if nxt else None, cin + o1n if nxt else None)
-            if path == "fused":   # the product and the cell in one launch
+            if path in ("fused", "step"):   # the product and the cell in one launch
                 hip.lstm_step_fwd(pre + o4, w_hh, b_hh, hin + o1, cin + o1, *out)
                 continue
             hip.gemm(N, 4 * H, H, hin + o1, H, 0, w_hh, H, 0, pre + o4, 4 * H, bias=b_hh, accumulate=True)
@@ -79,10 +85,17 @@ class _Lstm:
 
     def bwd(self, s, dy, ld_dy, w_hh, r, N, H, C, carry, path=None):
         path = time_loop_path(self.kind, H, path)
-        assert path in ("seq", "wseq") or ld_dy == H, "the per-step cells read d y in rows of H"
+        assert path in ("seq", "wseq", "step") or ld_dy == H, "the per-step cells read d y in rows of H"
         pre, _, cin, cnew, _ = s
         if path in ("seq", "wseq"):
             return (hip.lstm_seq_bwd if path == "seq" else hip.lstm_wseq_bwd)(dy, ld_dy, pre, w_hh, cin, cnew, r(0), N, H, C)
+        if path == "step":   # the launch for step c: d pre(c + 1) . W_hh, then the cell of step c
+            nxt = (None, None, None)   # d pre, d c_in and the reset flags of step c + 1
+            for c in range(C - 1, -1, -1):
+                o4, o1, (_, dc) = 4 * c * N * 4 * H, 4 * c * N * H, carry(c)
+                hip.lstm_step_bwd(dy and dy + 4 * c * N * ld_dy, ld_dy, *nxt, w_hh, pre + o4, cin + o1, cnew + o1, N, H, dc)
+                nxt = (pre + o4, dc, r(c))
+            return
         ch = cc = None
         for c in range(C - 1, -1, -1):
             o4, o1, (dh, dc) = 4 * c * N * 4 * H, 4 * c * N * H, carry(c)
@@ -105,7 +118,7 @@ class _Gru:
         for c in range(C):
             o3, o1, nxt = 4 * c * N * 3 * H, 4 * c * N * H, c + 1 < C
             out = (r(c + 1) if nxt else None, N, H, y + o1, hin + 4 * (c + 1) * N * H if nxt else None)
-            if path == "fused":   # the product and the cell in one launch
+            if path in ("fused", "step"):   # the product and the cell in one launch
                 hip.gru_step_fwd(gi + o3, gh + o3, w_hh, b_hh, hin + o1, *out)
                 continue
             hip.gemm(N, 3 * H, H, hin + o1, H, 0, w_hh, H, 0, gh + o3, 3 * H, bias=b_hh)
@@ -113,10 +126,17 @@ class _Gru:
 
     def bwd(self, s, dy, ld_dy, w_hh, r, N, H, C, carry, path=None):
         path = time_loop_path(self.kind, H, path)
-        assert path in ("seq", "wseq") or ld_dy == H, "the per-step cells read d y in rows of H"
+        assert path in ("seq", "wseq", "step") or ld_dy == H, "the per-step cells read d y in rows of H"
         gi, gh, hin, _ = s
         if path in ("seq", "wseq"):
             return (hip.gru_seq_bwd if path == "seq" else hip.gru_wseq_bwd)(dy, ld_dy, gi, gh, w_hh, hin, r(0), N, H, C)
+        if path == "step":   # the launch for step c: d gh(c + 1) . W_hh, then the cell of step c
+            nxt = (None, None, None)   # d gh, direct and the reset flags of step c + 1
+            for c in range(C - 1, -1, -1):
+                o3, o1, (cur,) = 4 * c * N * 3 * H, 4 * c * N * H, carry(c)
+                hip.gru_step_bwd(dy and dy + 4 * c * N * ld_dy, ld_dy, *nxt, w_hh, gi + o3, gh + o3, hin + o1, N, H, cur)
+                nxt = (gh + o3, cur, r(c))
+            return
         prev = None
         for c in range(C - 1, -1, -1):
             o3, o1, (cur,) = 4 * c * N * 3 * H, 4 * c * N * H, carry(c)

@@ -354,6 +354,23 @@ def lstm_step_fwd(pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_next_ptr, N, H, y
                                    hin_next_ptr, cin_next_ptr), "srl_lstm_step_fwd")
 
 
+def _step_bwd_flops(gates, N, H, has_next):
+    return 2.0 * int(N) * gates * int(H) * int(H) if has_next else 0.0   # d gates(t+1) . W_hh; a chunk's last step has none
+
+
+def gru_step_bwd(dy_ptr, ld_dy, dgh_next_ptr, direct_next_ptr, reset_next_ptr, w_hh, gates_ptr, gh_ptr, hin_ptr, N, H, direct_ptr):
+    """The backward of step t in one launch (csrc/rnn_step.hip): d gh(t+1) . W_hh, then the cell backward of step t."""
+    with _scope("gru_step_bwd", _step_bwd_flops(3, N, H, dgh_next_ptr), "f32"):
+        _check(lib().srl_gru_step_bwd(_stream(), dy_ptr, int(ld_dy), dgh_next_ptr, direct_next_ptr, reset_next_ptr, w_hh, gates_ptr,
+                                      gh_ptr, hin_ptr, int(N), int(H), direct_ptr), "srl_gru_step_bwd")
+
+
+def lstm_step_bwd(dy_ptr, ld_dy, dpre_next_ptr, dc_next_ptr, reset_next_ptr, w_hh, gates_ptr, cin_ptr, cnew_ptr, N, H, dc_in_ptr):
+    with _scope("lstm_step_bwd", _step_bwd_flops(4, N, H, dpre_next_ptr), "f32"):
+        _check(lib().srl_lstm_step_bwd(_stream(), dy_ptr, int(ld_dy), dpre_next_ptr, dc_next_ptr, reset_next_ptr, w_hh, gates_ptr,
+                                       cin_ptr, cnew_ptr, int(N), int(H), dc_in_ptr), "srl_lstm_step_bwd")
+
+
 def lstm_seq_fwd(pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_ptr, N, H, C, y_ptr, cnew_ptr):
     _check(lib().srl_lstm_seq_fwd(_stream(), pre_ptr, w_hh, b_hh, hin_ptr, cin_ptr, reset_ptr, int(N), int(H), int(C), y_ptr, cnew_ptr),
            "srl_lstm_seq_fwd")
