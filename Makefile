@@ -18,6 +18,9 @@ $(OBJD)/rnn_wseq.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops -R
 # ln_heads_wide.hip likewise: head weights and their gradient sums resident in registers beside the MFMAs, no scratch.
 $(OBJD)/ln_heads_wide.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops -Rpass-analysis=kernel-resource-usage
 
+# attn_xl.hip: a wavefront holds the whole 32 x F score strip (up to 6 accumulator blocks) beside its fragments, no scratch.
+$(OBJD)/attn_xl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+
 $(OBJD)/%.o: srl_amd/csrc/%.hip $(HDRS)
 	@mkdir -p $(OBJD)
 	$(HIPCC) $(FLAGS) -c -o $@ $<

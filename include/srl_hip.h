@@ -1110,6 +1110,36 @@ int srl_instr_lstm_bwd(void* stream, const srl_instr_lstm* d, int64_t rows, cons
                        int64_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Relative multi-head attention of Transformer-XL (csrc/attn_xl.hip): what AttentionXL.forward does between its projections
+ * (legacy/algorithm/modules/gtrxl.py:140-169 -- _rel_shift -- and 193-231), one launch per direction, float32 throughout.
+ * C current steps, M memory steps, F = M + C; per batch row b < N and head h < nh, scale = dh^-0.5:
+ *   s[i, j] = scale ((q[i] + u[h]) . k[j] + (q[i] + v[h]) . r[j + C - 1 - i])   for j <= i + M, else -inf
+ *   out[i]  = sum_j softmax_j(s)[i, j] val[j]
+ * (r[j + C - 1 - i] is _rel_shift in closed form; where its reshape wraps round lies under the mask.)  No dropout, no reset
+ * flags: memory rows a reset has zeroed are attended like any other.
+ * Layouts (floats; every leading dimension a multiple of 4 and at least nh dh, every pointer 16-byte aligned):
+ *   q, out, d_out, dq  [C, N, ld]; k, val (dk, dval) [F, N, ldkv] behind their own pointers and ONE leading dimension -- the
+ *   two halves of an attention_kv product are passed in place; r, dr [F, ld]; u, v, du, dv [nh, dh] dense;
+ *   lse [N, nh, C] dense: the row log-sum-exp, all the forward keeps for the backward.
+ * srl_attn_xl_fwd writes out and lse.  srl_attn_xl_bwd recomputes the probabilities from lse and WRITES (does not add to)
+ *   dq, dk, dval, dr, du, dv.  dr, du, dv sum over the batch: per-workgroup slabs in `workspace` (at least
+ *   srl_attn_xl_bwd_workspace bytes, 16-byte aligned, need not be cleared), folded in slab order by a second launch; no float
+ *   atomics anywhere: two calls on the same inputs give the same bits.  Columns beyond nh dh of a row are never written.
+ * srl_attn_xl_supported: 1 when dh is 16, 32 or 64, 1 <= nh <= 8, 1 <= C <= 64, M >= 0 and M + C <= 192, else 0; the launches
+ *   refuse (-EINVAL, nothing runs) what it refuses.  C = 1 (a rollout step over memory) and M = 0 (causal) are ordinary cases.
+ * srl_attn_xl_bwd_workspace: bytes = slabs nh (F + 2) dh 4 with slabs = min(N, 1024 / nh) workgroups per head (workgroup w
+ *   of a head takes the batch rows w, w + slabs, ...); -1 for an unsupported shape or N < 1. */
+int srl_attn_xl_supported(int nh, int dh, int C, int M);
+int srl_attn_xl_fwd(void* stream, const float* q, int64_t ldq, const float* k, const float* val, int64_t ldkv, const float* r,
+                    int64_t ldr, const float* u, const float* v, int64_t N, int nh, int dh, int C, int M, float* out, int64_t ldo,
+                    float* lse);
+int64_t srl_attn_xl_bwd_workspace(int nh, int dh, int C, int M, int64_t N);
+int srl_attn_xl_bwd(void* stream, const float* d_out, int64_t lddo, const float* q, int64_t ldq, const float* k, const float* val,
+                    int64_t ldkv, const float* r, int64_t ldr, const float* u, const float* v, const float* lse, int64_t N, int nh,
+                    int dh, int C, int M, float* dq, int64_t lddq, float* dk, float* dval, int64_t lddkv, float* dr, int64_t lddr,
+                    float* du, float* dv, void* workspace, int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Native step driver (launch-bound configurations).  The device part of MultiAgentPPO.step (mappo.py:219-328) is
  * captured once into a hipGraph; a plan = that executable graph (hipGraphExec_t as void*) + its static input leaves +
  * its outputs.  srl_step_plan_run enqueues, on `stream`: one copy per input from srcs[i] (host or device memory; NULL

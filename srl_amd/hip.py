@@ -1147,6 +1147,37 @@ def entity_attn_bwd(d: EntityAttn, x_self, x_keys, mask, rows, dout_ptr, lddo):
         _check(lib().srl_entity_attn_bwd(_stream(), ctypes.byref(d), int(rows), dout_ptr, int(lddo)), "srl_entity_attn_bwd")
 
 
+def attn_xl_supported(nh, dh, C, M) -> bool:
+    """Whether Transformer-XL's relative attention runs as one launch per direction for ``nh`` heads of width ``dh``, ``C`` current
+    and ``M`` memory steps (csrc/attn_xl.hip; needs the library, not a GPU)."""
+    return bool(lib().srl_attn_xl_supported(int(nh), int(dh), int(C), int(M)))
+
+
+def attn_xl_bwd_workspace(nh, dh, C, M, N) -> int:
+    """Bytes of workspace ``attn_xl_bwd`` wants for ``N`` batch rows: one slab of (C + M + 2) dh floats per head and workgroup
+    (``srl_attn_xl_bwd_workspace``); -1 for an unsupported shape."""
+    return int(lib().srl_attn_xl_bwd_workspace(int(nh), int(dh), int(C), int(M), int(N)))
+
+
+def attn_xl_fwd(q_ptr, ldq, k_ptr, val_ptr, ldkv, r_ptr, ldr, u_ptr, v_ptr, N, nh, dh, C, M, out_ptr, ldo, lse_ptr):
+    """out [C, N, ldo] = softmax(scale ((q + u) k^T + shift((q + v) r^T)), causal over M memory steps) val per batch row and head;
+    lse [N, nh, C] is what ``attn_xl_bwd`` needs.  k and val [C + M, N, ldkv] share a leading dimension: the two halves of one
+    key / value product are passed in place."""
+    with _scope("attn_xl_fwd", 3 * 2.0 * N * nh * C * (C + M) * dh, "f32"):   # q k^T, q r^T, p val
+        _check(lib().srl_attn_xl_fwd(_stream(), q_ptr, int(ldq), k_ptr, val_ptr, int(ldkv), r_ptr, int(ldr), u_ptr, v_ptr, int(N),
+                                     int(nh), int(dh), int(C), int(M), out_ptr, int(ldo), lse_ptr), "srl_attn_xl_fwd")
+
+
+def attn_xl_bwd(dout_ptr, lddo, q_ptr, ldq, k_ptr, val_ptr, ldkv, r_ptr, ldr, u_ptr, v_ptr, lse_ptr, N, nh, dh, C, M, dq_ptr, lddq,
+                dk_ptr, dval_ptr, lddkv, dr_ptr, lddr, du_ptr, dv_ptr, ws_ptr, ws_bytes):
+    """WRITES dq, dk, dval, dr [C + M, lddr], du and dv [nh, dh] given d out; the probabilities are recomputed from ``lse``.  dr, du
+    and dv are summed over the batch in slabs of the workspace folded in a fixed order: the same inputs give the same bits."""
+    with _scope("attn_xl_bwd", 8 * 2.0 * N * nh * C * (C + M) * dh, "f32"):   # the forward's two score products again + 6 of its own
+        _check(lib().srl_attn_xl_bwd(_stream(), dout_ptr, int(lddo), q_ptr, int(ldq), k_ptr, val_ptr, int(ldkv), r_ptr, int(ldr), u_ptr,
+                                     v_ptr, lse_ptr, int(N), int(nh), int(dh), int(C), int(M), dq_ptr, int(lddq), dk_ptr, dval_ptr,
+                                     int(lddkv), dr_ptr, int(lddr), du_ptr, dv_ptr, ws_ptr, int(ws_bytes)), "srl_attn_xl_bwd")
+
+
 def instr_lstm_desc(V, Ed, H, L, params=None, grads=None) -> InstrLstm:
     """``srl_instr_lstm`` for a vocabulary of ``V`` rows of ``Ed`` columns, ``H`` LSTM units and ``L`` tokens per row; ``params`` /
     ``grads``: name in ``INSTR_LSTM_PARAMS`` -> raw device pointer.  The tokens are set per call (``instr_lstm_fwd`` / ``_bwd``)."""
