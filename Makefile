@@ -21,6 +21,9 @@ $(OBJD)/ln_heads_wide.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-o
 # attn_xl.hip: a wavefront holds the whole 32 x F score strip (up to 6 accumulator blocks) beside its fragments, no scratch.
 $(OBJD)/attn_xl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 
+# gtrxl_gate.hip: six accumulator blocks (two-level sums) beside two weight fragments within 256 registers a lane, no scratch.
+$(OBJD)/gtrxl_gate.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+
 $(OBJD)/%.o: srl_amd/csrc/%.hip $(HDRS)
 	@mkdir -p $(OBJD)
 	$(HIPCC) $(FLAGS) -c -o $@ $<

@@ -1140,6 +1140,39 @@ int srl_attn_xl_bwd(void* stream, const float* d_out, int64_t lddo, const float*
                     float* du, float* dv, void* workspace, int64_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * GTrXL's GRU-style gating unit (csrc/gtrxl_gate.hip): GRUGatingUnit.forward (legacy/algorithm/modules/gtrxl.py:44-84; gate1 and
+ * gate2 of every layer, :317 and :320) and its backward, one launch per direction, float32 throughout.  Per row of [rows, D]:
+ *   r = s(y Wr^T + x Ur^T)   z = s(y Wz^T + x Uz^T - bg)   h = tanh(y Wg^T + (r o x) Ug^T)   g = (1 - z) o x + z o h
+ * Parameters, packed as the GRU kernels pack theirs: w_y = Wr | Wz | Wg and w_x = Ur | Uz | Ug, each [3D, D] row-major (torch
+ * Linear weights stacked along the output dimension, dense); bg [D].
+ * Layouts (floats; every leading dimension a multiple of 4, at least the payload width and at most 2^22 -- a tile is addressed
+ * with 32-bit offsets --, every pointer 16-byte aligned):
+ *   x, y, g, dg, dx, dy, rx [rows, ld] with D payload columns; gates [rows, ldgates] with 3D: r | z | h.
+ * srl_gtrxl_gate_fwd writes g and, when `gates` is non-NULL, r | z | h for the backward (a rollout passes NULL and nothing else is
+ *   stored).  g must not alias x or y.
+ * srl_gtrxl_gate_bwd, given dg and what the forward saved:
+ *   a_g = dg o z o (1 - h^2)   a_z = dg o (h - x) o z (1 - z)   t = a_g Ug   a_r = t o x o r (1 - r)   A = a_r | a_z | a_g
+ *   dy = A w_y   dx = dg o (1 - z) + t o r + A[:, :2D] w_x[:2D]   d_bg = - sum over rows of a_z
+ *   It WRITES (does not add to) dx, dy and d_bg [D], overwrites `gates` in place with A, and writes rx = r o x when `rx` is
+ *   non-NULL: the weight gradients are then dw_y = A^T y, dw_x[:2D] = A[:, :2D]^T x, dw_x[2D:] = a_g^T rx -- three srl_gemm calls in
+ *   the wgrad form above (hip.gtrxl_gate_wgrad).  y is not read by the launch (it belongs to those products); it is checked like
+ *   x.  d_bg sums over rows: one slab of D floats per workgroup in `workspace` (at least srl_gtrxl_gate_bwd_workspace bytes,
+ *   16-byte aligned, need not be cleared), folded in slab order by a second launch; no float atomics anywhere: two calls on the
+ *   same inputs give the same bits.  Columns beyond the payload and rows beyond `rows` are never written.
+ * srl_gtrxl_gate_supported: 1 when D is 64, 128 or 256, else 0; the launches refuse (-EINVAL, nothing runs) what it refuses, a
+ *   short workspace and a bad leading dimension.  Any rows >= 1 (the forward also takes rows == 0 and does nothing).
+ * srl_gtrxl_gate_bwd_workspace: bytes = groups D 4 with groups = min(ceil(rows / (8192 / D)), 256) workgroups (the backward's row
+ *   tile is 8192 / D rows; workgroup w takes the tiles w, w + groups, ...); -1 for an unsupported D or rows < 1. */
+int srl_gtrxl_gate_supported(int D);
+int srl_gtrxl_gate_fwd(void* stream, const float* x, int64_t ldx, const float* y, int64_t ldy, const float* w_y, const float* w_x,
+                       const float* bg, int64_t rows, int D, float* g, int64_t ldg, float* gates, int64_t ldgates);
+int64_t srl_gtrxl_gate_bwd_workspace(int D, int64_t rows);
+int srl_gtrxl_gate_bwd(void* stream, const float* dg, int64_t lddg, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                       const float* w_y, const float* w_x, float* gates, int64_t ldgates, int64_t rows, int D, float* dx,
+                       int64_t lddx, float* dy, int64_t lddy, float* rx, int64_t ldrx, float* d_bg, void* workspace,
+                       int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Native step driver (launch-bound configurations).  The device part of MultiAgentPPO.step (mappo.py:219-328) is
  * captured once into a hipGraph; a plan = that executable graph (hipGraphExec_t as void*) + its static input leaves +
  * its outputs.  srl_step_plan_run enqueues, on `stream`: one copy per input from srcs[i] (host or device memory; NULL

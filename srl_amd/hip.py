@@ -1178,6 +1178,47 @@ def attn_xl_bwd(dout_ptr, lddo, q_ptr, ldq, k_ptr, val_ptr, ldkv, r_ptr, ldr, u_
                                      int(lddkv), dr_ptr, int(lddr), du_ptr, dv_ptr, ws_ptr, int(ws_bytes)), "srl_attn_xl_bwd")
 
 
+def gtrxl_gate_supported(D) -> bool:
+    """Whether GTrXL's GRU-style gating unit runs as one launch per direction at width ``D`` (csrc/gtrxl_gate.hip: 64, 128, 256;
+    needs the library, not a GPU)."""
+    return bool(lib().srl_gtrxl_gate_supported(int(D)))
+
+
+def gtrxl_gate_bwd_workspace(D, rows) -> int:
+    """Bytes of workspace ``gtrxl_gate_bwd`` wants for ``rows`` rows: one slab of D floats per workgroup
+    (``srl_gtrxl_gate_bwd_workspace``); -1 for an unsupported width or rows < 1."""
+    return int(lib().srl_gtrxl_gate_bwd_workspace(int(D), int(rows)))
+
+
+def gtrxl_gate_fwd(x_ptr, ldx, y_ptr, ldy, w_y_ptr, w_x_ptr, bg_ptr, rows, D, g_ptr, ldg, gates_ptr=None, ldgates=0):
+    """g [rows, ldg] = (1 - z) x + z h with r = s(y Wr^T + x Ur^T), z = s(y Wz^T + x Uz^T - bg), h = tanh(y Wg^T + (r x) Ug^T);
+    w_y = Wr | Wz | Wg and w_x = Ur | Uz | Ug, [3D, D] each.  ``gates_ptr`` [rows, ldgates] takes r | z | h for ``gtrxl_gate_bwd``;
+    None (a rollout) stores nothing else."""
+    with _scope("gtrxl_gate_fwd", 12.0 * rows * D * D, "f32"):   # six D x D products
+        _check(lib().srl_gtrxl_gate_fwd(_stream(), x_ptr, int(ldx), y_ptr, int(ldy), w_y_ptr, w_x_ptr, bg_ptr, int(rows), int(D),
+                                        g_ptr, int(ldg), gates_ptr, int(ldgates)), "srl_gtrxl_gate_fwd")
+
+
+def gtrxl_gate_bwd(dg_ptr, lddg, x_ptr, ldx, y_ptr, ldy, w_y_ptr, w_x_ptr, gates_ptr, ldgates, rows, D, dx_ptr, lddx, dy_ptr, lddy,
+                   rx_ptr, ldrx, d_bg_ptr, ws_ptr, ws_bytes):
+    """WRITES dx, dy and d_bg [D] given dg; ``gates`` (r | z | h of the forward) is overwritten with A = a_r | a_z | a_g and
+    ``rx_ptr`` (or None) takes r x: what ``gtrxl_gate_wgrad`` needs.  d_bg is summed in slabs of the workspace folded in a fixed
+    order: the same inputs give the same bits."""
+    with _scope("gtrxl_gate_bwd", 12.0 * rows * D * D, "f32"):   # a_g Ug (D), A w_y (3D), A[:, :2D] w_x[:2D] (2D)
+        _check(lib().srl_gtrxl_gate_bwd(_stream(), dg_ptr, int(lddg), x_ptr, int(ldx), y_ptr, int(ldy), w_y_ptr, w_x_ptr, gates_ptr,
+                                        int(ldgates), int(rows), int(D), dx_ptr, int(lddx), dy_ptr, int(lddy), rx_ptr, int(ldrx),
+                                        d_bg_ptr, ws_ptr, int(ws_bytes)), "srl_gtrxl_gate_bwd")
+
+
+def gtrxl_gate_wgrad(A_ptr, ldA, x_ptr, ldx, y_ptr, ldy, rx_ptr, ldrx, rows, D, dw_y_ptr, dw_x_ptr, accumulate=False):
+    """The gate's weight gradients from what ``gtrxl_gate_bwd`` left, as three ``gemm`` calls in the header's wgrad form:
+    dw_y [3D, D] = A^T y, dw_x[:2D] = A[:, :2D]^T x, dw_x[2D:] = a_g^T rx (the packed layout is what lets the library's own
+    product serve it)."""
+    gemm(3 * D, D, rows, A_ptr, ldA, 1, y_ptr, ldy, 1, dw_y_ptr, D, accumulate=accumulate)
+    gemm(2 * D, D, rows, A_ptr, ldA, 1, x_ptr, ldx, 1, dw_x_ptr, D, accumulate=accumulate)
+    gemm(D, D, rows, A_ptr + 8 * D, ldA, 1, rx_ptr, ldrx, 1, dw_x_ptr + 8 * D * D, D, accumulate=accumulate)
+
+
 def instr_lstm_desc(V, Ed, H, L, params=None, grads=None) -> InstrLstm:
     """``srl_instr_lstm`` for a vocabulary of ``V`` rows of ``Ed`` columns, ``H`` LSTM units and ``L`` tokens per row; ``params`` /
     ``grads``: name in ``INSTR_LSTM_PARAMS`` -> raw device pointer.  The tokens are set per call (``instr_lstm_fwd`` / ``_bwd``)."""
