@@ -24,6 +24,9 @@ $(OBJD)/attn_xl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 # gtrxl_gate.hip: six accumulator blocks (two-level sums) beside two weight fragments within 256 registers a lane, no scratch.
 $(OBJD)/gtrxl_gate.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 
+# gtrxl_qkv.hip: six accumulator blocks forward, four backward beside sixteen registers of xhat, no scratch.
+$(OBJD)/gtrxl_qkv.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+
 $(OBJD)/%.o: srl_amd/csrc/%.hip $(HDRS)
 	@mkdir -p $(OBJD)
 	$(HIPCC) $(FLAGS) -c -o $@ $<

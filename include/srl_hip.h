@@ -1173,6 +1173,47 @@ int srl_gtrxl_gate_bwd(void* stream, const float* dg, int64_t lddg, const float*
                        int64_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * The front of a GTrXL layer (csrc/gtrxl_qkv.hip): memory || inputs, layernorm1, attention_kv and attention_q
+ * (legacy/algorithm/modules/gtrxl.py:313-314 and 196-198) with the reset product of AutoResetRNN.forward (autoreset_rnn.py:59),
+ * one launch per direction, float32 throughout.  M memory steps, C current steps, F = M + C, N batch rows; the F N rows are
+ * time-major as srl_attn_xl_fwd wants them.  Row (t, n) of `full` is keep[n] * mem[t, n] for t < M, else x[t - M, n]:
+ *   x1 = LayerNorm(full; gamma, beta, eps 1e-5)   kv = x1 w_kv^T + b_kv   q = x w_q^T + b_q   (q from the RAW current rows)
+ * Parameters as the torch modules hold them: gamma, beta [D]; w_kv [2D, D] row-major dense (rows 0 .. D - 1 the key, the rest
+ * the value), b_kv [2D]; w_q [D, D], b_q [D].  keep is a float [N] MULTIPLIER (the reference's hxs * masks; non-binary values
+ * follow the same rule), or NULL for all ones.  mem is not read when M == 0 and may then be NULL.
+ * Layouts (floats; every leading dimension a multiple of 4, at least the payload width and at most 2^22 -- a tile is addressed
+ * with 32-bit offsets --, every pointer 16-byte aligned; (M + C) N at most 2^31 - 1):
+ *   mem [M, N, ldm], x, q, dq, dx [C, N, ld], x1 [F, N, ldx1] with D payload columns; kv, dkv [F, N, ld] with 2D: key | value, so
+ *   that srl_attn_xl_fwd takes k = kv and val = kv + D under the one ldkv, and dkv is dk | dval as srl_attn_xl_bwd writes them;
+ *   stats [F N, 2] dense: mean, rstd of every row.
+ * srl_gtrxl_qkv_fwd writes kv and q and, when they are non-NULL, x1 (the operand of dW_kv) and stats (a rollout passes NULL for
+ *   both and nothing else is stored).
+ * srl_gtrxl_qkv_bwd, given dkv, dq and stats, with xhat recomputed from mem, keep, x and stats (never from x1: a zero in gamma
+ *   costs nothing):
+ *   dx1 = dkv w_kv (all F N rows)   dgamma = sum_rows dx1 o xhat   dbeta = sum_rows dx1   (memory rows included)
+ *   db_kv = sum_rows dkv   db_q = sum_rows dq   dx[i, n] = LN'(dx1)[M + i, n] + dq[i, n] w_q   (current rows only)
+ *   No gradient reaches mem (the reference detaches it).  It WRITES (does not add to) dx, dgamma, dbeta [D], db_kv [2D] and
+ *   db_q [D].  The five row sums go through one slab of 5D floats per workgroup in `workspace` (at least
+ *   srl_gtrxl_qkv_bwd_workspace bytes, 16-byte aligned, need not be cleared), folded in slab order by a second launch; no float
+ *   atomics anywhere: two calls on the same inputs give the same bits.  The weight gradients are dW_kv = dkv^T x1 and
+ *   dW_q = dq^T x: two srl_gemm calls in the wgrad form above (hip.gtrxl_qkv_wgrad).
+ *   Columns beyond the payload and rows beyond the last are never written.
+ * srl_gtrxl_qkv_supported: 1 when D is 64, 128 or 256 (the attention width is nh dh = D), else 0; the launches refuse (-EINVAL,
+ *   nothing runs) what it refuses, M < 0, C < 1, N < 1, a short workspace and a bad leading dimension.
+ * srl_gtrxl_qkv_bwd_workspace: bytes = groups 5 D 4 with groups = min(ceil(rows / (8192 / D)), 256) workgroups for rows = F N
+ *   (the row tile is 8192 / D rows; workgroup w takes the tiles w, w + groups, ...); -1 for an unsupported D or rows < 1. */
+int srl_gtrxl_qkv_supported(int D);
+int srl_gtrxl_qkv_fwd(void* stream, const float* mem, int64_t ldm, const float* x, int64_t ldx, const float* keep,
+                      const float* gamma, const float* beta, const float* w_kv, const float* b_kv, const float* w_q,
+                      const float* b_q, int M, int C, int64_t N, int D, float* kv, int64_t ldkv, float* q, int64_t ldq, float* x1,
+                      int64_t ldx1, float* stats);
+int64_t srl_gtrxl_qkv_bwd_workspace(int D, int64_t rows);
+int srl_gtrxl_qkv_bwd(void* stream, const float* dkv, int64_t lddkv, const float* dq, int64_t lddq, const float* mem, int64_t ldm,
+                      const float* x, int64_t ldx, const float* keep, const float* stats, const float* gamma, const float* w_kv,
+                      const float* w_q, int M, int C, int64_t N, int D, float* dx, int64_t lddx, float* dgamma, float* dbeta,
+                      float* db_kv, float* db_q, void* workspace, int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Native step driver (launch-bound configurations).  The device part of MultiAgentPPO.step (mappo.py:219-328) is
  * captured once into a hipGraph; a plan = that executable graph (hipGraphExec_t as void*) + its static input leaves +
  * its outputs.  srl_step_plan_run enqueues, on `stream`: one copy per input from srcs[i] (host or device memory; NULL

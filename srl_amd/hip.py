@@ -1219,6 +1219,51 @@ def gtrxl_gate_wgrad(A_ptr, ldA, x_ptr, ldx, y_ptr, ldy, rx_ptr, ldrx, rows, D, 
     gemm(D, D, rows, A_ptr + 8 * D, ldA, 1, rx_ptr, ldrx, 1, dw_x_ptr + 8 * D * D, D, accumulate=accumulate)
 
 
+def gtrxl_qkv_supported(D) -> bool:
+    """Whether the front of a GTrXL layer (memory || inputs, LayerNorm, k / v / q) runs as one launch per direction at width ``D``
+    (csrc/gtrxl_qkv.hip: 64, 128, 256; needs the library, not a GPU)."""
+    return bool(lib().srl_gtrxl_qkv_supported(int(D)))
+
+
+def gtrxl_qkv_bwd_workspace(D, rows) -> int:
+    """Bytes of workspace ``gtrxl_qkv_bwd`` wants for ``rows`` = (M + C) N rows: one slab of 5 D floats per workgroup
+    (``srl_gtrxl_qkv_bwd_workspace``); -1 for an unsupported width or rows < 1."""
+    return int(lib().srl_gtrxl_qkv_bwd_workspace(int(D), int(rows)))
+
+
+def gtrxl_qkv_fwd(mem_ptr, ldm, x_ptr, ldx, keep_ptr, gamma_ptr, beta_ptr, w_kv_ptr, b_kv_ptr, w_q_ptr, b_q_ptr, M, C, N, D, kv_ptr,
+                  ldkv, q_ptr, ldq, x1_ptr=None, ldx1=0, stats_ptr=None):
+    """kv [M + C, N, ldkv] = LayerNorm(cat([keep mem, x])) w_kv^T + b_kv (key | value, as ``attn_xl_fwd`` takes them in place) and
+    q [C, N, ldq] = x w_q^T + b_q from the raw current rows.  ``keep_ptr`` [N] multiplies the memory rows (None: all ones).
+    ``x1_ptr`` [M + C, N, ldx1] and ``stats_ptr`` [(M + C) N, 2] take what ``gtrxl_qkv_wgrad`` / ``gtrxl_qkv_bwd`` need; None (a
+    rollout) stores nothing else."""
+    with _scope("gtrxl_qkv_fwd", (4.0 * (M + C) + 2.0 * C) * N * D * D, "f32"):   # kv over all rows (2D wide), q over the current ones
+        _check(lib().srl_gtrxl_qkv_fwd(_stream(), mem_ptr, int(ldm), x_ptr, int(ldx), keep_ptr, gamma_ptr, beta_ptr, w_kv_ptr, b_kv_ptr,
+                                       w_q_ptr, b_q_ptr, int(M), int(C), int(N), int(D), kv_ptr, int(ldkv), q_ptr, int(ldq), x1_ptr,
+                                       int(ldx1), stats_ptr), "srl_gtrxl_qkv_fwd")
+
+
+def gtrxl_qkv_bwd(dkv_ptr, lddkv, dq_ptr, lddq, mem_ptr, ldm, x_ptr, ldx, keep_ptr, stats_ptr, gamma_ptr, w_kv_ptr, w_q_ptr, M, C, N, D,
+                  dx_ptr, lddx, dgamma_ptr, dbeta_ptr, db_kv_ptr, db_q_ptr, ws_ptr, ws_bytes):
+    """WRITES dx [C, N, lddx] = LN'(dkv w_kv)[current rows] + dq w_q, dgamma, dbeta [D] (summed over ALL rows), db_kv [2D] and
+    db_q [D]; xhat is recomputed from the rows and ``stats``.  No gradient reaches the memory.  The sums go through slabs of the
+    workspace folded in a fixed order: the same inputs give the same bits."""
+    with _scope("gtrxl_qkv_bwd", (4.0 * (M + C) + 2.0 * C) * N * D * D, "f32"):   # dkv w_kv (K = 2D), dq w_q
+        _check(lib().srl_gtrxl_qkv_bwd(_stream(), dkv_ptr, int(lddkv), dq_ptr, int(lddq), mem_ptr, int(ldm), x_ptr, int(ldx), keep_ptr,
+                                       stats_ptr, gamma_ptr, w_kv_ptr, w_q_ptr, int(M), int(C), int(N), int(D), dx_ptr, int(lddx),
+                                       dgamma_ptr, dbeta_ptr, db_kv_ptr, db_q_ptr, ws_ptr, int(ws_bytes)), "srl_gtrxl_qkv_bwd")
+
+
+def gtrxl_qkv_wgrad(dkv_ptr, lddkv, x1_ptr, ldx1, dq_ptr, lddq, x_ptr, ldx, M, C, N, D, dw_kv_ptr, dw_q_ptr, accumulate=False, split_k=1,
+                    workspace=None):
+    """The front's weight gradients as two ``gemm`` calls in the header's wgrad form: dw_kv [2D, D] = dkv^T x1 over all (M + C) N
+    rows, dw_q [D, D] = dq^T x over the C N current ones.  ``split_k`` / ``workspace`` (at least split_k 2 D D floats) go to both
+    products as ``gemm`` takes them: one chain over thousands of rows rounds at the size of its running sum every step, so the
+    trainers cut a long row count into slices of at least 512 rows (``hipnet._split_for``), and so should a caller here."""
+    gemm(2 * D, D, (M + C) * N, dkv_ptr, lddkv, 1, x1_ptr, ldx1, 1, dw_kv_ptr, D, accumulate=accumulate, split_k=split_k, workspace=workspace)
+    gemm(D, D, C * N, dq_ptr, lddq, 1, x_ptr, ldx, 1, dw_q_ptr, D, accumulate=accumulate, split_k=split_k, workspace=workspace)
+
+
 def instr_lstm_desc(V, Ed, H, L, params=None, grads=None) -> InstrLstm:
     """``srl_instr_lstm`` for a vocabulary of ``V`` rows of ``Ed`` columns, ``H`` LSTM units and ``L`` tokens per row; ``params`` /
     ``grads``: name in ``INSTR_LSTM_PARAMS`` -> raw device pointer.  The tokens are set per call (``instr_lstm_fwd`` / ``_bwd``)."""
